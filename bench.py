@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """Rasteriser fwd+bwd throughput on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  ``--full`` adds everything else the
+line can carry, outside the timed region: the cold figure, the blend kernels timed inside the timed region, the per-stage
+profile and the roofline record, the exchange on its own (N > 1), the CPU baseline and the SLAM rates.
 
 A step is one forward+backward render of BASELINE config 5 (2M Gaussians, 1920x1080, synthetic):
 preprocess, binning, blend, blend backward, per-Gaussian backward with the pose Jacobian.  With
@@ -38,6 +42,12 @@ def parse():
                          "utilisation sampler; c4: 200 -- its steps are optimiser iterations, so a long run is a different "
                          "map at the end than at the start)")
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="c5: also the measurements beyond the headline (value_cold, blend_in_timed_region, stages_ms, roofline, "
+                         "the exchange on its own, cpu_baseline, slam); a plain run times the steps and nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="c5: after the timed region, write what the last timed step returned to its caller as DIR/<name>.npy "
+                         "(float32; images in full, per-Gaussian arrays at a fixed seeded sample whose indices go to gaussian_index.npy)")
     ap.add_argument("--settle-steps", type=int, default=60,
                     help="c5: un-timed steps of the same workload run BEFORE the --warmup steps, so that a short run is timed "
                          "with the chip in the power state a long one reaches by itself: the two VALU-bound blend kernels get "
@@ -46,8 +56,8 @@ def parse():
                          "region is still exactly --steps steps between two fences")
     ap.add_argument("--gaussians", type=int, default=2_000_000)
     ap.add_argument("--intrinsics", default="davis_1080p")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-slam", action="store_true", help="skip the short tracking+mapping run (N=1 only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-slam", action="store_true", help="--full: skip the short tracking+mapping run (N=1 only)")
     ap.add_argument("--exact-count", action="store_true",
                     help="read the instance count back every forward (upstream behaviour) instead of capacity mode")
     ap.add_argument("--profile-steps", type=int, default=9,
@@ -71,6 +81,10 @@ def parse():
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 6000 if args.workload == "c5" else 200
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload != "c5":
+        ap.error("--dump-outputs is for the c5 workload")
     return args
 
 
@@ -146,6 +160,34 @@ def cpu_baseline():
             "sample": f"500k Gaussians, 960x540 crop of the 1080p workload (same focal length, same per-pixel "
                       f"density), fwd+bwd, float32, 1 warm-up + median of 3: {dt:.2f} s "
                       f"(min {min(times):.2f}, max {max(times):.2f})"}
+
+
+DUMP_SAMPLE = 1 << 16          # --dump-outputs: Gaussians sampled from larger maps
+DUMP_LIMIT = 64 << 20          # --dump-outputs: bytes in all (1080p images in full + the sample: ~46 MB)
+
+
+def dump_outputs(out_dir, outputs, P):
+    """`outputs`: name -> tensor, as the caller of the timed step received it.  Arrays whose first dimension is the map's P
+    are written at DUMP_SAMPLE Gaussians drawn by a fixed seed (their indices in gaussian_index.npy), the rest in full."""
+    import numpy as np
+    import torch
+    if P > DUMP_SAMPLE:
+        idx = torch.randperm(P, generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values
+    else:
+        idx = torch.arange(P)
+    arrays = {"gaussian_index": idx.numpy().astype(np.float64)}
+    for name, t in outputs.items():
+        t = t.detach()
+        if t.dim() and t.shape[0] == P:
+            t = t[idx.to(t.device)]
+        arrays[name] = t.float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit(f"--dump-outputs: {total} bytes, over the {DUMP_LIMIT}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return total
 
 
 def log(*a):
@@ -320,6 +362,12 @@ def main():
                 e1.record()
                 state.setdefault("exchange_events", []).append((e0, e1))
         state["radii"] = radii
+        if args.dump_outputs:
+            state["outputs"] = {
+                "color": color, "radii": radii, "depth": depth, "opacity": opacity, "n_touched": n_touched,
+                "grad_means3D": xyz.grad, "grad_means2D": means2D.grad, "grad_opacities": opac.grad,
+                "grad_colors_precomp": rgb.grad, "grad_scales": scaling.grad, "grad_rotations": rot.grad,
+                "grad_theta": theta.grad, "grad_rho": rho.grad}
 
     def fence():
         torch.cuda.synchronize()
@@ -361,8 +409,8 @@ def main():
     sync_free = not args.exact_count
     _rast.set_sync_free(sync_free)           # steady state: device-side instance count, no host sync per forward
     # What this process reads WITHOUT the settle steps: the first `cold_steps` steps after the exact one, between two fences
-    # (`value_cold` in the line; they also count as un-timed steps in front of the headline's timed region).
-    cold_steps = min(20, max(0, args.settle_steps)) if args.settle_steps > 0 else 0
+    # (`value_cold` in the line, --full only; they also count as un-timed steps in front of the headline's timed region).
+    cold_steps = min(20, max(0, args.settle_steps)) if (args.full and args.settle_steps > 0) else 0
     dt_cold = None
     if cold_steps:
         fence()
@@ -384,14 +432,14 @@ def main():
     # (short runs: an event per step, so that the line's reader can see how far from the steady state the run was -- the two
     #  blend kernels take ~40 steps of sustained load from process start to reach their speed, see --settle-steps)
     trace = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)] if (args.trace_region and args.steps <= 64 and rank == 0) else None
-    # the two blend kernels, timed INSIDE the timed region (rank 0): the library records a caller's events right around their
+    # the two blend kernels, timed INSIDE the timed region (rank 0, --full): the library records a caller's events right around their
     # launches in up to 8 evenly spaced steps (mgs_debug_set_blend_events: no sync, two event records per kernel: ~4 us of
     # stream time per probed step, i.e. < 0.2 % of a 20-step region; round 4 probed every step of a short run).  The
     # per-stage profile further down synchronises per call, and a device that idles between kernels runs the issue-bound
     # blend kernels ~8 % slower than back-to-back steps do -- this is the figure rocprofv3's average agrees with.
     from monogs_amd import _lib as _L
     hook, probes = _L.load().mgs_debug_set_blend_events, {}
-    if rank == 0:
+    if rank == 0 and args.full:
         for i in range(0, args.steps, max(1, -(-args.steps // 8))):
             probes[i] = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
             for e in probes[i]:
@@ -426,6 +474,9 @@ def main():
         log("blend kernels inside the timed region (HIP events around the launches):", region)
     if sync_free and _rast.check_overflow():
         raise SystemExit("capacity overflow during the timed region: rerun with --exact-count")
+    if args.dump_outputs and rank == 0:
+        nbytes = dump_outputs(args.dump_outputs, state["outputs"], args.gaussians)
+        log(f"outputs of the last timed step written to {args.dump_outputs} ({nbytes / 2**20:.1f} MiB)")
     if args.trace_steps > 0 and rank == 0 and not distributed:
         fence()
         evs = [torch.cuda.Event(enable_timing=True) for _ in range(args.trace_steps + 1)]
@@ -445,9 +496,9 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
 
-    # ---- N > 1: the exchange on its own (events around the collective, every rank runs it; rank 0 reports)
+    # ---- N > 1, --full: the exchange on its own (events around the collective, every rank runs it; rank 0 reports)
     exchange = None
-    if bucket is not None:
+    if bucket is not None and args.full:
         for _ in range(5):
             step(stats="time_exchange")
         torch.cuda.synchronize()
@@ -483,16 +534,17 @@ def main():
                 worst = max(worst, float(d.item()) / max(float(ref.abs().max().item()), 1e-30))
             exchange["max_relative_difference_between_ranks"] = worst
 
-    # ---- per-kernel time, live, with HIP events on the launch stream (separate from the timed region)
+    # ---- --full: per-kernel time, live, with HIP events on the launch stream (separate from the timed region)
     roof = None
     stages = {}
-    # every rank runs the same profile steps (they contain the collective); only rank 0 records stage times
-    import contextlib
-    with (collect_timing() if rank == 0 else contextlib.nullcontext([])) as sink:
-        for _ in range(max(1, args.profile_steps)):
-            step()
-        torch.cuda.synchronize()
-    if rank == 0:
+    if args.full:
+        # every rank runs the same profile steps (they contain the collective); only rank 0 records stage times
+        import contextlib
+        with (collect_timing() if rank == 0 else contextlib.nullcontext([])) as sink:
+            for _ in range(max(1, args.profile_steps)):
+                step()
+            torch.cuda.synchronize()
+    if rank == 0 and args.full:
         step(stats=True, reduce=False)       # (un-timed, rank 0 only: no collective) what the backward walks
         walk = state.get("walk")
         fw = [d for d in sink if d["kind"] == "forward"]
@@ -594,9 +646,10 @@ def main():
                                  "blend_fwd_bwd_frac_of_copy": round(both / copy_gbs, 5)},
                 "num_rendered": R, "visible": Pv, "backward_walk": walk}
 
-    log("stages_ms", stages)
+    if args.full:
+        log("stages_ms", stages)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         log("cpu baseline (oracle) ...")
         cpu = cpu_baseline()
         log("cpu baseline", cpu)
@@ -611,7 +664,7 @@ def main():
     #      Mapping = monogs_amd.mapping.WindowMapper, the SAME optimize_map / initialize_map the sharded C4 window runs, replayed
     #      from hipGraphs; every map-size change (surgery, new keyframe) costs a re-capture, which is INSIDE the rates.
     slam = None
-    if rank == 0 and world == 1 and not args.no_slam:
+    if rank == 0 and world == 1 and args.full and not args.no_slam:
         try:
             log("slam harness (tracking + mapping rates, map surgery on) ...")
             del xyz, rgb, opac, scaling, rot, params, g_color, g_depth
@@ -688,10 +741,6 @@ def main():
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             # every step this process ran before the timed region: the exact first step, the settle steps, the warm-up steps
             "warmup_effective": warmup_effective,
-            # the same workload timed WITHOUT the settle steps: the first `cold_steps` steps after the exact one (None: --settle-steps 0,
-            # then `value` itself is that figure)
-            "value_cold": (round(world * W * H * cold_steps / dt_cold / 1e6, 2) if dt_cold else None),
-            "ms_per_step_cold": (round(dt_cold / cold_steps * 1e3, 4) if dt_cold else None), "cold_steps": cold_steps,
             "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": f"{'C5' if is_c5 else 'custom'}: {args.gaussians} Gaussians, {W}x{H}, fwd+bwd, seeded synthetic map "
@@ -700,14 +749,21 @@ def main():
                        "instance_count": "device-side (capacity mode, overflow checked)" if sync_free else "host read-back per forward",
                        "parallelism": f"keyframe-per-gpu x{world}" + (f" + RCCL all-reduce of 12 floats/Gaussian in {bucket.last_collectives} collective(s)" if bucket is not None else "")
                        + (" [REHEARSAL: ranks share a device, collectives over gloo]" if rehearsal else "")},
-            "stages_ms": stages,
-            "stages_note": "HIP events between the stages, in profile steps outside the timed region (median); every profiled call "
-                           "synchronises, and behind an idle gap the issue-bound blend kernels run ~8 % slower than in back-to-back "
-                           "steps, so the stages add up to more than ms_per_step; blend_in_timed_region has the two blend kernels as "
-                           "the timed region runs them (what roofline is computed from)",
-            "blend_in_timed_region": region,
-            "roofline": roof, "cpu_baseline": cpu, "slam": slam,
         }
+        if args.full:
+            line.update({
+                # the same workload timed WITHOUT the settle steps: the first `cold_steps` steps after the exact one (None: --settle-steps 0,
+                # then `value` itself is that figure)
+                "value_cold": (round(world * W * H * cold_steps / dt_cold / 1e6, 2) if dt_cold else None),
+                "ms_per_step_cold": (round(dt_cold / cold_steps * 1e3, 4) if dt_cold else None), "cold_steps": cold_steps,
+                "stages_ms": stages,
+                "stages_note": "HIP events between the stages, in profile steps outside the timed region (median); every profiled call "
+                               "synchronises, and behind an idle gap the issue-bound blend kernels run ~8 % slower than in back-to-back "
+                               "steps, so the stages add up to more than ms_per_step; blend_in_timed_region has the two blend kernels as "
+                               "the timed region runs them (what roofline is computed from)",
+                "blend_in_timed_region": region,
+                "roofline": roof, "cpu_baseline": cpu, "slam": slam,
+            })
         if exchange is not None:
             line["exchange"] = exchange
             line["replicas_in_sync"] = exchange["replicas_in_sync"]

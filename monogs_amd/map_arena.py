@@ -16,7 +16,8 @@ IPC for device tensors -- ``torch.multiprocessing`` shares both the same way) an
   sequence.  The header therefore carries a write-in-progress word that the writer sets BEFORE the first byte is
   copied: a reader that took sequence ``s`` may use its views while ``stale(s)`` is False, and must re-check
   ``stale(s)`` AFTER it has finished reading them (seqlock read side) -- True means the data may be torn: discard
-  and ``acquire()`` again.
+  and ``acquire()`` again.  While the writer stores the new slot, count and sequence the word is negative, and
+  ``acquire()`` waits for the sequence to move rather than pair the old sequence with the new slot.
 
 Capacity is fixed at creation (MonoGS maps grow by at most a few thousand Gaussians per keyframe; size it for the
 session, 288 GB of HBM is not the constraint).  Works with any set of named tensors, so the activated tensors the tracker
@@ -24,13 +25,14 @@ renders from can ride along with the raw parameters.
 """
 from __future__ import annotations
 
+import time
 from typing import Dict, Sequence, Tuple
 
 import torch
 
 
 class MapArena:
-    HEADER = 4           # int64: [sequence, slot, count, write in progress (1 + target slot, 0 = none)]
+    HEADER = 4           # int64: [sequence, slot, count, write in progress (1 + target slot, negated while the header is stored, 0 = none)]
 
     def __init__(self, capacity: int, fields: Dict[str, Sequence[int]], device="cpu", dtype=torch.float32):
         """``fields`` maps a name to the trailing shape of one Gaussian's entry, e.g. {"xyz": (3,), "rotation": (4,)}."""
@@ -67,7 +69,9 @@ class MapArena:
         dev = next(iter(self.buffers.values()))[0].device
         if dev.type == "cuda":
             torch.cuda.current_stream(dev).synchronize()      # the copies are complete before the header says so
-        # count and slot first, sequence last: a reader that sees the new sequence sees its slot and count
+        # count and slot first, sequence last: a reader that sees the new sequence sees its slot and count, and one that
+        # reads the old sequence around them sees the negative word and retries
+        self.header[3] = -(back + 1)
         self.header[2] = n
         self.header[1] = back
         self.header[0] = seq + 1
@@ -83,6 +87,9 @@ class MapArena:
                 return 0, {}
             slot, n = int(self.header[1]), int(self.header[2])
             views = {k: pair[slot][:n] for k, pair in self.buffers.items()}
+            if int(self.header[3]) < 0:     # slot / count may already be the next sequence's
+                time.sleep(0)               # (a writer thread of this process needs the GIL to finish the header)
+                continue
             if int(self.header[0]) == seq:
                 return seq, views
         raise RuntimeError("MapArena.acquire: the writer kept publishing; no consistent header")

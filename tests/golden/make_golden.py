@@ -12,7 +12,10 @@ Outputs (data only -- inputs and the reference's outputs):
   lr_schedule.npz : general_utils.helper (the xyz learning-rate schedule of update_learning_rate)
   median_depth.npz: get_median_depth (value, std, valid mask) on a seeded depth image with holes, with and without a mask
   grad_mask.npz   : image_gradient / image_gradient_mask combined as compute_grad_mask does (the tracking loss's edge mask)
+  render_seam.json: the names the render seam imports and the keywords of its rasteriser / settings / distCUDA2 call sites
 """
+import ast
+import json
 import math
 import os
 import sys
@@ -233,9 +236,38 @@ def grad_mask():
     np.savez_compressed(os.path.join(HERE, "grad_mask.npz"), **out)
 
 
+def render_seam():
+    """What tests/test_reference_binding.py checks the drop-in packages against, read with `ast` from
+    gaussian_splatting/gaussian_renderer/__init__.py (imports, settings and rasteriser call sites) and
+    gaussian_splatting/scene/gaussian_model.py (the simple_knn import and the distCUDA2 call)."""
+    def calls(tree, name):
+        return [n for n in ast.walk(tree) if isinstance(n, ast.Call) and (
+            (isinstance(n.func, ast.Name) and n.func.id == name) or (isinstance(n.func, ast.Attribute) and n.func.attr == name))]
+
+    def site(c):
+        return {"n_args": len(c.args), "keywords": [k.arg for k in c.keywords]}
+
+    def imports(tree, module):
+        return sorted(a.name for n in ast.walk(tree) if isinstance(n, ast.ImportFrom) and n.module == module for a in n.names)
+
+    seam = ast.parse(open(os.path.join(REF, "gaussian_splatting", "gaussian_renderer", "__init__.py")).read())
+    model = ast.parse(open(os.path.join(REF, "gaussian_splatting", "scene", "gaussian_model.py")).read())
+    out = {"renderer": {"imports_diff_gaussian_rasterization": imports(seam, "diff_gaussian_rasterization"),
+                        "functions": sorted(n.name for n in seam.body if isinstance(n, ast.FunctionDef)),
+                        "settings_calls": [site(c) for c in calls(seam, "GaussianRasterizationSettings")],
+                        "rasterizer_calls": [site(c) for c in calls(seam, "rasterizer")]},
+           "gaussian_model": {"imports_simple_knn._C": imports(model, "simple_knn._C"),
+                              "distCUDA2_calls": [site(c) for c in calls(model, "distCUDA2")]}}
+    with open(os.path.join(HERE, "render_seam.json"), "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] in ("median_depth", "lr_schedule", "losses_invert", "grad_mask"):   # add one fixture without rewriting the others
-        {"median_depth": median_depth, "lr_schedule": lr_schedule, "losses_invert": losses_invert, "grad_mask": grad_mask}[sys.argv[1]]()
+    one = {"median_depth": median_depth, "lr_schedule": lr_schedule, "losses_invert": losses_invert, "grad_mask": grad_mask,
+           "render_seam": render_seam}
+    if len(sys.argv) > 1 and sys.argv[1] in one:   # add one fixture without rewriting the others
+        one[sys.argv[1]]()
         sys.exit(0)
     camera_pose()
     sh_eval()
@@ -244,4 +276,5 @@ if __name__ == "__main__":
     median_depth()
     lr_schedule()
     grad_mask()
+    render_seam()
     print("golden fixtures written to", HERE)

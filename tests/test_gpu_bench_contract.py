@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -11,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_line_carries_the_contract_fields():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "3", "--no-slam",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20", "--warmup", "3", "--no-slam",
                           "--no-cpu-baseline", "--gaussians", "200000", "--intrinsics", "fr3_office"],
                          capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -36,3 +37,41 @@ def test_bench_line_carries_the_contract_fields():
     assert d["cold_steps"] == 20 and d["value_cold"] > 0
     assert abs(d["value_cold"] - 640 * 480 / 1e6 / (d["ms_per_step_cold"] * 1e-3)) < 0.01 * d["value_cold"]
     assert d["blend_in_timed_region"]["launches_timed"] <= 8       # the probes inside the timed region stay few
+
+
+def _plain_run(out_dir):
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "7", "--warmup", "2", "--gaussians", "200000",
+                          "--intrinsics", "fr3_office", "--dump-outputs", str(out_dir)],
+                         capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    return json.loads(lines[0])
+
+
+def test_plain_run_times_the_steps_and_dumps_the_last_steps_outputs(tmp_path):
+    """Without --full the line is the headline alone, --steps is the number of timed steps, and --dump-outputs writes what the
+    last timed step returned (float32 / float64, <= 64 MB, per-Gaussian arrays at a seeded sample).  Two runs with the same arguments
+    see the same inputs, so they write the same outputs (up to the order of the backward's atomic sums)."""
+    d = _plain_run(tmp_path / "a")
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+        assert k in d, k
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["unit"] == "Mpix/s" and d["dtype"] == "f32"
+    assert abs(d["value"] - 640 * 480 / 1e6 / (d["ms_per_step"] * 1e-3)) < 0.01 * d["value"]
+    for k in ("roofline", "cpu_baseline", "slam", "stages_ms", "value_cold", "blend_in_timed_region"):
+        assert k not in d, k                       # measured behind --full only
+    names = {"color", "depth", "opacity", "radii", "n_touched", "grad_means3D", "grad_means2D", "grad_opacities",
+             "grad_colors_precomp", "grad_scales", "grad_rotations", "grad_theta", "grad_rho", "gaussian_index"}
+    a = {p.stem: np.load(p) for p in (tmp_path / "a").glob("*.npy")}
+    assert set(a) == names
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert a["color"].shape == (3, 480, 640) and a["depth"].shape == (1, 480, 640)
+    assert a["gaussian_index"].shape == (65536,) and a["grad_means3D"].shape == (65536, 3) and a["radii"].shape == (65536,)
+    assert (a["radii"] > 0).any() and np.abs(a["grad_theta"]).max() > 0
+    _plain_run(tmp_path / "b")
+    b = {p.stem: np.load(p) for p in (tmp_path / "b").glob("*.npy")}
+    for k in ("color", "depth", "opacity", "radii", "n_touched", "gaussian_index"):
+        assert np.array_equal(a[k], b[k]), k
+    for k in names - {"color", "depth", "opacity", "radii", "n_touched", "gaussian_index"}:
+        assert np.allclose(a[k], b[k], rtol=1e-4, atol=1e-5 * float(np.abs(b[k]).max())), k

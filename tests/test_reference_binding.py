@@ -1,61 +1,43 @@
-"""In-container check (skipped where /root/reference does not exist, i.e. on the GPU box) that the reference's OWN
-render seam binds to the drop-in packages: `gaussian_splatting/gaussian_renderer/__init__.py` imports
-`diff_gaussian_rasterization` (:13-16), builds the settings tuple by keyword (:70-84) and calls the rasteriser by
-keyword (:145-156).  Nothing is executed on a GPU here; the file is imported and its call sites are read with `ast`."""
-import ast
-import importlib
+"""The reference's OWN render seam binds to the drop-in packages: `gaussian_splatting/gaussian_renderer/__init__.py`
+imports `diff_gaussian_rasterization` (:13-16), builds the settings tuple by keyword (:70-84) and calls the rasteriser by
+keyword (:145-156).  Its imports and call sites were read with `ast` into tests/golden/render_seam.json
+(tests/golden/make_golden.py::render_seam); nothing is executed on a GPU here."""
 import inspect
+import json
 import os
-import sys
 
-import pytest
-
-REF = "/root/reference"
-SEAM = os.path.join(REF, "gaussian_splatting", "gaussian_renderer", "__init__.py")
-pytestmark = pytest.mark.skipif(not os.path.exists(SEAM), reason="the reference tree is not present (GPU box)")
-
-
-def _calls(tree, name):
-    out = []
-    for node in ast.walk(tree):
-        if isinstance(node, ast.Call):
-            f = node.func
-            if (isinstance(f, ast.Name) and f.id == name) or (isinstance(f, ast.Attribute) and f.attr == name):
-                out.append(node)
-    return out
+SEAM = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "render_seam.json")))
 
 
 def test_reference_render_seam_binds_to_the_shim():
     import diff_gaussian_rasterization as shim
     from monogs_amd import rasterizer
-    if REF not in sys.path:
-        sys.path.append(REF)
-    mod = importlib.import_module("gaussian_splatting.gaussian_renderer")
-    assert mod.GaussianRasterizer is rasterizer.GaussianRasterizer is shim.GaussianRasterizer
-    assert mod.GaussianRasterizationSettings is rasterizer.GaussianRasterizationSettings
-    assert callable(mod.render)
+    seam = SEAM["renderer"]
+    names = seam["imports_diff_gaussian_rasterization"]
+    assert {"GaussianRasterizer", "GaussianRasterizationSettings"} <= set(names)
+    for name in names:                   # every name the seam imports resolves to ours
+        assert getattr(shim, name) is getattr(rasterizer, name), name
+    assert "render" in seam["functions"]
 
-    tree = ast.parse(open(SEAM).read())
     # settings: every keyword the reference passes is a field, and every field is passed
-    (call,) = _calls(tree, "GaussianRasterizationSettings")
-    passed = [k.arg for k in call.keywords]
-    assert not call.args and sorted(passed) == sorted(rasterizer.GaussianRasterizationSettings._fields)
+    (call,) = seam["settings_calls"]
+    assert call["n_args"] == 0 and sorted(call["keywords"]) == sorted(rasterizer.GaussianRasterizationSettings._fields)
     # rasteriser: the reference's keyword calls are accepted by forward()
     params = set(inspect.signature(rasterizer.GaussianRasterizer.forward).parameters) - {"self"}
-    calls = _calls(tree, "rasterizer")
+    calls = seam["rasterizer_calls"]
     assert calls
     for c in calls:
-        assert not c.args and {k.arg for k in c.keywords} <= params, [k.arg for k in c.keywords]
-    assert {"theta", "rho", "means2D", "colors_precomp", "scales", "rotations"} <= {k.arg for c in calls for k in c.keywords}
+        assert c["n_args"] == 0 and set(c["keywords"]) <= params, c["keywords"]
+    assert {"theta", "rho", "means2D", "colors_precomp", "scales", "rotations"} <= {k for c in calls for k in c["keywords"]}
 
 
 def test_reference_simple_knn_call_site_binds():
-    """`from simple_knn._C import distCUDA2` (/root/reference/gaussian_splatting/scene/gaussian_model.py:18), called with
-    one positional tensor (:294-302).  gaussian_model itself needs open3d (absent), so only the import line is checked."""
+    """`from simple_knn._C import distCUDA2` (the reference's gaussian_splatting/scene/gaussian_model.py:18), called with
+    one positional tensor (:294-302)."""
     from simple_knn._C import distCUDA2
     from monogs_amd.knn import distCUDA2 as ours
     assert distCUDA2 is ours
-    src = open(os.path.join(REF, "gaussian_splatting", "scene", "gaussian_model.py")).read()
-    assert "from simple_knn._C import distCUDA2" in src
-    (call,) = [c for c in _calls(ast.parse(src), "distCUDA2")]
-    assert len(call.args) == 1 and not call.keywords
+    model = SEAM["gaussian_model"]
+    assert "distCUDA2" in model["imports_simple_knn._C"]
+    (call,) = model["distCUDA2_calls"]
+    assert call["n_args"] == 1 and not call["keywords"]

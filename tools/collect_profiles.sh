@@ -6,7 +6,7 @@ tag=${1:-r02}
 R=${GRAFT_REPO_ROOT:-$PWD}
 O=$R/gpurun_out
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py --no-cpu-baseline --no-slam"
+B="python3 $R/bench.py --full --no-cpu-baseline --no-slam"
 rm -rf /tmp/prof_$tag && mkdir -p /tmp/prof_$tag
 # 1. per-kernel time (the same command bench.py's live HIP-event figures come from)
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$tag/ks -o b -- $B --steps 20 > $O/${tag}_rocprof_run.log 2>&1
@@ -30,8 +30,8 @@ python3 $R/tools/isa_mix.py $O/${tag}_isa_mix.json > /dev/null 2>&1
 ( for n in 10000 20000 24576; do $R/tools/ubench/depth_small_bench $n; done ) > $O/${tag}_small_depth_chain_bench.txt 2>&1
 python3 $R/tools/group_stats.py > $O/${tag}_group_stream_counts.txt 2>&1
 python3 $R/tools/tail_probe.py 30 > $O/${tag}_tail_probe.txt 2>&1
-# 4. the plain line (with the stamped files in place the roofline record carries traffic and valu)
+# 4. the full line (with the stamped files in place the roofline record carries traffic and valu)
 cp $O/${tag}_traffic.json $R/profiles/traffic.json; cp $O/${tag}_pmc_valu.json $R/profiles/pmc_valu.json
 cp $O/${tag}_valu_costs.json $R/profiles/valu_costs.json; cp $O/${tag}_isa_mix.json $R/profiles/isa_mix.json
-python3 $R/bench.py > $O/${tag}_bench_default.log 2>&1
+python3 $R/bench.py --full > $O/${tag}_bench_default.log 2>&1
 tail -1 $O/${tag}_bench_default.log | cut -c1-2500
