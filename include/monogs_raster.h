@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define MGS_ABI_VERSION 9
+#define MGS_ABI_VERSION 10
 #define MGS_TILE 16 /* tile edge in pixels; ranges are per 16x16 tile */
 
 /* GaussianRasterizationSettings, minus `prefiltered` / `debug` which are call flags
@@ -137,7 +137,7 @@ int mgs_forward_preprocess(const mgs_camera* cam, int32_t P,
                                                         path cannot pass unseen, and costs no synchronisation of its own */,
                            mgs_timing* timing /* [host] or NULL */, void* stream);
 
-/* Forward, stage 2: duplicate (in depth order), stable grouping by tile, per-tile ranges, front-to-back blend.
+/* Forward, stage 2: duplicate (in depth order, or in index order -- mgs_binning_path), stable grouping by tile, per-tile ranges, front-to-back blend.
  * Outputs: color[3,H,W], depth[1,H,W] (sum z.alpha.T), opacity[1,H,W] (1 - T), n_touched[P]
  * (zeroed here, then incremented per pixel where the Gaussian is blended with T.(1-alpha) > 0.5). */
 int mgs_forward_render(const mgs_camera* cam, int32_t P, uint64_t num_rendered,
@@ -177,6 +177,14 @@ int mgs_debug_set_radix_spin_limit(uint32_t limit);
  * "debug_sort_exclusive" (1 = mgs_debug_sort_pairs sorts as under MGS_FLAG_EXCLUSIVE_DEVICE).  Nothing on the launch path
  * consults the environment. */
 int mgs_debug_set_option(const char* name, int64_t value);
+
+/* Which depth order a forward of P Gaussians at W x H builds (pure; follows the "radix_scanned" option, process-global):
+ * 0 = a global stable sort of the P depth keys, the instances emitted in that order and grouped by tile;
+ * 1 = per tile: the instances emitted in Gaussian-index order with their depth bits packed into the tile sort's pairs,
+ *     grouped by tile, and each tile's list sorted by (depth bits, index) in LDS -- taken where the depth sort would
+ *     take the counted-tiles path (P > 512 k, or any P with "radix_scanned" = 1), the tile id has <= 16 bits and
+ *     P <= 2^(37 - tile bits).  Both orders are identical; what the geometry scratch holds differs (monogs_amd/debug.py). */
+int mgs_binning_path(int32_t P, int32_t W, int32_t H);
 
 /* Test entry: the library's stable radix sort of n (key, value) pairs on key bits [0, bits) -- what the forward runs on
  * the depth keys and on the tile ids -- on caller-provided DEVICE buffers: keys / vals hold the input and receive the

@@ -138,6 +138,7 @@ using namespace mgs;
 extern "C" {
 
 int mgs_abi_version(void) { return MGS_ABI_VERSION; }
+int mgs_binning_path(int32_t P, int32_t W, int32_t H) { return binning_path(P, W, H); }
 const char* mgs_last_error(void) { return g_err; }
 
 size_t mgs_geometry_bytes(int32_t P) { return GeometryState::bytes(P < 0 ? 0 : P); }
@@ -188,13 +189,17 @@ int mgs_forward_preprocess(const mgs_camera* cam, int32_t P, const float* means3
                                            prepare_backward ? backward_grad_acc(prepare_backward) : nullptr, s)) return rc;
     tm.mark();
     const bool exclusive = (cam->flags & MGS_FLAG_EXCLUSIVE_DEVICE) != 0;
-    if (depth_chain_is_small(P)) {          // one single-workgroup launch: sort, rectangle gather and scan (timed as the depth sort)
+    const bool per_tile = binning_path(P, cam->image_width, cam->image_height) != 0;
+    if (per_tile) {                         // no global depth sort: the scan runs in index order (binning.hip)
+        tm.mark();
+        if (int rc = launch_scan(g, P, s, exclusive, g.rect)) return rc;
+    } else if (depth_chain_is_small(P)) {   // one single-workgroup launch: sort, rectangle gather and scan (timed as the depth sort)
         if (int rc = launch_depth_chain_small(g, P, s)) return rc;
         tm.mark();
     } else {
         if (int rc = launch_depth_sort(g, P, depth_sort_payload(P, cam->image_width, cam->image_height), s, exclusive)) return rc;
         tm.mark();
-        if (int rc = launch_scan(g, P, s, exclusive)) return rc;
+        if (int rc = launch_scan(g, P, s, exclusive, g.rect_sorted)) return rc;
     }
     tm.mark();
     if (num_rendered) {
@@ -213,7 +218,7 @@ int mgs_forward_preprocess(const mgs_camera* cam, int32_t P, const float* means3
     if (timing) {
         if (!num_rendered) MGS_HIP(hipStreamSynchronize(s));
         timing->preprocess_ms = tm.ms(0);
-        timing->depth_sort_ms = tm.ms(1);
+        timing->depth_sort_ms = per_tile ? 0.f : tm.ms(1);
         timing->scan_ms = tm.ms(2);
     }
     return 0;
@@ -241,14 +246,19 @@ static int forward_render_impl(const mgs_camera* cam, int32_t P, uint64_t R, boo
     StageTimer tm(s, timing != nullptr);
     const bool cap = capacity && binning;
     if (cap) n_dev = b.count;
+    const bool per_tile = binning_path(P, W, H) != 0;       // (the same decision mgs_forward_preprocess took)
     tm.mark();
     // (also zeroes n_touched, the tile ranges and the scratch of the tile sort; in capacity mode it publishes the
     //  clamped live count and the overflow flag; with R == 0 it emits nothing)
     if (int rc = launch_duplicate(*cam, P, g, b, capacity ? R : (R > 0 ? 0xFFFFFFFFull : 0ull), n_touched, img, R,
-                                  tile_bits(W, H), cap ? b.count : nullptr, overflow, s)) return rc;
+                                  tile_bits(W, H), cap ? b.count : nullptr, overflow, s, per_tile)) return rc;
     tm.mark();
     // (the sort's final pass writes the per-tile ranges: no ranges launch since round 4)
-    if (int rc = launch_sort(g, b, R, tile_bits(W, H), s, n_dev, (cam->flags & MGS_FLAG_EXCLUSIVE_DEVICE) != 0, img.ranges)) return rc;
+    if (int rc = launch_sort(g, b, R, tile_bits(W, H), s, n_dev, (cam->flags & MGS_FLAG_EXCLUSIVE_DEVICE) != 0, img.ranges,
+                             per_tile)) return rc;
+    // per-tile depth order: each tile's list, in index order now, sorted by depth in LDS (timed with the sort)
+    if (per_tile)
+        if (int rc = launch_tile_depth_sort(*cam, P, g, b, img, R, n_dev, s)) return rc;
     tm.mark();
     if (g_dbg_fwd_events[0]) MGS_HIP(hipEventRecord(g_dbg_fwd_events[0], s));
     if (int rc = launch_blend_forward(*cam, g, b, img, out_color, out_depth, out_opacity, n_touched,

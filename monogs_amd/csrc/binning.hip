@@ -73,6 +73,7 @@ __device__ __forceinline__ uint32_t scan_block_rows(const uint2* __restrict__ re
 }
 
 // out[i] = inclusive sum of the tiles touched by the Gaussians j <= i in depth order (rects = rect_sorted), within the block
+// (per-tile depth order: in index order, rects = rect)
 __global__ void __launch_bounds__(SCAN_THREADS) scan_local_kernel(const uint2* __restrict__ rects, uint32_t* out,
                                                                   uint32_t* block_sums, int n) {
     __shared__ uint32_t smem[8];
@@ -162,17 +163,17 @@ bool scan_is_small(int P) { return g_opt_scan_small != 0 && scan_nblocks(P) <= S
 
 // (Measured and rejected: a single-workgroup scan for small P -- 1024 threads x a serial run of dependent
 //  gathers each -- took ~300 us at P = 38 k against ~15 us for the three launches below: latency, not launches.)
-int launch_scan(const GeometryState& g, int P, hipStream_t s, bool exclusive) {
+int launch_scan(const GeometryState& g, int P, hipStream_t s, bool exclusive, const uint2* rects) {
     if (P == 0) return 0;
     const int nb = scan_nblocks(P);
     if (scan_is_small(P)) {
-        hipLaunchKernelGGL(scan_small_kernel, dim3(nb), dim3(SCAN_THREADS), 0, s, g.rect_sorted, g.point_offsets, g.scan_blocks,
+        hipLaunchKernelGGL(scan_small_kernel, dim3(nb), dim3(SCAN_THREADS), 0, s, rects, g.point_offsets, g.scan_blocks,
                            g.scan_status, P, nb, const_cast<uint32_t*>(radix_depth_error_flag(g.sort_temp, (uint64_t)P)),
                            exclusive ? 0 : 1);
         MGS_HIP(hipGetLastError());
         return 0;
     }
-    hipLaunchKernelGGL(scan_local_kernel, dim3(nb), dim3(SCAN_THREADS), 0, s, g.rect_sorted, g.point_offsets,
+    hipLaunchKernelGGL(scan_local_kernel, dim3(nb), dim3(SCAN_THREADS), 0, s, rects, g.point_offsets,
                        g.scan_blocks, P);
     hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(SCAN_THREADS), 0, s, g.scan_blocks, nb);
     MGS_HIP(hipGetLastError());
@@ -352,9 +353,24 @@ int launch_depth_chain_small(const GeometryState& g, int P, hipStream_t s) {
 // ------------------------------------------------------------------------------------------------
 // duplicate: thread i takes the i-th Gaussian in depth order and walks its tile rectangle
 // (y outer, x inner), emitting (tile id, Gaussian index)
+//
+// Per-tile depth order (`depth_key` non-NULL, perm NULL): the i-th Gaussian by INDEX, and the pair carries its depth --
+// key = tile << tshift | depth27 >> lo, value = (depth27 & (2^lo - 1)) << (32 - lo) | index (common.h).  Depths beyond
+// the narrow range are clamped to DEPTH_KEY_NARROW; tile_depth_sort_kernel re-sorts that trailing run by the full key.
 // ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void dup_pair(uint32_t gidx, const uint32_t* __restrict__ depth_key, int lo, uint32_t& val,
+                                         uint32_t& kfield) {
+    val = gidx; kfield = 0u;
+    if (depth_key) {
+        const uint32_t k = depth_key[gidx];
+        const uint32_t d = k == 0xFFFFFFFFu ? DEPTH_KEY_NARROW : min(k - DEPTH_KEY_SUB, DEPTH_KEY_NARROW);
+        kfield = d >> lo;
+        if (lo) val |= (d & ((1u << lo) - 1u)) << (32 - lo);
+    }
+}
 __global__ void __launch_bounds__(256) duplicate_kernel(int P, const uint2* __restrict__ rects,
                                                         const uint32_t* __restrict__ perm,
+                                                        const uint32_t* __restrict__ depth_key, int tshift, int lo,
                                                         const uint32_t* __restrict__ offsets /* block-local inclusive sums */,
                                                         const uint32_t* __restrict__ block_sums /* [nb] exclusive, [nb] = total */,
                                                         uint32_t* keys,
@@ -385,10 +401,10 @@ __global__ void __launch_bounds__(256) duplicate_kernel(int P, const uint2* __re
     // what is still {~0, 0} afterwards into {0, 0})
     if (i < ntiles) ranges[i] = make_uint2(0xFFFFFFFFu, 0u);
     if (i < P) n_touched[i] = 0;                         // (was a memset)
-    uint32_t idx = 0, nt = 0, off = 0;
+    uint32_t idx = 0, nt = 0, off = 0, kf = 0;
     int x0 = 0, y0 = 0, x1 = 0;
-    if (i < P) {                                         // everything in depth order and coalesced: no gather
-        idx = perm[i];
+    if (i < P) {                                         // everything in depth (or index) order and coalesced: no gather
+        dup_pair(perm ? perm[i] : (uint32_t)i, depth_key, lo, idx, kf);
         const uint2 r = rects[i];                        // the rectangle preprocess computed (0 x 0: culled)
         const int w = (int)(r.y & 0xFFFFu), h = (int)(r.y >> 16);
         nt = (uint32_t)(w * h);
@@ -401,7 +417,7 @@ __global__ void __launch_bounds__(256) duplicate_kernel(int P, const uint2* __re
     // owner of its slot: owners mark their first slot in LDS, an inclusive max-scan spreads the mark to the right.
     // A thread walking its own rectangle instead wrote 64 interleaved streams per wave (73 us at C5 for 26 MB).
     __shared__ uint32_t s_own[4][WAVE];
-    __shared__ uint32_t s_idx[4][WAVE], s_off[4][WAVE];
+    __shared__ uint32_t s_idx[4][WAVE], s_off[4][WAVE], s_kf[4][WAVE];
     __shared__ int s_x0[4][WAVE], s_y0[4][WAVE], s_w[4][WAVE];
     // Digit counts of the emitted tile ids (every pass of the tile sort), collected in LDS while the keys are written and
     // added to the global table once per workgroup: the one-sweep sort then needs no histogram launch of its own.
@@ -444,7 +460,7 @@ __global__ void __launch_bounds__(256) duplicate_kernel(int P, const uint2* __re
         while (sl < s1 && g < (uint32_t)P) {                                   // wave-uniform
             const uint32_t gi = g + (uint32_t)lane;
             const bool valid = gi < (uint32_t)P;
-            uint32_t inc = 0, ntg = 0, idg = 0;
+            uint32_t inc = 0, ntg = 0, idg = 0, kfg = 0;
             int gx0 = 0, gy0 = 0, gw = 1;
             if (valid) {
                 inc = incl(gi);
@@ -452,14 +468,14 @@ __global__ void __launch_bounds__(256) duplicate_kernel(int P, const uint2* __re
                 gw = (int)(r.y & 0xFFFFu);
                 ntg = (uint32_t)(gw * (int)(r.y >> 16));
                 gx0 = (int)(r.x & 0xFFFFu); gy0 = (int)(r.x >> 16);
-                idg = perm[gi];
+                dup_pair(perm ? perm[gi] : gi, depth_key, lo, idg, kfg);
             }
             const uint32_t exc = inc - ntg;                                    // first slot of the Gaussian
             uint32_t Eg = valid ? inc : 0u;                                    // end of the group's slots = the largest inclusive sum
 #pragma unroll
             for (int o2 = 32; o2 > 0; o2 >>= 1) Eg = max(Eg, (uint32_t)__shfl_xor((int)Eg, o2, 64));
             __builtin_amdgcn_wave_barrier();
-            s_idx[wv][lane] = idg; s_off[wv][lane] = exc; s_x0[wv][lane] = gx0; s_y0[wv][lane] = gy0; s_w[wv][lane] = max(gw, 1);
+            s_idx[wv][lane] = idg; s_kf[wv][lane] = kfg; s_off[wv][lane] = exc; s_x0[wv][lane] = gx0; s_y0[wv][lane] = gy0; s_w[wv][lane] = max(gw, 1);
             const uint32_t e = min(s1, Eg);
             const uint32_t cb0 = sl & ~63u;
             const unsigned long long before = __builtin_amdgcn_ballot_w64(ntg != 0u && exc < cb0);
@@ -483,13 +499,14 @@ __global__ void __launch_bounds__(256) duplicate_kernel(int P, const uint2* __re
                     const uint32_t t = o - s_off[wv][L];
                     const uint32_t w = (uint32_t)s_w[wv][L];
                     const uint32_t yy = t / w, xx = t - yy * w;
-                    const uint32_t key = (uint32_t)((s_y0[wv][L] + (int)yy) * gx + s_x0[wv][L] + (int)xx);
+                    const uint32_t tid = (uint32_t)((s_y0[wv][L] + (int)yy) * gx + s_x0[wv][L] + (int)xx);
+                    const uint32_t key = (tid << tshift) | s_kf[wv][L];
                     keys[o] = key;
                     vals[o] = s_idx[wv][L];
                     if (hist) {
-                        atomicAdd(&s_hist[0][key & 0xFFu], 1u);
+                        atomicAdd(&s_hist[0][(key >> tshift) & 0xFFu], 1u);
                         if (hist_passes > 1) {      // (few values: the lanes that share the first active lane's digit add once)
-                            const uint32_t d1 = (key >> 8) & 0xFFu;
+                            const uint32_t d1 = (key >> (tshift + 8)) & 0xFFu;
                             const uint32_t lead = (uint32_t)__builtin_amdgcn_readfirstlane((int)d1);
                             const unsigned long long same = __builtin_amdgcn_ballot_w64(d1 == lead);
                             if (d1 != lead) atomicAdd(&s_hist[1][d1], 1u);
@@ -509,7 +526,7 @@ __global__ void __launch_bounds__(256) duplicate_kernel(int P, const uint2* __re
         }
         return;
     }
-    s_idx[wv][lane] = idx; s_off[wv][lane] = off; s_x0[wv][lane] = x0; s_y0[wv][lane] = y0; s_w[wv][lane] = max(x1 - x0, 1);
+    s_idx[wv][lane] = idx; s_kf[wv][lane] = kf; s_off[wv][lane] = off; s_x0[wv][lane] = x0; s_y0[wv][lane] = y0; s_w[wv][lane] = max(x1 - x0, 1);
     const unsigned long long live = __builtin_amdgcn_ballot_w64(nt != 0);
     if (live == 0ull && !hist) return;                                      // wave-uniform
     const int first = live ? __builtin_ctzll(live) : 0, lastl = live ? 63 - __builtin_clzll(live) : 0;
@@ -535,14 +552,15 @@ __global__ void __launch_bounds__(256) duplicate_kernel(int P, const uint2* __re
             const uint32_t t = o - s_off[wv][L];
             const uint32_t w = (uint32_t)s_w[wv][L];
             const uint32_t yy = t / w, xx = t - yy * w;
-            const uint32_t key = (uint32_t)((s_y0[wv][L] + (int)yy) * gx + s_x0[wv][L] + (int)xx);
+            const uint32_t tid = (uint32_t)((s_y0[wv][L] + (int)yy) * gx + s_x0[wv][L] + (int)xx);
+            const uint32_t key = (tid << tshift) | s_kf[wv][L];
             keys[o] = key;
             vals[o] = s_idx[wv][L];
             if (hist) {
-                atomicAdd(&s_hist[0][key & 0xFFu], 1u);
+                atomicAdd(&s_hist[0][(key >> tshift) & 0xFFu], 1u);
                 if (hist_passes > 1) {
                     // the high digit takes a handful of values: the lanes that share the first active lane's digit add once
-                    const uint32_t d1 = (key >> 8) & 0xFFu;
+                    const uint32_t d1 = (key >> (tshift + 8)) & 0xFFu;
                     const uint32_t lead = (uint32_t)__builtin_amdgcn_readfirstlane((int)d1);
                     const unsigned long long same = __builtin_amdgcn_ballot_w64(d1 == lead);
                     if (d1 != lead) atomicAdd(&s_hist[1][d1], 1u);
@@ -564,7 +582,7 @@ int g_opt_dup_slot_major = -1;      // mgs_debug_set_option("dup_slot_major", -1
 
 int launch_duplicate(const mgs_camera& cam, int P, const GeometryState& g, const BinningState& b, uint64_t r_cap,
                      int32_t* n_touched, const ImageState& img, uint64_t sort_n, int sort_bits, uint32_t* count,
-                     uint32_t* overflow, hipStream_t s) {
+                     uint32_t* overflow, hipStream_t s, bool per_tile) {
     const uint32_t* depth_err = P > 0 ? radix_depth_error_flag(g.sort_temp, (uint64_t)P) : nullptr;
     const int ntiles = tiles_x(cam.image_width) * tiles_y(cam.image_height);
     int n = P > ntiles ? P : ntiles;
@@ -584,10 +602,14 @@ int launch_duplicate(const mgs_camera& cam, int P, const GeometryState& g, const
     size_t zero_words = 0;
     if (sort_n > 0) radix_zero_region(b.sort_temp, sort_n, sort_bits, &zero_ptr, &zero_words);
     const bool count_digits = P > 0 && sort_bits <= 16 && radix_wants_hist(sort_n);
-    hipLaunchKernelGGL(duplicate_kernel, dim3(n_threads / 256), dim3(256), 0, s, P, g.rect_sorted, g.perm, g.point_offsets,
+    const int tb = tile_bits(cam.image_width, cam.image_height);
+    hipLaunchKernelGGL(duplicate_kernel, dim3(n_threads / 256), dim3(256), 0, s, P, per_tile ? g.rect : g.rect_sorted,
+                       per_tile ? nullptr : g.perm, per_tile ? g.depth_key : nullptr, per_tile ? 32 - tb : 0,
+                       per_tile ? tile_depth_lo_bits(tb) : 0, g.point_offsets,
                        g.scan_blocks, b.keys_a, b.vals_a, tiles_x(cam.image_width), tiles_y(cam.image_height),
                        (uint32_t)(r_cap > 0xFFFFFFFFull ? 0xFFFFFFFFull : r_cap), n_touched, img.ranges, ntiles, zero_ptr,
-                       zero_words, count, overflow, depth_err, (P > 0 && (scan_is_small(P) || depth_chain_is_small(P))) ? 1 : 0,
+                       zero_words, count, overflow, depth_err,
+                       (P > 0 && (scan_is_small(P) || (!per_tile && depth_chain_is_small(P)))) ? 1 : 0,
                        count_digits ? g.tile_hist : nullptr, (sort_bits + 7) / 8, n_threads, slot_major ? 1 : 0);
     MGS_HIP(hipGetLastError());
     return 0;
@@ -606,13 +628,264 @@ int launch_depth_sort(const GeometryState& g, int P, bool payload, hipStream_t s
 }
 
 int launch_sort(const GeometryState& g, const BinningState& b, uint64_t R, int bits, hipStream_t s, const uint32_t* n_dev,
-                bool exclusive, uint2* ranges) {
+                bool exclusive, uint2* ranges, bool per_tile) {
     if (R == 0) return 0;
     // the scratch was cleared by duplicate_kernel, which also counted the digits of the keys it emitted (small sorts; the
     // same predicate as launch_duplicate's `count_digits` -- R > 0 implies P > 0, forward_render_impl)
     const bool counted = bits <= 16 && radix_wants_hist(R) && g.tile_hist != nullptr;
+    // per-tile depth order: the tile id is the top `bits` of the key (shift 32 - bits), the depth bits below it ride along
     return radix_sort_pairs(b.keys_a, b.vals_a, b.keys_b, b.vals_b, R, bits, b.sort_temp, s, n_dev, true, nullptr, nullptr,
-                            counted ? g.tile_hist : nullptr, false, exclusive, ranges);
+                            counted ? g.tile_hist : nullptr, false, exclusive, ranges, per_tile ? 32 - bits : 0);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Per-tile depth order (binning_path() == 1: large maps).  Instead of a global depth sort of all P Gaussians (three or
+// four counted-tiles passes: ~105 us at C5, 2 M Gaussians), duplicate_kernel emits the instances in Gaussian-index order
+// with the depth packed into the pair (see dup_pair), the stable tile sort groups them by tile -- index order inside a
+// tile -- and ONE workgroup per tile sorts its list by depth here, stably, in LDS.  Result: (depth bits, index) order
+// inside every tile, bit for bit what the two global sorts produce.
+//   * a list of <= TDS_CAP pairs: keys = depth27 - (the tile's minimum), LSD passes of 9 bits over the significant bits
+//     only (C5: 500 - 851 pairs per tile, ~25 significant bits: three passes).  Ranking as in the radix sort: a returning
+//     LDS atomic on the wave's digit counter (lanes of one DS instruction in lane order, a wave's instructions in program
+//     order: stable); wave w owns elements [w * 256, (w + 1) * 256), row i of them 64 consecutive ones.
+//   * depths beyond the narrow range were clamped to DEPTH_KEY_NARROW: those pairs form the LAST run of the sorted list,
+//     still in index order; it is re-sorted by the full depth key (gathered through the index), the same way.
+//   * a longer list (a scene of large splats, never C5): the same LSD sort over the tile's segment in global memory,
+//     256 pairs at a time with running digit offsets, on the full depth key, ping-ponging through the other half of the
+//     tile sort's buffers (free once it is done); four 8-bit passes end in the original buffers.
+// The indices are written in place over the tile's values: b.vals_sorted is the blend kernels' point_list.
+// ------------------------------------------------------------------------------------------------
+constexpr int TDS_THREADS = 256, TDS_WAVES = TDS_THREADS / WAVE, TDS_ITEMS = 4, TDS_CAP = TDS_THREADS * TDS_ITEMS;
+constexpr int TDS_DB = 9, TDS_RADIX = 1 << TDS_DB, TDS_DPT = TDS_RADIX / TDS_THREADS;
+
+// block-wide min / max of one value per thread (valid lanes only); every thread gets both
+__device__ __forceinline__ void tds_minmax(uint32_t lo, uint32_t hi, uint32_t* s_red /* >= 2 * TDS_WAVES */, uint32_t& mn,
+                                           uint32_t& mx) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        lo = min(lo, (uint32_t)__shfl_xor((int)lo, o, 64));
+        hi = max(hi, (uint32_t)__shfl_xor((int)hi, o, 64));
+    }
+    if (lane == 0) { s_red[wv] = lo; s_red[TDS_WAVES + wv] = hi; }
+    __syncthreads();
+    mn = s_red[0]; mx = s_red[TDS_WAVES];
+#pragma unroll
+    for (int w = 1; w < TDS_WAVES; ++w) { mn = min(mn, s_red[w]); mx = max(mx, s_red[TDS_WAVES + w]); }
+    __syncthreads();                                      // (s_red is reused)
+}
+
+// stable LSD sort of the LDS pairs [base, base + m), m <= TDS_CAP, on key bits [0, bits)
+__device__ __forceinline__ void tds_lds_sort(uint32_t* s_k, uint32_t* s_v, uint32_t (*s_cnt)[TDS_RADIX], uint32_t* s_wsum,
+                                             int base, int m, int bits) {
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    for (int sh = 0; sh < bits; sh += TDS_DB) {
+#pragma unroll
+        for (int w = 0; w < TDS_WAVES; ++w)
+#pragma unroll
+            for (int j = 0; j < TDS_DPT; ++j) s_cnt[w][t * TDS_DPT + j] = 0u;
+        __syncthreads();                                  // (also: the previous pass's scatter is visible)
+        uint32_t k[TDS_ITEMS], v[TDS_ITEMS], r[TDS_ITEMS];
+#pragma unroll
+        for (int i = 0; i < TDS_ITEMS; ++i) {
+            const int e = wv * (TDS_ITEMS * WAVE) + i * WAVE + lane;
+            k[i] = 0u; v[i] = 0u; r[i] = 0u;
+            if (e < m) {
+                k[i] = s_k[base + e]; v[i] = s_v[base + e];
+                r[i] = __hip_atomic_fetch_add(&s_cnt[wv][(k[i] >> sh) & (TDS_RADIX - 1)], 1u, __ATOMIC_RELAXED,
+                                              __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+        }
+        __syncthreads();
+        // thread t owns digits t * DPT + j: per-wave exclusive prefixes on top of the exclusive prefix over the digits
+        uint32_t c[TDS_DPT][TDS_WAVES], tot[TDS_DPT], tsum = 0;
+#pragma unroll
+        for (int j = 0; j < TDS_DPT; ++j) {
+            tot[j] = 0u;
+#pragma unroll
+            for (int w = 0; w < TDS_WAVES; ++w) { c[j][w] = s_cnt[w][t * TDS_DPT + j]; tot[j] += c[j][w]; }
+            tsum += tot[j];
+        }
+        const uint32_t incl = wave_incl_scan_dpp(tsum);
+        if (lane == 63) s_wsum[wv] = incl;
+        __syncthreads();
+        uint32_t run = incl - tsum;
+        for (int w = 0; w < wv; ++w) run += s_wsum[w];
+#pragma unroll
+        for (int j = 0; j < TDS_DPT; ++j)
+#pragma unroll
+            for (int w = 0; w < TDS_WAVES; ++w) { s_cnt[w][t * TDS_DPT + j] = run; run += c[j][w]; }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < TDS_ITEMS; ++i) {
+            const int e = wv * (TDS_ITEMS * WAVE) + i * WAVE + lane;
+            if (e < m) {
+                const uint32_t dst = s_cnt[wv][(k[i] >> sh) & (TDS_RADIX - 1)] + r[i];
+                s_k[base + dst] = k[i]; s_v[base + dst] = v[i];
+            }
+        }
+        __syncthreads();                                  // (every wave is done with the offsets before the next pass clears them)
+    }
+    __syncthreads();
+}
+
+// A list longer than TDS_CAP: stable LSD sort of the segment [0, n) of (kx, vx) on the full depth key, 8 bits per pass,
+// ping-ponging through (ky, vy); rare (large splats), so simple: one pair per thread per step.
+__device__ void tds_global_sort(uint32_t* __restrict__ kx, uint32_t* __restrict__ vx, uint32_t* __restrict__ ky,
+                                uint32_t* __restrict__ vy, uint32_t n, const uint32_t* __restrict__ depth_key, int lo,
+                                uint32_t (*s_cnt)[TDS_RADIX], uint32_t* s_run, uint32_t* s_wsum) {
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const uint32_t imask = lo ? (1u << (32 - lo)) - 1u : 0xFFFFFFFFu;
+    for (uint32_t e = t; e < n; e += TDS_THREADS) {       // in place: (packed key, packed value) -> (full key, index)
+        const uint32_t g = vx[e] & imask;
+        kx[e] = depth_key[g] - DEPTH_KEY_SUB;
+        vx[e] = g;
+    }
+    for (int sh = 0; sh < 32; sh += 8) {
+        __threadfence();                                  // (this workgroup's stores, read back by other lanes)
+        if (t < 256) s_run[t] = 0u;
+#pragma unroll
+        for (int w = 0; w < TDS_WAVES; ++w) s_cnt[w][t] = 0u;
+        __syncthreads();
+        for (uint32_t e = t; e < n; e += TDS_THREADS) atomicAdd(&s_run[(kx[e] >> sh) & 255u], 1u);
+        __syncthreads();
+        {                                                 // exclusive scan of the 256 digit counts: running offsets
+            const uint32_t c = s_run[t], incl = wave_incl_scan_dpp(c);
+            if (lane == 63) s_wsum[wv] = incl;
+            __syncthreads();
+            uint32_t b0 = incl - c;
+            for (int w = 0; w < wv; ++w) b0 += s_wsum[w];
+            s_run[t] = b0;
+        }
+        __syncthreads();
+        for (uint32_t c0 = 0; c0 < n; c0 += TDS_THREADS) {
+            const uint32_t e = c0 + (uint32_t)t;          // element order = (wave, lane) order
+            uint32_t k = 0u, v = 0u, r = 0u, d = 0u;
+            if (e < n) {
+                k = kx[e]; v = vx[e]; d = (k >> sh) & 255u;
+                r = __hip_atomic_fetch_add(&s_cnt[wv][d], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+            __syncthreads();
+            uint32_t pre[TDS_WAVES];                      // thread t = digit t: where each wave's pairs of it go
+            {
+                uint32_t run = s_run[t];
+#pragma unroll
+                for (int w = 0; w < TDS_WAVES; ++w) { const uint32_t c = s_cnt[w][t]; pre[w] = run; run += c; }
+                s_run[t] = run;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int w = 0; w < TDS_WAVES; ++w) s_cnt[w][t] = pre[w];
+            __syncthreads();
+            if (e < n) { const uint32_t dst = s_cnt[wv][d] + r; ky[dst] = k; vy[dst] = v; }
+            __syncthreads();
+#pragma unroll
+            for (int w = 0; w < TDS_WAVES; ++w) s_cnt[w][t] = 0u;
+            __syncthreads();
+        }
+        __threadfence();
+        __syncthreads();
+        uint32_t* tk = kx; kx = ky; ky = tk;
+        uint32_t* tv = vx; vx = vy; vy = tv;
+    }
+}
+
+__global__ void __launch_bounds__(TDS_THREADS) tile_depth_sort_kernel(const uint2* __restrict__ ranges, int ntiles,
+                                                                       uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
+                                                                       uint32_t* __restrict__ keys_alt, uint32_t* __restrict__ vals_alt,
+                                                                       const uint32_t* __restrict__ depth_key, int tb, uint32_t n_cap,
+                                                                       const uint32_t* __restrict__ n_dev,
+                                                                       const uint32_t* __restrict__ sort_err) {
+    __shared__ uint32_t s_k[TDS_CAP], s_v[TDS_CAP];
+    __shared__ uint32_t s_cnt[TDS_WAVES][TDS_RADIX];
+    __shared__ uint32_t s_wsum[TDS_WAVES], s_red[2 * TDS_WAVES];
+    const int tile = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    if (tile >= ntiles) return;
+    // a timed-out tile sort left the ranges invalid: blend_forward_kernel empties every tile, nothing to order here
+    if (sort_err && radix_failed(sort_err) != 0u) return;
+    const uint32_t n_live = n_dev ? min(n_cap, n_dev[0]) : n_cap;     // capacity mode: never past the live pairs
+    const uint2 rg = ranges[tile];                                     // {~0, 0}: empty
+    const uint32_t start = rg.x, end = min(rg.y, n_live);
+    if (start >= end) return;
+    const uint32_t n = end - start;
+    const int lo = tile_depth_lo_bits(tb);
+    const uint32_t kmask = tb < 32 ? (0xFFFFFFFFu >> tb) : 0u, imask = lo ? (1u << (32 - lo)) - 1u : 0xFFFFFFFFu;
+    if (n > (uint32_t)TDS_CAP) {
+        tds_global_sort(keys + start, vals + start, keys_alt + start, vals_alt + start, n, depth_key, lo, s_cnt, s_k, s_wsum);
+        return;
+    }
+    // ---- load (wave-striped), unpack depth27 and index, range of the depths
+    uint32_t d[TDS_ITEMS], g[TDS_ITEMS];
+    uint32_t dmin = 0xFFFFFFFFu, dmax = 0u;
+#pragma unroll
+    for (int i = 0; i < TDS_ITEMS; ++i) {
+        const uint32_t e = (uint32_t)(wv * (TDS_ITEMS * WAVE) + i * WAVE + lane);
+        d[i] = 0u; g[i] = 0u;
+        if (e < n) {
+            const uint32_t k = keys[start + e], v = vals[start + e];
+            d[i] = ((k & kmask) << lo) | (lo ? v >> (32 - lo) : 0u);
+            g[i] = v & imask;
+            dmin = min(dmin, d[i]); dmax = max(dmax, d[i]);
+        }
+    }
+    uint32_t mn, mx;
+    tds_minmax(dmin, dmax, s_red, mn, mx);
+#pragma unroll
+    for (int i = 0; i < TDS_ITEMS; ++i) {
+        const int e = wv * (TDS_ITEMS * WAVE) + i * WAVE + lane;
+        if (e < (int)n) { s_k[e] = d[i] - mn; s_v[e] = g[i]; }
+    }
+    const uint32_t span = mx - mn;
+    tds_lds_sort(s_k, s_v, s_cnt, s_wsum, 0, (int)n, span ? 32 - __builtin_clz(span) : 0);
+    if (mx == DEPTH_KEY_NARROW) {
+        // ---- clamped depths: the trailing run of keys DEPTH_KEY_NARROW - mn, in index order; re-sort it by the full key
+        uint32_t c = 0;
+#pragma unroll
+        for (int i = 0; i < TDS_ITEMS; ++i) {
+            const uint32_t e = (uint32_t)(wv * (TDS_ITEMS * WAVE) + i * WAVE + lane);
+            c += (e < n && d[i] == DEPTH_KEY_NARROW) ? 1u : 0u;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) c += (uint32_t)__shfl_xor((int)c, o, 64);
+        if (lane == 0) s_red[wv] = c;
+        __syncthreads();
+        uint32_t m = 0;
+#pragma unroll
+        for (int w = 0; w < TDS_WAVES; ++w) m += s_red[w];
+        __syncthreads();
+        const uint32_t f = n - m;                                    // first pair of the run
+        uint32_t xmin = 0xFFFFFFFFu, xmax = 0u;
+        for (uint32_t e = f + t; e < n; e += TDS_THREADS) {
+            const uint32_t x = depth_key[s_v[e]] - DEPTH_KEY_SUB;
+            s_k[e] = x;
+            xmin = min(xmin, x); xmax = max(xmax, x);
+        }
+        uint32_t rmn, rmx;
+        tds_minmax(xmin, xmax, s_red, rmn, rmx);
+        for (uint32_t e = f + t; e < n; e += TDS_THREADS) s_k[e] -= rmn;
+        __syncthreads();
+        const uint32_t rspan = rmx - rmn;
+        tds_lds_sort(s_k, s_v, s_cnt, s_wsum, (int)f, (int)m, rspan ? 32 - __builtin_clz(rspan) : 0);
+    }
+    // ---- the indices, in place (coalesced)
+#pragma unroll
+    for (int i = 0; i < TDS_ITEMS; ++i) {
+        const int e = wv * (TDS_ITEMS * WAVE) + i * WAVE + lane;
+        if (e < (int)n) vals[start + e] = s_v[e];
+    }
+}
+
+int launch_tile_depth_sort(const mgs_camera& cam, int P, const GeometryState& g, const BinningState& b, const ImageState& img,
+                           uint64_t R, const uint32_t* n_dev, hipStream_t s) {
+    if (R == 0 || P == 0) return 0;
+    const int W = cam.image_width, H = cam.image_height, ntiles = tiles_x(W) * tiles_y(H), tb = tile_bits(W, H);
+    uint32_t* keys_alt = b.keys_sorted == b.keys_a ? b.keys_b : b.keys_a;
+    uint32_t* vals_alt = b.vals_sorted == b.vals_a ? b.vals_b : b.vals_a;
+    hipLaunchKernelGGL(tile_depth_sort_kernel, dim3(ntiles), dim3(TDS_THREADS), 0, s, img.ranges, ntiles, b.keys_sorted,
+                       b.vals_sorted, keys_alt, vals_alt, g.depth_key, tb, (uint32_t)R, n_dev,
+                       radix_error_flag(b.sort_temp, R, tb));
+    MGS_HIP(hipGetLastError());
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------------------

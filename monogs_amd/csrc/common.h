@@ -180,6 +180,17 @@ inline int tile_bits(int W, int H) {     // bits of the tile id that can be set
     return b == 0 ? 1 : b;
 }
 
+// Depth keys: float bits of a view-space depth > 0.2 (preprocess culls the rest; all ones = culled).  key - DEPTH_KEY_SUB
+// stays below DEPTH_KEY_NARROW = 2^27 - 1 for every depth below 13 107.2 units (radix_sort.hip).
+constexpr uint32_t DEPTH_KEY_SUB = 0x3E4CCCCDu;             // float bits of 0.2f
+constexpr uint32_t DEPTH_KEY_NARROW = (1u << 27) - 1u;
+// Per-tile depth order (binning.hip): the tile sort's key is tile << (32 - tb) | depth27 >> lo, its value
+// (depth27 & (2^lo - 1)) << (32 - lo) | index, with depth27 = min(key - DEPTH_KEY_SUB, DEPTH_KEY_NARROW) and lo = the
+// depth bits that do not fit beside a tile id of tb bits
+__host__ __device__ inline int tile_depth_lo_bits(int tb) { return tb > 5 ? tb - 5 : 0; }
+// 1: the forward orders the Gaussians by depth per tile (no global depth sort); 0: the global depth sort (radix_sort.hip)
+int binning_path(int P, int W, int H);
+
 // ---- error plumbing --------------------------------------------------------------------------
 void set_error(const char* fmt, ...);
 #define MGS_HIP(expr)                                                                     \
@@ -203,14 +214,16 @@ constexpr int TAU_SLOTS = 256;              // one 64-byte line each
 inline float* backward_grad_acc(void* scratch) { return (float*)align_up((size_t)scratch, 256); }
 inline float* backward_tau_part(void* scratch, int P) { return backward_grad_acc(scratch) + (size_t)P * GRAD_FLOATS; }
 inline float* backward_tau_out(void* scratch, int P) { return backward_tau_part(scratch, P) + (size_t)TAU_SLOTS * 16; }
-int launch_scan(const GeometryState& g, int P, hipStream_t s, bool exclusive = false);
+// `rects`: the rectangles in the order the scan runs in (rect_sorted after a depth sort, rect by index on the per-tile path)
+int launch_scan(const GeometryState& g, int P, hipStream_t s, bool exclusive, const uint2* rects);
 // small maps: depth sort + rectangle gather + scan in ONE single-workgroup launch (binning.hip); replaces launch_depth_sort + launch_scan
 bool depth_chain_is_small(int P);
 int launch_depth_chain_small(const GeometryState& g, int P, hipStream_t s);
 // `r_cap`: capacity of the binning buffers; `count` (device): [0] live instance count min(R, r_cap), [1] overflow flag
+// `per_tile`: emit in Gaussian-index order with the depth bits packed into the pairs (binning_path() == 1)
 int launch_duplicate(const mgs_camera& cam, int P, const GeometryState& g, const BinningState& b, uint64_t r_cap,
                      int32_t* n_touched, const ImageState& img, uint64_t sort_n, int sort_bits, uint32_t* count,
-                     uint32_t* overflow, hipStream_t s);
+                     uint32_t* overflow, hipStream_t s, bool per_tile);
 size_t sort_temp_bytes(uint64_t n, int bits);
 size_t radix_temp_bytes(uint64_t n, int bits);
 size_t radix_depth_temp_bytes(uint64_t n);
@@ -220,7 +233,7 @@ const uint32_t* radix_error_flag(void* temp, uint64_t n, int bits);
 const uint32_t* radix_depth_error_flag(void* temp, uint64_t n);
 __device__ __forceinline__ uint32_t radix_failed(const uint32_t* __restrict__ e) { return (e[0] | e[1]) | (e[2] | e[3]); }
 void radix_zero_region(void* temp, uint64_t n, int bits, uint32_t** ptr, size_t* words);   // what must be 0 before a sort
-void radix_depth_zero_region(void* temp, uint64_t n, uint32_t** ptr, size_t* words);
+void radix_depth_zero_region(void* temp, uint64_t n, uint32_t** ptr, size_t* words, bool header_only = false);
 // `ext_hist` ([4][256], one-sweep path only): digit counts of the keys already counted by the kernel that produced them
 // -- the sort then launches no histogram kernel.  radix_wants_hist(n) tells the producer whether they will be used.
 int radix_sort_pairs(uint32_t* ka, uint32_t* va, uint32_t* kb, uint32_t* vb, uint64_t n, int bits, void* temp,
@@ -229,8 +242,10 @@ int radix_sort_pairs(uint32_t* ka, uint32_t* va, uint32_t* kb, uint32_t* vb, uin
                      const uint32_t* ext_hist = nullptr,
                      bool aux_empty_for_ones = false,        // a key of all ones gets aux (0, 0) without the fetch
                      bool exclusive = false,                 // MGS_FLAG_EXCLUSIVE_DEVICE: small sorts may use block ids as tile ids
-                     uint2* ranges = nullptr);               // keys are small integers: ranges[key] = {first, last + 1} sorted position
+                     uint2* ranges = nullptr,                // keys are small integers: ranges[key] = {first, last + 1} sorted position
                                                              // (the final pass: atomicMin / atomicMax on words preset to {~0, 0})
+                     int key_shift = 0);                     // the bits sorted are [key_shift, key_shift + bits); ranges are indexed
+                                                             // by key >> key_shift, and the final pass keeps the keys
 bool radix_wants_hist(uint64_t n);
 // The forward's first sort (radix_sort.hip): depth keys -> perm + rect_sorted; three 9-bit passes (+ a fourth that only
 // runs for depths beyond 13 107 units).  radix_depth_payload(n): the sort carries the packed rectangles itself.
@@ -242,7 +257,10 @@ int radix_sort_depth(uint32_t* keys, uint32_t* key_b, uint32_t* val_a, uint32_t*
 inline bool depth_sort_payload(int P, int W, int H) { return radix_depth_payload((uint64_t)P) && tiles_x(W) <= 255 && tiles_y(H) <= 255; }
 int launch_depth_sort(const GeometryState& g, int P, bool payload, hipStream_t s, bool exclusive = false);
 int launch_sort(const GeometryState& g, const BinningState& b, uint64_t R, int bits, hipStream_t s,
-                const uint32_t* n_dev = nullptr, bool exclusive = false, uint2* ranges = nullptr);
+                const uint32_t* n_dev = nullptr, bool exclusive = false, uint2* ranges = nullptr, bool per_tile = false);
+// per-tile depth order: each tile's list, grouped by the tile sort in index order, sorted by (depth, index) in place
+int launch_tile_depth_sort(const mgs_camera& cam, int P, const GeometryState& g, const BinningState& b, const ImageState& img,
+                           uint64_t R, const uint32_t* n_dev, hipStream_t s);
 int set_radix_spin_limit(uint32_t limit);
 extern int g_opt_radix_ballot_rank, g_opt_radix_scanned, g_opt_radix_xcd_band, g_opt_radix_tile_items, g_opt_knn_grid_min, g_opt_scan_small, g_opt_dup_slot_major, g_opt_blend_bwd_transposed, g_opt_blend_lds_pad_fwd, g_opt_blend_lds_pad_bwd, g_opt_depth_small;      // test knobs (mgs_debug_set_option)
 // `sort_err`: the tile sort's error words (NULL: nothing was sorted); a raised word empties every tile and sets

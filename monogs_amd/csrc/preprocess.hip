@@ -392,8 +392,11 @@ int launch_preprocess_forward(const mgs_camera& cam, int P, const float* means3D
     a.P = P; a.W = cam.image_width; a.H = cam.image_height;
     a.gx = tiles_x(a.W); a.gy = tiles_y(a.H); a.deg = cam.sh_degree; a.M = cam.sh_coeffs;
     if (P == 0) return 0;
-    a.rect_packed = depth_sort_payload(P, cam.image_width, cam.image_height) ? 1 : 0;
-    radix_depth_zero_region(g.sort_temp, (uint64_t)P, &a.zero_ptr, &a.zero_words);
+    // per-tile depth order: no depth sort follows -- the scan and duplicate read the rectangles {x0 | y0 << 16, w | h << 16}
+    // by index, and of the depth sort's scratch only the header (its error words, which the consumers check) is cleared
+    const bool per_tile = binning_path(P, cam.image_width, cam.image_height) != 0;
+    a.rect_packed = (!per_tile && depth_sort_payload(P, cam.image_width, cam.image_height)) ? 1 : 0;
+    radix_depth_zero_region(g.sort_temp, (uint64_t)P, &a.zero_ptr, &a.zero_words, per_tile);
     // + the two small tables carved right in front of it (scan status words, tile-sort digit counts)
     a.zero_words += (size_t)((char*)a.zero_ptr - (char*)g.scan_status) / 4;
     a.zero_ptr = (uint32_t*)g.scan_status;

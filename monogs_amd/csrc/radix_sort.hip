@@ -103,8 +103,8 @@ __device__ uint32_t g_rs_spin_limit = RS_SPIN_LIMIT;
 constexpr uint32_t RS_GROUP = 16;                  // tiles per group of the one-sweep all-gather
 
 // depth keys: see the header.  key - RS_DEPTH_SUB < RS_DEPTH_NARROW for every visible depth below 13 107.2
-constexpr uint32_t RS_DEPTH_SUB = 0x3E4CCCCDu;             // float bits of 0.2f (preprocess culls depth <= 0.2)
-constexpr uint32_t RS_DEPTH_NARROW = (1u << 27) - 1u;
+constexpr uint32_t RS_DEPTH_SUB = DEPTH_KEY_SUB;           // float bits of 0.2f (preprocess culls depth <= 0.2)
+constexpr uint32_t RS_DEPTH_NARROW = DEPTH_KEY_NARROW;
 // digit source of a key: culled keys (all ones) keep their pattern, so they sort behind every visible key in every mode
 __device__ __forceinline__ uint32_t rs_xf(uint32_t k, uint32_t sub) { return k == 0xFFFFFFFFu ? k : k - sub; }
 
@@ -116,6 +116,18 @@ constexpr uint64_t RS_SCANNED_MIN = 64ull * 1024;       // the knob can force co
 static inline bool rs_scanned(uint64_t n) {
     if (g_opt_radix_scanned >= 0) return g_opt_radix_scanned == 1 && n > RS_SCANNED_MIN;
     return n > RS_ONE_SWEEP_MAX;
+}
+
+// Which depth order the forward builds (binning.hip): 1 = per tile (tile_depth_sort_kernel) wherever the map's depth sort
+// would take the counted-tiles path -- or at any size when the radix_scanned knob is 1 -- and the tile sort's keys have
+// room for the high depth bits beside a tile id of <= 16 bits, the values for the low ones beside the index:
+// P <= 2^(37 - tile bits).  0 = the global depth sort (one sweep, depth_chain_small, or counted tiles with the knob at 0).
+int binning_path(int P, int W, int H) {
+    if (P <= 0) return 0;
+    const bool large = g_opt_radix_scanned >= 0 ? g_opt_radix_scanned == 1 : (uint64_t)P > RS_ONE_SWEEP_MAX;
+    const int tb = tile_bits(W, H);
+    if (!large || tb > 16) return 0;
+    return (uint64_t)P <= (1ull << (32 - tile_depth_lo_bits(tb))) ? 1 : 0;
 }
 // Pairs per thread.  On the counted-tiles path a tile lives ~10-20 us and the kernel ends when the last one does: if the
 // tiles do not all fit on the chip at once, the stragglers start when the first ones retire and the pass takes two tile
@@ -422,6 +434,7 @@ struct RsPassArgs {
     int pass;
     int xcd_band;             // counted tiles: tile = band mapping of the block id (see rs_pass_kernel)
     int last;                 // cond 0: this pass is the final one
+    int range_shift;          // ranges: the key's small integer is key >> range_shift (tile keys with depth bits below it)
     int cond;                 // 0: plain; 1: final unless the wide flag is up (depth, third pass); 2: runs only if it is (fourth)
     const uint32_t* wide;
     uint2* ranges;            // final pass of a sort whose keys are SMALL integers (tile ids): [key] receives {first, last + 1}
@@ -807,12 +820,15 @@ __global__ void __launch_bounds__(RS_THREADS, (SCANNED && ITEMS == RS_ITEMS_WIDE
             const uint32_t p = (uint32_t)i * RS_THREADS + t;
             uint32_t l = (uint32_t)__shfl_up((int)key[i], 1, 64);
             if (lane == 0) l = wv > 0 ? s_edge[(wv - 1) * ITEMS + i] : (i > 0 ? s_edge[(RS_WAVES - 1) * ITEMS + i - 1] : 0xFFFFFFFFu);
-            if (p < tile_n && (p == 0 || l != key[i])) {
-                atomicMin(&a.ranges[key[i]].x, g[i]);
+            // (tile keys that carry depth bits: pairs of one tile are neighbours too -- the tile field is the top of the
+            //  sorted bits -- and only that field opens and closes a run)
+            const uint32_t kr = key[i] >> a.range_shift, lr = l >> a.range_shift;
+            if (p < tile_n && (p == 0 || lr != kr)) {
+                atomicMin(&a.ranges[kr].x, g[i]);
                 if (p > 0)          // the piece that ends at p - 1: its last position follows from ITS digit's base
-                    atomicMax(&a.ranges[l].y, gbase[(rs_xf(l, a.sub) >> a.shift) & (RADIX - 1)] + p);
+                    atomicMax(&a.ranges[lr].y, gbase[(rs_xf(l, a.sub) >> a.shift) & (RADIX - 1)] + p);
             }
-            if (p + 1 == tile_n) atomicMax(&a.ranges[key[i]].y, g[i] + 1u);
+            if (p + 1 == tile_n) atomicMax(&a.ranges[kr].y, g[i] + 1u);
         }
     }
     RS_STAMP(5);
@@ -873,10 +889,11 @@ void radix_zero_region(void* temp, uint64_t n, int bits, uint32_t** ptr, size_t*
     *ptr = t.hist;
     *words = t.zero_bytes / 4;
 }
-void radix_depth_zero_region(void* temp, uint64_t n, uint32_t** ptr, size_t* words) {
+void radix_depth_zero_region(void* temp, uint64_t n, uint32_t** ptr, size_t* words, bool header_only) {
     const RsTemp t = rs_carve(temp, n ? n : 1, rs_plan_for_depth(n ? n : 1), rs_scanned(n ? n : 1));
     *ptr = t.hist;
-    *words = t.zero_bytes / 4;
+    // header only (per-tile depth order, no depth sort runs): histograms, tickets, the error words the consumers check
+    *words = header_only ? (size_t)((char*)t.status - (char*)t.hist) / 4 : t.zero_bytes / 4;
 }
 
 // does a sort of n pairs read a global digit histogram (one-sweep path) -- i.e. is it worth counting one while the keys are produced?
@@ -917,7 +934,7 @@ struct RsBuffers {
     bool aux_skip_ones;
 };
 static int rs_run(const RsPlan& pl, const RsBuffers& b, uint64_t n, void* temp, hipStream_t s, const uint32_t* n_dev,
-                  bool temp_zeroed, const uint32_t* ext_hist, bool exclusive) {
+                  bool temp_zeroed, const uint32_t* ext_hist, bool exclusive, int key_shift = 0) {
     if (n == 0) return 0;
     if (n >= (1ull << 32)) { set_error("radix sort: more than 2^32-1 pairs"); return 1; }
     const bool scanned = rs_scanned(n);
@@ -972,7 +989,10 @@ static int rs_run(const RsPlan& pl, const RsBuffers& b, uint64_t n, void* temp, 
         a.vfinal = b.vfinal ? b.vfinal : vout;
         a.kfinal = b.vfinal ? b.kfinal : kout;
         a.ranges = (!pl.depth && p == pl.npasses - 1) ? b.ranges : nullptr;
-        if (a.ranges) a.kfinal = nullptr;       // whoever asks for the ranges does not read the sorted keys: 4 n bytes of stores less
+        a.range_shift = key_shift;
+        // whoever asks for the ranges of plain tile ids does not read the sorted keys: 4 n bytes of stores less (tile keys
+        // with depth bits keep them: tile_depth_sort_kernel reads them)
+        if (a.ranges && key_shift == 0) a.kfinal = nullptr;
         a.aux_in = b.aux_in; a.aux_out = b.aux_out; a.aux_skip_ones = b.aux_skip_ones ? 1 : 0;
         if (scanned) {
             RsTileHistArgs h;
@@ -1006,14 +1026,15 @@ static int rs_run(const RsPlan& pl, const RsBuffers& b, uint64_t n, void* temp, 
 
 int radix_sort_pairs(uint32_t* ka, uint32_t* va, uint32_t* kb, uint32_t* vb, uint64_t n, int bits, void* temp,
                      hipStream_t s, const uint32_t* n_dev, bool temp_zeroed, const uint2* aux_in, uint2* aux_out,
-                     const uint32_t* ext_hist, bool aux_empty_for_ones, bool exclusive, uint2* ranges) {
-    const RsPlan pl = rs_plan_plain(bits);
+                     const uint32_t* ext_hist, bool aux_empty_for_ones, bool exclusive, uint2* ranges, int key_shift) {
+    RsPlan pl = rs_plan_plain(bits);
+    for (int p = 0; p < RS_MAX_PASSES; ++p) pl.shift[p] += key_shift;      // (same passes, same scratch, same result side)
     if (pl.npasses > RS_MAX_PASSES) { set_error("radix sort: more than 32 key bits"); return 1; }
     RsBuffers b;
     b.ranges = ranges;
     b.ka = ka; b.va = va; b.va_is_index = false; b.pa = nullptr; b.kb = kb; b.vb = vb; b.pb = nullptr; b.kfinal = nullptr; b.vfinal = nullptr;
     b.aux_in = aux_in; b.aux_out = aux_out; b.aux_skip_ones = aux_empty_for_ones;
-    return rs_run(pl, b, n, temp, s, n_dev, temp_zeroed, ext_hist, exclusive);
+    return rs_run(pl, b, n, temp, s, n_dev, temp_zeroed, ext_hist, exclusive, key_shift);
 }
 
 // The depth sort of the forward (see the header): keys[P] = float bits of the depths (all ones: culled), destroyed;

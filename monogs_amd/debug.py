@@ -18,11 +18,17 @@ def _au(v, a=256):
 def forward_tables(rs, means3D, opacities, colors_precomp=None, shs=None, scales=None, rotations=None,
                    cov3D_precomp=None, between=None):
     """Run the HIP forward and return outputs plus the per-tile tables as torch tensors.  ``between``: called after the
-    first stage (per-Gaussian kernel, depth sort, scan) has finished and before the second (duplicate, tile sort, blend) starts."""
+    first stage (per-Gaussian kernel, depth sort, scan) has finished and before the second (duplicate, tile sort, blend) starts.
+
+    ``depth_path`` tells which depth order the forward built (``mgs_binning_path``): "global" (a depth sort of all
+    Gaussians, whose result ``perm`` is read from the scratch) or "per_tile" (each tile's list sorted by depth on its own).
+    On the per-tile path no kernel materialises ``perm``: it is derived here from the depth keys, in the order the global
+    sort defines -- visible Gaussians by (depth key, index), culled ones (key of all ones) last, by index."""
     lib = _lib.load()
     dev = means3D.device
     P = means3D.shape[0]
     H, W = int(rs.image_height), int(rs.image_width)
+    per_tile = lib.mgs_binning_path(P, W, H) == 1
     c = lambda t, n: None if t is None else _f32(t.detach(), n)  # noqa: E731
     means3D, opacities = c(means3D, "means3D"), c(opacities, "opacities")
     colors_precomp, shs, scales = c(colors_precomp, "colors"), c(shs, "shs"), c(scales, "scales")
@@ -80,14 +86,22 @@ def forward_tables(rs, means3D, opacities, colors_precomp=None, shs=None, scales
     # geometry scratch after rec (GeometryState::carve, csrc/api.hip): depth_key, depth_alt, iota, iota_alt (the depth
     # sort's ping-pong buffers), perm (its result), point_offsets, scan_blocks, clamped, rect (by Gaussian index: consumed
     # by the sort, possibly as its packed payload), rect_sorted {x0 | y0 << 16, w | h << 16} in depth order
-    perm = view(geom, o + 4 * _au(P * 4), P * 4, torch.int32)
     o_rect = o + 6 * _au(P * 4) + _au(((P + 2047) // 2048 + 64) * 4) + _au(P * 4)
-    wh_sorted = view(geom, o_rect + _au(P * 8), P * 8, torch.int32).reshape(P, 2)[:, 1]
-    tiles_touched = torch.zeros(P, dtype=torch.int32, device=geom.device)
-    # tiles each Gaussian touches = w * h of its rectangle (scattered back from depth order to Gaussian index)
-    tiles_touched[perm.long()] = (wh_sorted & 0xFFFF) * ((wh_sorted >> 16) & 0xFFFF)
+    if per_tile:
+        # rect {x0 | y0 << 16, w | h << 16} by Gaussian index (what the scan and duplicate read); perm from the depth keys
+        keys = view(geom, o, P * 4, torch.int32).long() & 0xFFFFFFFF
+        perm = torch.sort(keys, stable=True).indices.to(torch.int32)
+        wh = view(geom, o_rect, P * 8, torch.int32).reshape(P, 2)[:, 1]
+        tiles_touched = (wh & 0xFFFF) * ((wh >> 16) & 0xFFFF)
+    else:
+        perm = view(geom, o + 4 * _au(P * 4), P * 4, torch.int32)
+        wh_sorted = view(geom, o_rect + _au(P * 8), P * 8, torch.int32).reshape(P, 2)[:, 1]
+        tiles_touched = torch.zeros(P, dtype=torch.int32, device=geom.device)
+        # tiles each Gaussian touches = w * h of its rectangle (scattered back from depth order to Gaussian index)
+        tiles_touched[perm.long()] = (wh_sorted & 0xFFFF) * ((wh_sorted >> 16) & 0xFFFF)
     depth_key = rec[:, 11].contiguous().view(torch.int32)          # float32 bits of the view-space depth
     return dict(color=color, depth=depth, opacity=opacity, radii=radii, n_touched=n_touched, num_rendered=R,
                 status=int(status.item()),
                 final_T=final_T, n_contrib=n_contrib, ranges=ranges, tile_sorted=tile_sorted,
-                point_list=point_list, rec=rec, tiles_touched=tiles_touched, depth_key=depth_key, perm=perm)
+                point_list=point_list, rec=rec, tiles_touched=tiles_touched, depth_key=depth_key, perm=perm,
+                depth_path="per_tile" if per_tile else "global")
