@@ -80,9 +80,10 @@ typedef struct mgs_timing {
     float depth_sort_ms;
     float scan_ms;
     float duplicate_ms;
-    float sort_ms;
+    float sort_ms;        /* the tile sort; on the per-tile path (mgs_binning_path) also the per-tile depth sort when it runs as a
+                             launch of its own (option "tile_sort_fused" = 0) -- by default it runs inside the blend forward */
     float ranges_ms;      /* always 0 since ABI v8: the tile sort's final pass writes the ranges (kept for layout compatibility) */
-    float blend_fwd_ms;
+    float blend_fwd_ms;   /* per-tile path, by default: includes the per-tile depth sort */
     float blend_bwd_ms;
     float geom_bwd_ms;
 } mgs_timing;
@@ -170,6 +171,8 @@ int mgs_debug_set_radix_spin_limit(uint32_t limit);
  * depth sort + rectangle gather + scan as ONE single-workgroup launch: measured slower, off by default), "blend_lds_pad_fwd" / "blend_lds_pad_bwd" (dynamic
  * LDS bytes the blend kernels never touch: fewer workgroups per compute unit, a measurement knob),
  * "dup_slot_major" (0 / 1 = the duplicate kernel's emission balanced by Gaussians / by output slots at every size),
+ * "tile_sort_fused" (per-tile path: 1 = default, each blend forward workgroup sorts its own tile's list first; 0 = the
+ * per-tile depth sort as a launch of its own between the tile sort and the blend forward; the same lists either way),
  * "knn_grid_min" (Morton-box kNN from this many points), "blend_bwd_transposed" (2 = default, 1 = round 3's transposed blend
  * backward fed by per-survivor scalar loads, 0 = the per-survivor wave reduction),
  * "radix_xcd_band" (0 = counted tiles in block-id order instead of one contiguous band of tiles per XCD), "radix_tile_items"

@@ -224,6 +224,8 @@ int mgs_forward_preprocess(const mgs_camera* cam, int32_t P, const float* means3
     return 0;
 }
 
+static int g_opt_tile_sort_fused = 1;        // mgs_debug_set_option("tile_sort_fused", 0): the per-tile depth sort as a launch of its own
+
 static int forward_render_impl(const mgs_camera* cam, int32_t P, uint64_t R, bool capacity, void* geometry,
                                void* binning, void* image, float* out_color, float* out_depth, float* out_opacity,
                                int32_t* n_touched, uint32_t* overflow, mgs_timing* timing, void* stream) {
@@ -256,13 +258,18 @@ static int forward_render_impl(const mgs_camera* cam, int32_t P, uint64_t R, boo
     // (the sort's final pass writes the per-tile ranges: no ranges launch since round 4)
     if (int rc = launch_sort(g, b, R, tile_bits(W, H), s, n_dev, (cam->flags & MGS_FLAG_EXCLUSIVE_DEVICE) != 0, img.ranges,
                              per_tile)) return rc;
-    // per-tile depth order: each tile's list, in index order now, sorted by depth in LDS (timed with the sort)
-    if (per_tile)
-        if (int rc = launch_tile_depth_sort(*cam, P, g, b, img, R, n_dev, s)) return rc;
+    const uint32_t* sort_err = R > 0 ? radix_error_flag(b.sort_temp, R, tile_bits(W, H)) : nullptr;
+    // per-tile depth order: each tile's list, in index order now, sorted by depth in LDS -- by the blend forward's workgroup
+    // of the tile (timed with the blend forward), or by a launch of its own (timed with the sort)
+    const bool sort_tiles = per_tile && R > 0;
+    const TileSortArgs ts = sort_tiles ? tile_sort_args(*cam, g, b, R, n_dev) : TileSortArgs{};
+    const bool fused = sort_tiles && g_opt_tile_sort_fused != 0;
+    if (sort_tiles && !fused)
+        if (int rc = launch_tile_depth_sort(*cam, ts, img, sort_err, s)) return rc;
     tm.mark();
     if (g_dbg_fwd_events[0]) MGS_HIP(hipEventRecord(g_dbg_fwd_events[0], s));
-    if (int rc = launch_blend_forward(*cam, g, b, img, out_color, out_depth, out_opacity, n_touched,
-                                      R > 0 ? radix_error_flag(b.sort_temp, R, tile_bits(W, H)) : nullptr, overflow, s)) return rc;
+    if (int rc = launch_blend_forward(*cam, g, b, img, out_color, out_depth, out_opacity, n_touched, sort_err, overflow,
+                                      fused ? &ts : nullptr, s)) return rc;
     if (g_dbg_fwd_events[1]) MGS_HIP(hipEventRecord(g_dbg_fwd_events[1], s));
     tm.mark();
     if (timing) {
@@ -431,6 +438,7 @@ int mgs_debug_set_option(const char* name, int64_t value) {
     if (name && !strcmp(name, "blend_bwd_transposed")) { g_opt_blend_bwd_transposed = (int)value; return 0; }
     if (name && !strcmp(name, "scan_small")) { g_opt_scan_small = (int)value; return 0; }
     if (name && !strcmp(name, "depth_small")) { g_opt_depth_small = (int)value; return 0; }
+    if (name && !strcmp(name, "tile_sort_fused")) { g_opt_tile_sort_fused = value < 0 ? 1 : (int)value; return 0; }
     if (name && !strcmp(name, "blend_lds_pad_fwd")) { g_opt_blend_lds_pad_fwd = (int)value; return 0; }
     if (name && !strcmp(name, "blend_lds_pad_bwd")) { g_opt_blend_lds_pad_bwd = (int)value; return 0; }
     if (name && !strcmp(name, "knn_grid_min")) { g_opt_knn_grid_min = value > 0x7FFFFFFF ? 0x7FFFFFFF : (int)value; return 0; }

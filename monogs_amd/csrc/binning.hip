@@ -13,6 +13,7 @@
 // the hand-written LSD radix sort of radix_sort.hip.  The last pass of the depth sort also lays the tile
 // rectangles out in depth order, so the scan and duplicate below read everything coalesced.
 #include "common.h"
+#include "tile_sort.h"
 
 
 namespace mgs {
@@ -639,251 +640,39 @@ int launch_sort(const GeometryState& g, const BinningState& b, uint64_t R, int b
 }
 
 // ------------------------------------------------------------------------------------------------
-// Per-tile depth order (binning_path() == 1: large maps).  Instead of a global depth sort of all P Gaussians (three or
-// four counted-tiles passes: ~105 us at C5, 2 M Gaussians), duplicate_kernel emits the instances in Gaussian-index order
-// with the depth packed into the pair (see dup_pair), the stable tile sort groups them by tile -- index order inside a
-// tile -- and ONE workgroup per tile sorts its list by depth here, stably, in LDS.  Result: (depth bits, index) order
-// inside every tile, bit for bit what the two global sorts produce.
-//   * a list of <= TDS_CAP pairs: keys = depth27 - (the tile's minimum), LSD passes of 9 bits over the significant bits
-//     only (C5: 500 - 851 pairs per tile, ~25 significant bits: three passes).  Ranking as in the radix sort: a returning
-//     LDS atomic on the wave's digit counter (lanes of one DS instruction in lane order, a wave's instructions in program
-//     order: stable); wave w owns elements [w * 256, (w + 1) * 256), row i of them 64 consecutive ones.
-//   * depths beyond the narrow range were clamped to DEPTH_KEY_NARROW: those pairs form the LAST run of the sorted list,
-//     still in index order; it is re-sorted by the full depth key (gathered through the index), the same way.
-//   * a longer list (a scene of large splats, never C5): the same LSD sort over the tile's segment in global memory,
-//     256 pairs at a time with running digit offsets, on the full depth key, ping-ponging through the other half of the
-//     tile sort's buffers (free once it is done); four 8-bit passes end in the original buffers.
-// The indices are written in place over the tile's values: b.vals_sorted is the blend kernels' point_list.
+// Per-tile depth order (binning_path() == 1: large maps): tile_sort.h.  By default blend_forward_kernel<true> sorts its
+// own tile's list before it walks it (option "tile_sort_fused"); this kernel is the same sort as a launch of its own,
+// one 256-thread workgroup per tile.
 // ------------------------------------------------------------------------------------------------
-constexpr int TDS_THREADS = 256, TDS_WAVES = TDS_THREADS / WAVE, TDS_ITEMS = 4, TDS_CAP = TDS_THREADS * TDS_ITEMS;
-constexpr int TDS_DB = 9, TDS_RADIX = 1 << TDS_DB, TDS_DPT = TDS_RADIX / TDS_THREADS;
-
-// block-wide min / max of one value per thread (valid lanes only); every thread gets both
-__device__ __forceinline__ void tds_minmax(uint32_t lo, uint32_t hi, uint32_t* s_red /* >= 2 * TDS_WAVES */, uint32_t& mn,
-                                           uint32_t& mx) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        lo = min(lo, (uint32_t)__shfl_xor((int)lo, o, 64));
-        hi = max(hi, (uint32_t)__shfl_xor((int)hi, o, 64));
-    }
-    if (lane == 0) { s_red[wv] = lo; s_red[TDS_WAVES + wv] = hi; }
-    __syncthreads();
-    mn = s_red[0]; mx = s_red[TDS_WAVES];
-#pragma unroll
-    for (int w = 1; w < TDS_WAVES; ++w) { mn = min(mn, s_red[w]); mx = max(mx, s_red[TDS_WAVES + w]); }
-    __syncthreads();                                      // (s_red is reused)
+TileSortArgs tile_sort_args(const mgs_camera& cam, const GeometryState& g, const BinningState& b, uint64_t R,
+                            const uint32_t* n_dev) {
+    TileSortArgs ts;
+    ts.keys = b.keys_sorted;
+    ts.vals = b.vals_sorted;
+    ts.keys_alt = b.keys_sorted == b.keys_a ? b.keys_b : b.keys_a;
+    ts.vals_alt = b.vals_sorted == b.vals_a ? b.vals_b : b.vals_a;
+    ts.depth_key = g.depth_key;
+    ts.n_dev = n_dev;
+    ts.n_cap = (uint32_t)R;
+    ts.tb = tile_bits(cam.image_width, cam.image_height);
+    return ts;
 }
 
-// stable LSD sort of the LDS pairs [base, base + m), m <= TDS_CAP, on key bits [0, bits)
-__device__ __forceinline__ void tds_lds_sort(uint32_t* s_k, uint32_t* s_v, uint32_t (*s_cnt)[TDS_RADIX], uint32_t* s_wsum,
-                                             int base, int m, int bits) {
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    for (int sh = 0; sh < bits; sh += TDS_DB) {
-#pragma unroll
-        for (int w = 0; w < TDS_WAVES; ++w)
-#pragma unroll
-            for (int j = 0; j < TDS_DPT; ++j) s_cnt[w][t * TDS_DPT + j] = 0u;
-        __syncthreads();                                  // (also: the previous pass's scatter is visible)
-        uint32_t k[TDS_ITEMS], v[TDS_ITEMS], r[TDS_ITEMS];
-#pragma unroll
-        for (int i = 0; i < TDS_ITEMS; ++i) {
-            const int e = wv * (TDS_ITEMS * WAVE) + i * WAVE + lane;
-            k[i] = 0u; v[i] = 0u; r[i] = 0u;
-            if (e < m) {
-                k[i] = s_k[base + e]; v[i] = s_v[base + e];
-                r[i] = __hip_atomic_fetch_add(&s_cnt[wv][(k[i] >> sh) & (TDS_RADIX - 1)], 1u, __ATOMIC_RELAXED,
-                                              __HIP_MEMORY_SCOPE_WORKGROUP);
-            }
-        }
-        __syncthreads();
-        // thread t owns digits t * DPT + j: per-wave exclusive prefixes on top of the exclusive prefix over the digits
-        uint32_t c[TDS_DPT][TDS_WAVES], tot[TDS_DPT], tsum = 0;
-#pragma unroll
-        for (int j = 0; j < TDS_DPT; ++j) {
-            tot[j] = 0u;
-#pragma unroll
-            for (int w = 0; w < TDS_WAVES; ++w) { c[j][w] = s_cnt[w][t * TDS_DPT + j]; tot[j] += c[j][w]; }
-            tsum += tot[j];
-        }
-        const uint32_t incl = wave_incl_scan_dpp(tsum);
-        if (lane == 63) s_wsum[wv] = incl;
-        __syncthreads();
-        uint32_t run = incl - tsum;
-        for (int w = 0; w < wv; ++w) run += s_wsum[w];
-#pragma unroll
-        for (int j = 0; j < TDS_DPT; ++j)
-#pragma unroll
-            for (int w = 0; w < TDS_WAVES; ++w) { s_cnt[w][t * TDS_DPT + j] = run; run += c[j][w]; }
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < TDS_ITEMS; ++i) {
-            const int e = wv * (TDS_ITEMS * WAVE) + i * WAVE + lane;
-            if (e < m) {
-                const uint32_t dst = s_cnt[wv][(k[i] >> sh) & (TDS_RADIX - 1)] + r[i];
-                s_k[base + dst] = k[i]; s_v[base + dst] = v[i];
-            }
-        }
-        __syncthreads();                                  // (every wave is done with the offsets before the next pass clears them)
-    }
-    __syncthreads();
-}
-
-// A list longer than TDS_CAP: stable LSD sort of the segment [0, n) of (kx, vx) on the full depth key, 8 bits per pass,
-// ping-ponging through (ky, vy); rare (large splats), so simple: one pair per thread per step.
-__device__ void tds_global_sort(uint32_t* __restrict__ kx, uint32_t* __restrict__ vx, uint32_t* __restrict__ ky,
-                                uint32_t* __restrict__ vy, uint32_t n, const uint32_t* __restrict__ depth_key, int lo,
-                                uint32_t (*s_cnt)[TDS_RADIX], uint32_t* s_run, uint32_t* s_wsum) {
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    const uint32_t imask = lo ? (1u << (32 - lo)) - 1u : 0xFFFFFFFFu;
-    for (uint32_t e = t; e < n; e += TDS_THREADS) {       // in place: (packed key, packed value) -> (full key, index)
-        const uint32_t g = vx[e] & imask;
-        kx[e] = depth_key[g] - DEPTH_KEY_SUB;
-        vx[e] = g;
-    }
-    for (int sh = 0; sh < 32; sh += 8) {
-        __threadfence();                                  // (this workgroup's stores, read back by other lanes)
-        if (t < 256) s_run[t] = 0u;
-#pragma unroll
-        for (int w = 0; w < TDS_WAVES; ++w) s_cnt[w][t] = 0u;
-        __syncthreads();
-        for (uint32_t e = t; e < n; e += TDS_THREADS) atomicAdd(&s_run[(kx[e] >> sh) & 255u], 1u);
-        __syncthreads();
-        {                                                 // exclusive scan of the 256 digit counts: running offsets
-            const uint32_t c = s_run[t], incl = wave_incl_scan_dpp(c);
-            if (lane == 63) s_wsum[wv] = incl;
-            __syncthreads();
-            uint32_t b0 = incl - c;
-            for (int w = 0; w < wv; ++w) b0 += s_wsum[w];
-            s_run[t] = b0;
-        }
-        __syncthreads();
-        for (uint32_t c0 = 0; c0 < n; c0 += TDS_THREADS) {
-            const uint32_t e = c0 + (uint32_t)t;          // element order = (wave, lane) order
-            uint32_t k = 0u, v = 0u, r = 0u, d = 0u;
-            if (e < n) {
-                k = kx[e]; v = vx[e]; d = (k >> sh) & 255u;
-                r = __hip_atomic_fetch_add(&s_cnt[wv][d], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            }
-            __syncthreads();
-            uint32_t pre[TDS_WAVES];                      // thread t = digit t: where each wave's pairs of it go
-            {
-                uint32_t run = s_run[t];
-#pragma unroll
-                for (int w = 0; w < TDS_WAVES; ++w) { const uint32_t c = s_cnt[w][t]; pre[w] = run; run += c; }
-                s_run[t] = run;
-            }
-            __syncthreads();
-#pragma unroll
-            for (int w = 0; w < TDS_WAVES; ++w) s_cnt[w][t] = pre[w];
-            __syncthreads();
-            if (e < n) { const uint32_t dst = s_cnt[wv][d] + r; ky[dst] = k; vy[dst] = v; }
-            __syncthreads();
-#pragma unroll
-            for (int w = 0; w < TDS_WAVES; ++w) s_cnt[w][t] = 0u;
-            __syncthreads();
-        }
-        __threadfence();
-        __syncthreads();
-        uint32_t* tk = kx; kx = ky; ky = tk;
-        uint32_t* tv = vx; vx = vy; vy = tv;
-    }
-}
-
-__global__ void __launch_bounds__(TDS_THREADS) tile_depth_sort_kernel(const uint2* __restrict__ ranges, int ntiles,
-                                                                       uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
-                                                                       uint32_t* __restrict__ keys_alt, uint32_t* __restrict__ vals_alt,
-                                                                       const uint32_t* __restrict__ depth_key, int tb, uint32_t n_cap,
-                                                                       const uint32_t* __restrict__ n_dev,
-                                                                       const uint32_t* __restrict__ sort_err) {
+__global__ void __launch_bounds__(TDS_THREADS) tile_depth_sort_kernel(TileSortArgs ts, const uint2* __restrict__ ranges,
+                                                                       int ntiles, const uint32_t* __restrict__ sort_err) {
     __shared__ uint32_t s_k[TDS_CAP], s_v[TDS_CAP];
     __shared__ uint32_t s_cnt[TDS_WAVES][TDS_RADIX];
     __shared__ uint32_t s_wsum[TDS_WAVES], s_red[2 * TDS_WAVES];
-    const int tile = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const int tile = blockIdx.x;
     if (tile >= ntiles) return;
     // a timed-out tile sort left the ranges invalid: blend_forward_kernel empties every tile, nothing to order here
-    if (sort_err && radix_failed(sort_err) != 0u) return;
-    const uint32_t n_live = n_dev ? min(n_cap, n_dev[0]) : n_cap;     // capacity mode: never past the live pairs
-    const uint2 rg = ranges[tile];                                     // {~0, 0}: empty
-    const uint32_t start = rg.x, end = min(rg.y, n_live);
-    if (start >= end) return;
-    const uint32_t n = end - start;
-    const int lo = tile_depth_lo_bits(tb);
-    const uint32_t kmask = tb < 32 ? (0xFFFFFFFFu >> tb) : 0u, imask = lo ? (1u << (32 - lo)) - 1u : 0xFFFFFFFFu;
-    if (n > (uint32_t)TDS_CAP) {
-        tds_global_sort(keys + start, vals + start, keys_alt + start, vals_alt + start, n, depth_key, lo, s_cnt, s_k, s_wsum);
-        return;
-    }
-    // ---- load (wave-striped), unpack depth27 and index, range of the depths
-    uint32_t d[TDS_ITEMS], g[TDS_ITEMS];
-    uint32_t dmin = 0xFFFFFFFFu, dmax = 0u;
-#pragma unroll
-    for (int i = 0; i < TDS_ITEMS; ++i) {
-        const uint32_t e = (uint32_t)(wv * (TDS_ITEMS * WAVE) + i * WAVE + lane);
-        d[i] = 0u; g[i] = 0u;
-        if (e < n) {
-            const uint32_t k = keys[start + e], v = vals[start + e];
-            d[i] = ((k & kmask) << lo) | (lo ? v >> (32 - lo) : 0u);
-            g[i] = v & imask;
-            dmin = min(dmin, d[i]); dmax = max(dmax, d[i]);
-        }
-    }
-    uint32_t mn, mx;
-    tds_minmax(dmin, dmax, s_red, mn, mx);
-#pragma unroll
-    for (int i = 0; i < TDS_ITEMS; ++i) {
-        const int e = wv * (TDS_ITEMS * WAVE) + i * WAVE + lane;
-        if (e < (int)n) { s_k[e] = d[i] - mn; s_v[e] = g[i]; }
-    }
-    const uint32_t span = mx - mn;
-    tds_lds_sort(s_k, s_v, s_cnt, s_wsum, 0, (int)n, span ? 32 - __builtin_clz(span) : 0);
-    if (mx == DEPTH_KEY_NARROW) {
-        // ---- clamped depths: the trailing run of keys DEPTH_KEY_NARROW - mn, in index order; re-sort it by the full key
-        uint32_t c = 0;
-#pragma unroll
-        for (int i = 0; i < TDS_ITEMS; ++i) {
-            const uint32_t e = (uint32_t)(wv * (TDS_ITEMS * WAVE) + i * WAVE + lane);
-            c += (e < n && d[i] == DEPTH_KEY_NARROW) ? 1u : 0u;
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) c += (uint32_t)__shfl_xor((int)c, o, 64);
-        if (lane == 0) s_red[wv] = c;
-        __syncthreads();
-        uint32_t m = 0;
-#pragma unroll
-        for (int w = 0; w < TDS_WAVES; ++w) m += s_red[w];
-        __syncthreads();
-        const uint32_t f = n - m;                                    // first pair of the run
-        uint32_t xmin = 0xFFFFFFFFu, xmax = 0u;
-        for (uint32_t e = f + t; e < n; e += TDS_THREADS) {
-            const uint32_t x = depth_key[s_v[e]] - DEPTH_KEY_SUB;
-            s_k[e] = x;
-            xmin = min(xmin, x); xmax = max(xmax, x);
-        }
-        uint32_t rmn, rmx;
-        tds_minmax(xmin, xmax, s_red, rmn, rmx);
-        for (uint32_t e = f + t; e < n; e += TDS_THREADS) s_k[e] -= rmn;
-        __syncthreads();
-        const uint32_t rspan = rmx - rmn;
-        tds_lds_sort(s_k, s_v, s_cnt, s_wsum, (int)f, (int)m, rspan ? 32 - __builtin_clz(rspan) : 0);
-    }
-    // ---- the indices, in place (coalesced)
-#pragma unroll
-    for (int i = 0; i < TDS_ITEMS; ++i) {
-        const int e = wv * (TDS_ITEMS * WAVE) + i * WAVE + lane;
-        if (e < (int)n) vals[start + e] = s_v[e];
-    }
+    tile_depth_sort(ts, ranges[tile], sort_err && radix_failed(sort_err) != 0u, TdsLds{s_k, s_v, s_cnt, s_wsum, s_red});
 }
 
-int launch_tile_depth_sort(const mgs_camera& cam, int P, const GeometryState& g, const BinningState& b, const ImageState& img,
-                           uint64_t R, const uint32_t* n_dev, hipStream_t s) {
-    if (R == 0 || P == 0) return 0;
-    const int W = cam.image_width, H = cam.image_height, ntiles = tiles_x(W) * tiles_y(H), tb = tile_bits(W, H);
-    uint32_t* keys_alt = b.keys_sorted == b.keys_a ? b.keys_b : b.keys_a;
-    uint32_t* vals_alt = b.vals_sorted == b.vals_a ? b.vals_b : b.vals_a;
-    hipLaunchKernelGGL(tile_depth_sort_kernel, dim3(ntiles), dim3(TDS_THREADS), 0, s, img.ranges, ntiles, b.keys_sorted,
-                       b.vals_sorted, keys_alt, vals_alt, g.depth_key, tb, (uint32_t)R, n_dev,
-                       radix_error_flag(b.sort_temp, R, tb));
+int launch_tile_depth_sort(const mgs_camera& cam, const TileSortArgs& ts, const ImageState& img, const uint32_t* sort_err,
+                           hipStream_t s) {
+    const int ntiles = tiles_x(cam.image_width) * tiles_y(cam.image_height);
+    hipLaunchKernelGGL(tile_depth_sort_kernel, dim3(ntiles), dim3(TDS_THREADS), 0, s, ts, img.ranges, ntiles, sort_err);
     MGS_HIP(hipGetLastError());
     return 0;
 }

@@ -19,6 +19,7 @@
 // Skipping an instance for a whole quadrant never changes a pixel: every skipped pair has
 // alpha < 1/255 and the per-pixel rule would have skipped it too.
 #include "common.h"
+#include "tile_sort.h"
 
 #include <type_traits>
 
@@ -186,6 +187,11 @@ __device__ __forceinline__ void blend_one(unsigned long long& live, unsigned lon
     }
 }
 
+// SORT (per-tile depth order, binning_path() == 1): the workgroup first sorts its tile's list by depth (tile_sort.h) and
+// writes it to point_list for the backward; a list of <= TDS_CAP pairs is then walked from the LDS copy of the sorted
+// indices.  The sort's keys and digit counters live in the record queue's LDS (first written after the sort's last
+// barrier), so the workgroup's LDS grows by the 4 KB index list only.  SORT = false: point_list is already in depth order.
+template <bool SORT>
 __global__ void __launch_bounds__(256) blend_forward_kernel(BlendArgs a, float* __restrict__ out_color,
                                                             float* __restrict__ out_depth,
                                                             float* __restrict__ out_opacity,
@@ -194,7 +200,7 @@ __global__ void __launch_bounds__(256) blend_forward_kernel(BlendArgs a, float* 
                                                             int32_t* __restrict__ n_touched,
                                                             uint2* ranges_rw /* = a.ranges: read AND written here, through this pointer only */,
                                                             const uint32_t* __restrict__ sort_err,
-                                                            uint32_t* __restrict__ status) {
+                                                            uint32_t* __restrict__ status, TileSortArgs ts) {
     MGS_TILE_WAVE(a.gx * ((a.H + TILE - 1) / TILE), tile, wave, ws)
     const int tx = tile % a.gx, ty = tile / a.gx;
     const int lane = threadIdx.x & 63;
@@ -212,8 +218,9 @@ __global__ void __launch_bounds__(256) blend_forward_kernel(BlendArgs a, float* 
     //  of this table for the kernels that only read it; the other waves of the workgroup may see the table before or after lane 0's
     //  store: both forms decode to the same range.  The backward relies on the canonical {0, 0} written here.)
     uint2 range = ranges_rw[tile];
+    const uint2 range_raw = range;
+    const bool sort_bad = sort_err != nullptr && radix_failed(sort_err) != 0u;
     {
-        const bool sort_bad = sort_err != nullptr && radix_failed(sort_err) != 0u;
         if (sort_bad && tile == 0 && first_of_tile && status) atomicOr(status, (uint32_t)MGS_STATUS_TILE_SORT_TIMEOUT);
         if (sort_bad || range.x >= range.y) {
             range = make_uint2(0u, 0u);
@@ -288,6 +295,20 @@ __global__ void __launch_bounds__(256) blend_forward_kernel(BlendArgs a, float* 
     }
 #else
     __shared__ __attribute__((aligned(16))) float4 s_queue[MGS_WG_WAVES][WAVE][3];
+    // SORT: the tile's sorted indices (<= TDS_CAP), and the sort's reductions; its keys and digit counters alias the queue
+    __shared__ uint32_t s_list[TDS_CAP], s_wsum[TDS_WAVES], s_red[2 * TDS_WAVES];
+    static_assert(sizeof(s_queue) == sizeof(uint32_t) * (TDS_CAP + TDS_WAVES * TDS_RADIX), "sort scratch = record queue");
+    bool list_in_lds = false;                       // (tile-uniform) walk the indices from s_list, not from point_list
+    if constexpr (SORT) {
+        uint32_t* const s_k = reinterpret_cast<uint32_t*>(&s_queue[0][0][0]);
+        const uint32_t n_lds = tile_depth_sort(ts, range_raw, sort_bad,
+                                               TdsLds{s_k, s_list, reinterpret_cast<uint32_t (*)[TDS_RADIX]>(s_k + TDS_CAP),
+                                                      s_wsum, s_red});
+        list_in_lds = n_lds != 0u && n_lds == range.y - range.x;
+        // otherwise the walk reads the in-place result from point_list: every wave's stores first (a tile that was not
+        // sorted at all passes this barrier too: the condition is uniform over the workgroup)
+        if (!list_in_lds) __syncthreads();
+    }
     float4 c1_n = make_float4(0.f, 0.f, 0.f, 0.f), c2_n = c1_n;
     float4* const my_entry = &s_queue[ws][lane][0];
     // LDS byte address of this wave's queue, in a scalar register: an entry's address is then scalar arithmetic + one v_mov
@@ -296,7 +317,8 @@ __global__ void __launch_bounds__(256) blend_forward_kernel(BlendArgs a, float* 
         gid_n = 0;
         box_n = make_float4(0.f, 0.f, -1.f, -1.f);
         if (i < range.y) {
-            gid_n = a.point_list[i];
+            if constexpr (SORT) gid_n = list_in_lds ? s_list[i - range.x] : ts.vals[i];
+            else gid_n = a.point_list[i];
             box_n = a.rec[(size_t)gid_n * 4];
             ell_n = a.rec[(size_t)gid_n * 4 + 3];
             c1_n = a.rec[(size_t)gid_n * 4 + 1];
@@ -387,7 +409,8 @@ static BlendArgs make_args(const mgs_camera& cam, const GeometryState& g, const 
 
 int launch_blend_forward(const mgs_camera& cam, const GeometryState& g, const BinningState& b,
                          const ImageState& img, float* out_color, float* out_depth, float* out_opacity,
-                         int32_t* n_touched, const uint32_t* sort_err, uint32_t* status, hipStream_t s) {
+                         int32_t* n_touched, const uint32_t* sort_err, uint32_t* status, const TileSortArgs* tile_sort,
+                         hipStream_t s) {
     BlendArgs a = make_args(cam, g, b, img);
 #ifdef BS_TRACE
     a.trace = g_trace_fwd;
@@ -395,8 +418,21 @@ int launch_blend_forward(const mgs_camera& cam, const GeometryState& g, const Bi
     const int ntiles = a.gx * tiles_y(a.H);
     if (ntiles == 0) return 0;
     const dim3 grid(ntiles), block(256);
-    hipLaunchKernelGGL(blend_forward_kernel, grid, block, (size_t)g_opt_blend_lds_pad_fwd, s, a, out_color, out_depth, out_opacity,
-                       img.final_T, img.n_contrib, n_touched, img.ranges, sort_err, status);
+    const TileSortArgs ts = tile_sort ? *tile_sort : TileSortArgs{};
+#ifdef MGS_FWD_SCALAR
+    // (no record queue to hold the sort's scratch: the per-tile sort keeps its own launch in this experiment)
+    if (tile_sort)
+        if (int rc = launch_tile_depth_sort(cam, ts, img, sort_err, s)) return rc;
+    hipLaunchKernelGGL(blend_forward_kernel<false>, grid, block, (size_t)g_opt_blend_lds_pad_fwd, s, a, out_color, out_depth,
+                       out_opacity, img.final_T, img.n_contrib, n_touched, img.ranges, sort_err, status, ts);
+#else
+    if (tile_sort)
+        hipLaunchKernelGGL(blend_forward_kernel<true>, grid, block, (size_t)g_opt_blend_lds_pad_fwd, s, a, out_color, out_depth,
+                           out_opacity, img.final_T, img.n_contrib, n_touched, img.ranges, sort_err, status, ts);
+    else
+        hipLaunchKernelGGL(blend_forward_kernel<false>, grid, block, (size_t)g_opt_blend_lds_pad_fwd, s, a, out_color, out_depth,
+                           out_opacity, img.final_T, img.n_contrib, n_touched, img.ranges, sort_err, status, ts);
+#endif
     MGS_HIP(hipGetLastError());
     return 0;
 }

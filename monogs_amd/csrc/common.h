@@ -259,15 +259,30 @@ int launch_depth_sort(const GeometryState& g, int P, bool payload, hipStream_t s
 int launch_sort(const GeometryState& g, const BinningState& b, uint64_t R, int bits, hipStream_t s,
                 const uint32_t* n_dev = nullptr, bool exclusive = false, uint2* ranges = nullptr, bool per_tile = false);
 // per-tile depth order: each tile's list, grouped by the tile sort in index order, sorted by (depth, index) in place
-int launch_tile_depth_sort(const mgs_camera& cam, int P, const GeometryState& g, const BinningState& b, const ImageState& img,
-                           uint64_t R, const uint32_t* n_dev, hipStream_t s);
+// (tile_sort.h) -- by blend_forward_kernel (launch_blend_forward's `tile_sort`) or by a launch of its own
+struct TileSortArgs {
+    uint32_t* keys;                            // the tile sort's output pairs: read, and the long-list path's ping-pong
+    uint32_t* vals;                            // = point_list: the sorted indices are written here in place
+    uint32_t* keys_alt;
+    uint32_t* vals_alt;
+    const uint32_t* depth_key;
+    const uint32_t* n_dev;                     // capacity mode: live pair count (NULL: n_cap)
+    uint32_t n_cap;
+    int tb;                                    // tile bits
+};
+TileSortArgs tile_sort_args(const mgs_camera& cam, const GeometryState& g, const BinningState& b, uint64_t R,
+                            const uint32_t* n_dev);
+int launch_tile_depth_sort(const mgs_camera& cam, const TileSortArgs& ts, const ImageState& img, const uint32_t* sort_err,
+                           hipStream_t s);
 int set_radix_spin_limit(uint32_t limit);
 extern int g_opt_radix_ballot_rank, g_opt_radix_scanned, g_opt_radix_xcd_band, g_opt_radix_tile_items, g_opt_knn_grid_min, g_opt_scan_small, g_opt_dup_slot_major, g_opt_blend_bwd_transposed, g_opt_blend_lds_pad_fwd, g_opt_blend_lds_pad_bwd, g_opt_depth_small;      // test knobs (mgs_debug_set_option)
 // `sort_err`: the tile sort's error words (NULL: nothing was sorted); a raised word empties every tile and sets
-// MGS_STATUS_TILE_SORT_TIMEOUT in *status (what ranges_kernel did until round 4)
+// MGS_STATUS_TILE_SORT_TIMEOUT in *status (what ranges_kernel did until round 4).  `tile_sort` (per-tile depth order, or
+// NULL): every workgroup first sorts its tile's list (tile_sort.h)
 int launch_blend_forward(const mgs_camera& cam, const GeometryState& g, const BinningState& b,
                          const ImageState& img, float* out_color, float* out_depth, float* out_opacity,
-                         int32_t* n_touched, const uint32_t* sort_err, uint32_t* status, hipStream_t s);
+                         int32_t* n_touched, const uint32_t* sort_err, uint32_t* status, const TileSortArgs* tile_sort,
+                         hipStream_t s);
 int launch_blend_backward(const mgs_camera& cam, const GeometryState& g, const BinningState& b,
                           const ImageState& img, const float* dL_dcolor, const float* dL_ddepth,
                           float* grad_acc, bool pose_only, hipStream_t s);

@@ -6,6 +6,8 @@
 For the C5 scene (and 100 k / VGA): how many waves are resident in each tenth of the kernel's span, how long a wave lives, how the
 lifetimes of the four waves of a workgroup differ, how evenly the work (survivors) is spread over the SIMDs, and how much of the
 span is ramp-up and tail -- the 52 us (backward) / 28 us (forward) that tools/tail_probe.py finds independent of the image size.
+On the per-tile path (C5) the forward's workgroup sorts its tile's list before its waves walk it: a forward wave's start stamp is
+taken before that sort, so its lifetime includes it.
 """
 import ctypes as C
 import json
