@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define MGS_ABI_VERSION 10
+#define MGS_ABI_VERSION 11
 #define MGS_TILE 16 /* tile edge in pixels; ranges are per 16x16 tile */
 
 /* GaussianRasterizationSettings, minus `prefiltered` / `debug` which are call flags
@@ -174,7 +174,16 @@ int mgs_debug_set_radix_spin_limit(uint32_t limit);
  * "tile_sort_fused" (per-tile path: 1 = default, each blend forward workgroup sorts its own tile's list first; 0 = the
  * per-tile depth sort as a launch of its own between the tile sort and the blend forward; the same lists either way),
  * "knn_grid_min" (Morton-box kNN from this many points), "blend_bwd_transposed" (2 = default, 1 = round 3's transposed blend
- * backward fed by per-survivor scalar loads, 0 = the per-survivor wave reduction),
+ * backward fed by per-survivor scalar loads, 0 = the per-survivor wave reduction; a value set by hand names that one kernel:
+ * once 2 has been SET, it is the unsplit walk FOR THE REST OF THE PROCESS -- also for callers that only meant "the default" --
+ * until "blend_bwd_split" says otherwise or "blend_bwd_transposed" is set to -1, which alone restores the default),
+ * "blend_bwd_split" (with blend_bwd_transposed = 2 and the forward's images given to mgs_backward: 1 = every quadrant's list is
+ * walked by two waves, its front part front to back and the rest back to front, all back parts launched first; 2 = the same
+ * with the two parts of a tile in adjacent workgroups; 0 = one wave walks the whole list; -1 = the default: 1 from a mean
+ * list of 128 instances per tile, if "blend_bwd_transposed" has not been set by hand; the count is mgs_backward's
+ * num_rendered, i.e. in capacity mode the CAPACITY, so the line moves with the caller's headroom),
+ * "blend_bwd_split_min" / "blend_bwd_split_frac" (the shortest list that is split, in 64-instance steps, default 4; the
+ * front walk's share of a list in 256ths, default 32),
  * "radix_xcd_band" (0 = counted tiles in block-id order instead of one contiguous band of tiles per XCD), "radix_tile_items"
  * (8 | 12 | 16 pairs per thread on the counted-tiles path, 0 = by size; set it before any scratch is sized),
  * "debug_sort_exclusive" (1 = mgs_debug_sort_pairs sorts as under MGS_FLAG_EXCLUSIVE_DEVICE).  Nothing on the launch path
@@ -221,13 +230,17 @@ int mgs_forward_capacity(const mgs_camera* cam, int32_t P, const float* means3D,
  * the scratch of the matching forward.  Any output pointer may be NULL (that gradient is then not
  * stored); dL_dtau is [6] = (rho, theta), already summed over Gaussians.
  * scratch_prepared = 1: `backward_scratch` was handed to the matching mgs_forward_preprocess as prepare_backward and has
- * not been used by a backward since; dL_dtau must then be NULL or mgs_backward_tau(backward_scratch, P). */
+ * not been used by a backward since; dL_dtau must then be NULL or mgs_backward_tau(backward_scratch, P).
+ * `out_color` [3,H,W] and `out_depth` [1,H,W] are the images the matching forward wrote, unchanged; with them the blend
+ * backward may walk every pixel list from both ends at once (two waves per quadrant).  Either may be NULL: the lists are
+ * then walked from the back only -- the same gradients to rounding, a longer kernel on large images. */
 int mgs_backward(const mgs_camera* cam, int32_t P, uint64_t num_rendered,
                  const float* means3D, const float* shs, const float* colors_precomp,
                  const float* opacities, const float* scales, const float* rotations,
                  const float* cov3D_precomp, const int32_t* radii,
                  const void* geometry, const void* binning, const void* image,
                  const float* dL_dcolor, const float* dL_ddepth,
+                 const float* out_color, const float* out_depth,
                  float* dL_dmeans2D,  /* [P,3] NDC-scaled x,y; z = 0 */
                  float* dL_dcolors,   /* [P,3] (colors_precomp) */
                  float* dL_dopacity,  /* [P]   */
@@ -254,6 +267,10 @@ int mgs_debug_valu_ceiling(float* out, int32_t iters, void* stream);
  * with it (an mgs_timing struct synchronises per call, and a device that idles between kernels clocks the issue-bound
  * blend kernels ~8 % slower than back-to-back steps do).  Process-wide, not thread-safe, not for use under stream capture. */
 int mgs_debug_set_blend_events(void* fwd_start, void* fwd_end, void* bwd_start, void* bwd_end);
+
+/* TEST USE ONLY, process-global: 1 / 0 = the last blend backward launched by mgs_backward with blend_bwd_transposed = 2 walked
+ * the lists split / unsplit; -1 = there was none yet. */
+int mgs_debug_last_backward_split(void);
 
 /* Diagnostic (not on the hot path): counts what the blend backward of the matching forward does, into
  * stats_dev[MGS_BLEND_STATS_WORDS] (device uint64): [0] 64-instance steps walked, [1] instances that pass the per-quadrant

@@ -311,8 +311,8 @@ int mgs_forward_capacity(const mgs_camera* cam, int32_t P, const float* means3D,
 int mgs_backward(const mgs_camera* cam, int32_t P, uint64_t R, const float* means3D, const float* shs,
                  const float* colors_precomp, const float* opacities, const float* scales, const float* rotations,
                  const float* cov3D_precomp, const int32_t* radii, const void* geometry, const void* binning,
-                 const void* image, const float* dL_dcolor, const float* dL_ddepth, float* dL_dmeans2D,
-                 float* dL_dcolors, float* dL_dopacity, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh,
+                 const void* image, const float* dL_dcolor, const float* dL_ddepth, const float* out_color,
+                 const float* out_depth, float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacity, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh,
                  float* dL_dscales, float* dL_drotations, float* dL_dtau, void* backward_scratch,
                  int32_t scratch_prepared, mgs_timing* timing, void* stream) {
     if (check_cam(cam)) return 1;
@@ -351,7 +351,7 @@ int mgs_backward(const mgs_camera* cam, int32_t P, uint64_t R, const float* mean
         // colours / opacities take no gradient and do not feed the geometry (no SH): the lighter blend backward
         const bool pose_only = !dL_dcolors && !dL_dopacity && !dL_dsh && !shs;
         if (g_dbg_bwd_events[0]) MGS_HIP(hipEventRecord(g_dbg_bwd_events[0], s));
-        if (int rc = launch_blend_backward(*cam, g, b, img, dL_dcolor, dL_ddepth, grad_acc, pose_only, s)) return rc;
+        if (int rc = launch_blend_backward(*cam, g, b, img, dL_dcolor, dL_ddepth, out_color, out_depth, grad_acc, pose_only, R, s)) return rc;
         if (g_dbg_bwd_events[1]) MGS_HIP(hipEventRecord(g_dbg_bwd_events[1], s));
     }
     tm.mark();
@@ -390,6 +390,8 @@ int mgs_debug_valu_ceiling(float* out, int32_t iters, void* stream) {
     if (!out || iters < 1) { set_error("mgs_debug_valu_ceiling: bad arguments"); return 1; }
     return launch_valu_ceiling(out, iters, (hipStream_t)stream);
 }
+
+int mgs_debug_last_backward_split(void) { return g_dbg_last_bwd_split; }
 
 int mgs_debug_set_radix_spin_limit(uint32_t limit) { return set_radix_spin_limit(limit); }
 
@@ -435,7 +437,14 @@ int mgs_debug_set_option(const char* name, int64_t value) {
     if (name && !strcmp(name, "radix_xcd_band")) { g_opt_radix_xcd_band = (int)value; return 0; }
     if (name && !strcmp(name, "debug_sort_exclusive")) { g_opt_debug_sort_exclusive = (int)value; return 0; }
     if (name && !strcmp(name, "dup_slot_major")) { g_opt_dup_slot_major = (int)value; return 0; }
-    if (name && !strcmp(name, "blend_bwd_transposed")) { g_opt_blend_bwd_transposed = (int)value; return 0; }
+    if (name && !strcmp(name, "blend_bwd_transposed")) {       // (2 / 1 / 0 name one kernel each: 2 set by hand is the UNSPLIT s-kernel; -1: the default)
+        g_opt_blend_bwd_transposed = value < 0 ? 2 : (int)value;
+        g_opt_blend_bwd_transposed_set = value >= 0;
+        return 0;
+    }
+    if (name && !strcmp(name, "blend_bwd_split")) { g_opt_blend_bwd_split = value < 0 ? -1 : (int)value; return 0; }
+    if (name && !strcmp(name, "blend_bwd_split_min")) { g_opt_blend_bwd_split_min = value < 0 ? 4 : (int)value; return 0; }
+    if (name && !strcmp(name, "blend_bwd_split_frac")) { g_opt_blend_bwd_split_frac = value < 0 ? 32 : (int)value; return 0; }
     if (name && !strcmp(name, "scan_small")) { g_opt_scan_small = (int)value; return 0; }
     if (name && !strcmp(name, "depth_small")) { g_opt_depth_small = (int)value; return 0; }
     if (name && !strcmp(name, "tile_sort_fused")) { g_opt_tile_sort_fused = value < 0 ? 1 : (int)value; return 0; }

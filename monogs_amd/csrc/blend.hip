@@ -32,6 +32,7 @@ extern int g_opt_blend_lds_pad_fwd, g_opt_blend_lds_pad_bwd;
 // kernels leaves {start, end} (s_memrealtime, 100 MHz), its hardware id and the survivors it evaluated in a buffer of its own.
 static unsigned long long* g_trace_fwd = nullptr;
 static unsigned long long* g_trace_bwd = nullptr;
+static unsigned long long g_trace_bwd_records = 0;      // 4-word records the backward table holds (a split launch needs 2 x tiles x 4)
 #define BS_STAMP(v) asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) :: "memory")
 #endif
 
@@ -958,46 +959,74 @@ __global__ void __launch_bounds__(256) blend_backward_t_kernel(BlendArgs a, int 
 typedef float v2f __attribute__((ext_vector_type(2)));
 typedef float v3f __attribute__((ext_vector_type(3)));
 typedef float v8f __attribute__((ext_vector_type(8)));
-template <bool POSE_ONLY>
-__global__ void __launch_bounds__(256) blend_backward_s_kernel(BlendArgs a, int ntiles,
-                                                               const float* __restrict__ final_T,
-                                                               const uint32_t* __restrict__ n_contrib,
-                                                               const float* __restrict__ dL_dcolor,
-                                                               const float* __restrict__ dL_ddepth,
-                                                               float* __restrict__ grad_acc) {
-    // per wave: the factor slab [h | w][slot][pixel] and the slots' metadata {cx, cy, index << 6}, every array with the SAME slot
-    // stride so that ONE scalar (slab base + open slot x stride) addresses all three -- 272 bytes, not 256, so that the four rows of
-    // a flush find their metadata words on different LDS banks.  (SQ_LDS_BANK_CONFLICT reads 7.9 M cycles per launch at C5 -- two per
-    // survivor -- with either stride, and with the slot-clearing or the factor store taken out: not isolated, and not worth more.)
-    struct WaveLds { float h[BT_SLOTS][BS_STRIDE / 4]; float pad[(BS_W_OFF - BT_SLOTS * BS_STRIDE) / 4]; float w[BT_SLOTS][BS_STRIDE / 4];
-                     BtMetaRec meta[BT_SLOTS][BS_STRIDE / 16]; };
-    static_assert(sizeof(WaveLds) == BS_META_OFF + BT_SLOTS * BS_STRIDE, "layout");
-    __shared__ __attribute__((aligned(16))) WaveLds s_w[MGS_WG_WAVES];
-    __shared__ __attribute__((aligned(16))) float s_pix[MGS_WG_WAVES][POSE_ONLY ? 1 : 4][16][4];    // [wave][(rgb,) depth][q][4 pixels]
-    MGS_TILE_WAVE(ntiles, tile, wave, ws)
+// ---- the split walk (mgs_debug_set_option("blend_bwd_split")) ----------------------------------------------
+// A walk is sequential in depth only because T is recovered by division from T_final and the "colour behind" B by recursion
+// from the back.  Both can be had from the FRONT as cheaply: T_i is the forward's own product (T <- T (1 - alpha), from 1), and
+// with q_i = sum_ch c_i,ch dL/dC_ch + z_i dL/dD the part of the pixel's loss-weighted colour that lies behind contributor i is
+// S_tot - S_i, S_i = sum_{j <= i} alpha_j T_j q_j, S_tot = sum_ch (C_ch - bg_ch T_final) dL/dC_ch + D dL/dD from the forward's
+// finished images.  T_i B_i = (S_tot - S_i) / (1 - alpha_i), so with U_i = bgT - S_tot + S_i = S_i - (C . dL/dC + D dL/dD)
+//     dL/dalpha_i = T_i q_i + U_i / (1 - alpha_i)
+// (one reciprocal per survivor, as in the back walk; the background term is inside U).  So the list positions [0, m) of a
+// quadrant are walked front to back by one wave (DIR 2) while [m, maxc) are walked back to front by another (DIR 1, the
+// unsplit walk with a bound): up to twice the jobs, each shorter.  Both waves derive m from the same data
+// (bs_split_point), so every list position is walked exactly once.  DIR 0 is the unsplit walk.
+// Measured at C5: the FIRST steps of a list are its dearest -- every pixel is still alive, so the cull keeps
+// the most survivors -- and halving the positions (128 / 256) gives the front wave the longer job: 0.745 against 0.741 ms per
+// step unsplit.  An eighth of the positions (one step of most lists) is the balance: 0.718 against 0.734.
+constexpr int BS_SPLIT_MIN = 4, BS_SPLIT_FRAC = 32;
+struct BsSplit { int min_steps, frac256; };          // shortest list (64-instance steps) that is split; the front's share / 256
+__device__ __forceinline__ uint32_t bs_split_point(uint32_t maxc, BsSplit sp) {
+    const uint32_t steps = (maxc + WAVE - 1) / WAVE;
+    if (steps < 2u || steps < (uint32_t)sp.min_steps) return 0u;
+    const uint32_t f = (maxc * (uint32_t)sp.frac256 / 256u + WAVE / 2) / WAVE;      // the front's share, in whole steps
+    return min(max(f, 1u), steps - 1u) * WAVE;
+}
+struct BsWaveLds { float h[BT_SLOTS][BS_STRIDE / 4]; float pad[(BS_W_OFF - BT_SLOTS * BS_STRIDE) / 4]; float w[BT_SLOTS][BS_STRIDE / 4];
+                   BtMetaRec meta[BT_SLOTS][BS_STRIDE / 16]; };
+static_assert(sizeof(BsWaveLds) == BS_META_OFF + BT_SLOTS * BS_STRIDE, "layout");
+template <bool POSE_ONLY, int DIR>
+__device__ __forceinline__ void bs_walk(const BlendArgs& a, const int tile, const int job, const int wave, BsWaveLds* const s_w_ws, float* const s_pix_ws,
+                                        const float* __restrict__ final_T, const uint32_t* __restrict__ n_contrib,
+                                        const float* __restrict__ dL_dcolor, const float* __restrict__ dL_ddepth,
+                                        const float* __restrict__ out_color, const float* __restrict__ out_depth,
+                                        float* __restrict__ grad_acc, const BsSplit sp) {
+    constexpr bool FRONT = DIR == 2;
     const int lane = threadIdx.x & 63;
     const int tx = tile % a.gx, ty = tile / a.gx;
     const uint2 range = a.ranges[tile];
     if (range.y <= range.x) return;
     const size_t HW = (size_t)a.H * a.W;
-    const float bg0 = a.bg[0], bg1 = a.bg[1], bg2 = a.bg[2];
 
     const int qx0i = tx * TILE + (wave & 1) * SUB, qy0i = ty * TILE + (wave >> 1) * SUB;
     const int pxi = qx0i + (lane & 7), pyi = qy0i + (lane >> 3);
     const bool inside = pxi < a.W && pyi < a.H;
     const size_t pix = (size_t)pyi * a.W + pxi;
     const float pxf = (float)pxi, pyf = (float)pyi;
-    const float T_final = inside ? final_T[pix] : 0.f;
     const uint32_t last = inside ? n_contrib[pix] : 0u;
+    const uint32_t maxc = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max_u32(last));
+    if (maxc == 0) return;
+    // the walk's bounds in list positions: the front wave takes [0, m), the back wave [m, maxc)
+    const uint32_t m = DIR == 0 ? 0u : bs_split_point(maxc, sp);
+    if (FRONT && m == 0) return;
     const float g0 = inside ? dL_dcolor[pix] : 0.f;
     const float g1 = inside ? dL_dcolor[HW + pix] : 0.f;
     const float g2 = inside ? dL_dcolor[2 * HW + pix] : 0.f;
     const float gd = inside ? dL_ddepth[pix] : 0.f;
-    const float bgT = -T_final * (bg0 * g0 + bg1 * g1 + bg2 * g2);
-    float T = T_final, Bk = 0.f;
-    const uint32_t maxc = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max_u32(last));
-    if (maxc == 0) return;
-    const uint32_t end = range.x + maxc;
+    // back walk: T from T_final by division, Bk the colour behind; front walk: T from 1 by the forward's product, Bk holds
+    // U = S_i - (C . dL/dC + D dL/dD) (see above), which has the background term inside
+    float T, Bk, bgT = 0.f;
+    if (FRONT) {
+        const float C0 = inside ? out_color[pix] : 0.f, C1 = inside ? out_color[HW + pix] : 0.f;
+        const float C2 = inside ? out_color[2 * HW + pix] : 0.f, Dz = inside ? out_depth[pix] : 0.f;
+        T = 1.f;
+        Bk = -(C0 * g0 + C1 * g1 + C2 * g2 + Dz * gd);
+    } else {
+        const float T_final = inside ? final_T[pix] : 0.f;
+        bgT = -T_final * (a.bg[0] * g0 + a.bg[1] * g1 + a.bg[2] * g2);
+        T = T_final, Bk = 0.f;
+    }
+    const uint32_t end = range.x + (FRONT ? m : maxc);
+    const int b_lo = (int)(m / WAVE);                               // back walk: its frontmost step; front walk: one past its last
 #ifdef BS_TRACE
     unsigned long long tr0;
     uint32_t tr_n = 0;
@@ -1012,19 +1041,19 @@ __global__ void __launch_bounds__(256) blend_backward_s_kernel(BlendArgs a, int 
             const bool in_i = (fxi + i) < a.W && fyi < a.H;
             const size_t px_i = (size_t)fyi * a.W + fxi + i;
             if (!POSE_ONLY) {
-                s_pix[ws][0][q][i] = in_i ? dL_dcolor[px_i] : 0.f;
-                s_pix[ws][1][q][i] = in_i ? dL_dcolor[HW + px_i] : 0.f;
-                s_pix[ws][2][q][i] = in_i ? dL_dcolor[2 * HW + px_i] : 0.f;
+                s_pix_ws[(0 * 16 + q) * 4 + i] = in_i ? dL_dcolor[px_i] : 0.f;
+                s_pix_ws[(1 * 16 + q) * 4 + i] = in_i ? dL_dcolor[HW + px_i] : 0.f;
+                s_pix_ws[(2 * 16 + q) * 4 + i] = in_i ? dL_dcolor[2 * HW + px_i] : 0.f;
             }
-            s_pix[ws][POSE_ONLY ? 0 : 3][q][i] = in_i ? dL_ddepth[px_i] : 0.f;
+            s_pix_ws[((POSE_ONLY ? 0 : 3) * 16 + q) * 4 + i] = in_i ? dL_ddepth[px_i] : 0.f;
         }
     }
     const int slot = POSE_ONLY ? bt_slot6(q) : bt_slot10(q);
     const uint32_t slot_bytes = slot < 0 ? 0u : (uint32_t)slot * 4u;
     const unsigned long long m_out = __builtin_amdgcn_ballot_w64(slot >= 0);
     const unsigned long long m_q0 = __builtin_amdgcn_ballot_w64((q & 3) == 0), m_q1 = __builtin_amdgcn_ballot_w64((q & 3) == 1);
-    const BtLane bl{&s_w[ws].h[0][0], &s_pix[ws][0][0][0], &s_w[ws].meta[0][0], lane, 0.f, 0.f, slot_bytes, m_out, m_q0, m_q1, grad_acc, qx0i, qy0i};
-    const uint32_t wbase = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)&s_w[ws]);   // LDS address (SGPR)
+    const BtLane bl{&s_w_ws->h[0][0], s_pix_ws, &s_w_ws->meta[0][0], lane, 0.f, 0.f, slot_bytes, m_out, m_q0, m_q1, grad_acc, qx0i, qy0i};
+    const uint32_t wbase = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)s_w_ws);   // LDS address (SGPR)
     const const_float_p recs = MGS_CONST(reinterpret_cast<const float*>(a.rec));
     uint32_t koff = 0;              // open batch: survivors x 272 = byte offset of the open slot in the slab and in the metadata (SGPR)
     float zero = 0.f;
@@ -1032,21 +1061,22 @@ __global__ void __launch_bounds__(256) blend_backward_s_kernel(BlendArgs a, int 
 
     uint32_t gid_n = 0;
     float4 box_n = make_float4(0.f, 0.f, -1.f, -1.f), ell_n = make_float4(0.f, 0.f, 0.f, 0.f);
-    auto prefetch = [&](int b) {                    // lane l takes instance 63 - l of step b
+    auto prefetch = [&](int b) {                    // lane l takes instance 63 - l of step b (front walk: instance l)
         gid_n = 0;
         box_n = make_float4(0.f, 0.f, -1.f, -1.f);
-        const uint32_t i = range.x + (uint32_t)b * WAVE + (uint32_t)(63 - lane);
-        if (b >= 0 && i < end) {
+        const uint32_t i = range.x + (uint32_t)b * WAVE + (uint32_t)(FRONT ? lane : 63 - lane);
+        if (b >= (FRONT ? 0 : b_lo) && i < end) {
             gid_n = a.point_list[i];
             box_n = a.rec[(size_t)gid_n * 4];
             ell_n = a.rec[(size_t)gid_n * 4 + 3];
         }
     };
-    prefetch((int)((maxc - 1) / WAVE));
-    for (int b = (int)((maxc - 1) / WAVE); b >= 0; --b) {
+    const int b_first = FRONT ? 0 : (int)((maxc - 1) / WAVE), b_step = FRONT ? 1 : -1;
+    prefetch(b_first);
+    for (int b = b_first; FRONT ? b < b_lo : b >= b_lo; b += b_step) {
         const float4 c = box_n, el = ell_n;
         v3f meta = {c.x, c.y, __uint_as_float(gid_n << 6)};        // what the lane notes for the flush if its instance survives
-        prefetch(b - 1);
+        prefetch(b + b_step);
         const unsigned long long alive = __builtin_amdgcn_ballot_w64(last >= (uint32_t)b * WAVE + 1u);
         // (the quadrant origin as floats is re-derived per step from the scalar integers: kept across the walk the two floats
         //  sit in vector registers, and the kernel has exactly 64)
@@ -1055,7 +1085,8 @@ __global__ void __launch_bounds__(256) blend_backward_s_kernel(BlendArgs a, int 
         unsigned long long mask = __builtin_amdgcn_ballot_w64(quadrant_hit(c, el, (float)qxs, (float)qys, alive));
         // lane j holds the instance with list position k_first + 63 - j: a pixel takes it only if that is <= last,
         // i.e. j >= 63 + k_first - last
-        const int thr = 63 + (int)((uint32_t)b * WAVE + 1u) - (int)last;
+        // (front walk: lane j holds position k_first + j, taken if j <= last - k_first; the lowest set bit is the frontmost)
+        const int thr = FRONT ? (int)last - (int)((uint32_t)b * WAVE + 1u) : 63 + (int)((uint32_t)b * WAVE + 1u) - (int)last;
         // One survivor: pop the next set bit (the lane), fetch its record with two scalar loads off the lane's index << 6.
         // The fetch of survivor t + 1 is ISSUED before survivor t is evaluated and only waited for one trip later (two
         // register sets, the loop unrolled by two: no copies).  A scalar load that misses the 16 KB scalar cache takes ~240 ns
@@ -1073,6 +1104,51 @@ __global__ void __launch_bounds__(256) blend_backward_s_kernel(BlendArgs a, int 
         auto evaluate = [&](const v2f r0, const v8f r1, const int j) {
                 float dx, dy, t1, t2, G, al, inv, qq;
                 uint32_t adv, sa, tmp;
+                if (FRONT)
+                asm volatile(
+                    "v_sub_f32_e32 %[dx], %[px], %[pxf]\n\t"
+                    "v_sub_f32_e32 %[dy], %[py], %[pyf]\n\t"
+                    "v_mul_f32_e32 %[t1], %[cb], %[dy]\n\t"
+                    "v_mul_f32_e32 %[t2], %[cc], %[dy]\n\t"
+                    "v_fmac_f32_e32 %[t1], %[ca], %[dx]\n\t"
+                    "v_mul_f32_e32 %[t2], %[dy], %[t2]\n\t"
+                    "v_fmac_f32_e32 %[t2], %[dx], %[t1]\n\t"               // power (log2 of the falloff), as the other kernels form it
+                    "v_exp_f32_e32 %[G], %[t2]\n\t"
+                    "s_add_u32 %[tmp], %[wbase], %[koff]\n\t"               // the open slot
+                    "v_lshl_add_u32 %[sa], %[lane], 2, %[tmp]\n\t"           // this lane's word of it
+                    "ds_write2st64_b32 %[sa], %[zero], %[zero] offset1:5\n\t"   // the slot's h and w of every pixel <- 0 (full EXEC)
+                    "v_cmpx_le_i32_e32 vcc, %[j], %[thr]\n\t"              // EXEC: pixels whose last contributor is not in front of j
+                    "v_cmpx_nlt_f32_e32 vcc, 0, %[t2]\n\t"                 //       and power <= 0
+                    "v_mul_f32_e32 %[al], %[op], %[G]\n\t"
+                    "v_min_f32_e32 %[al], 0x3f7d70a4, %[al]\n\t"           // min(0.99, opacity G)
+                    "v_cmpx_ngt_f32_e32 vcc, %[amin], %[al]\n\t"           //       and alpha >= 1/255
+                    "v_sub_f32_e32 %[t1], 1.0, %[al]\n\t"
+                    "v_rcp_f32_e32 %[inv], %[t1]\n\t"
+                    "v_mul_f32_e32 %[qq], %[cr], %[g0]\n\t"
+                    "v_fmac_f32_e32 %[qq], %[cg], %[g1]\n\t"
+                    "v_fmac_f32_e32 %[qq], %[cb2], %[g2]\n\t"
+                    "v_fmac_f32_e32 %[qq], %[cz], %[gd]\n\t"
+                    "v_mul_f32_e32 %[dy], %[al], %[T]\n\t"                 // w = alpha T (T: transmittance in front of j)
+                    "v_mul_f32_e32 %[dx], %[T], %[qq]\n\t"
+                    "v_fmac_f32_e32 %[Bk], %[dy], %[qq]\n\t"               // U <- U + w q: minus what lies behind j (background included)
+                    "v_fmac_f32_e32 %[dx], %[Bk], %[inv]\n\t"              // dL/dalpha = T q + U / (1 - alpha)
+                    "v_mul_f32_e32 %[dx], %[G], %[dx]\n\t"                 // h = G dL/dalpha
+                    "v_mul_f32_e32 %[T], %[T], %[t1]\n\t"                  // T <- T (1 - alpha), as the forward forms it
+                    "ds_write2st64_b32 %[sa], %[dx], %[dy] offset1:5\n\t"  // (active pixels only)
+                    "s_cmp_lg_u64 exec, 0\n\t"
+                    "s_cselect_b32 %[adv], 272, 0\n\t"                     // the slot is taken only if some pixel was active
+                    "s_lshl_b64 exec, 1, %[j]\n\t"                         // lane j: the slot's metadata {centre, index << 6}
+                    "v_mov_b32_e32 %[sa], %[tmp]\n\t"
+                    "ds_write_b96 %[sa], %[meta] offset:2368\n\t"
+                    "s_mov_b64 exec, -1\n\t"
+                    : [dx] "=&v"(dx), [dy] "=&v"(dy), [t1] "=&v"(t1), [t2] "=&v"(t2), [G] "=&v"(G), [al] "=&v"(al), [inv] "=&v"(inv),
+                      [qq] "=&v"(qq), [sa] "=&v"(sa), [T] "+v"(T), [Bk] "+v"(Bk), [adv] "=&s"(adv), [tmp] "=&s"(tmp)
+                    : [px] "s"(r0[0]), [py] "s"(r0[1]), [ca] "s"(r1[0]), [cb] "s"(r1[1]), [cc] "s"(r1[2]), [op] "s"(r1[3]),
+                      [cr] "s"(r1[4]), [cg] "s"(r1[5]), [cb2] "s"(r1[6]), [cz] "s"(r1[7]), [pxf] "v"(pxf), [pyf] "v"(pyf), [thr] "v"(thr),
+                      [j] "s"(j), [g0] "v"(g0), [g1] "v"(g1), [g2] "v"(g2), [gd] "v"(gd), [lane] "v"(lane), [zero] "v"(zero),
+                      [koff] "s"(koff), [wbase] "s"(wbase), [meta] "v"(meta), [amin] "s"(1.0f / 255.0f)
+                    : "vcc", "scc", "memory");
+                else
                 asm volatile(
                     "v_sub_f32_e32 %[dx], %[px], %[pxf]\n\t"
                     "v_sub_f32_e32 %[dy], %[py], %[pyf]\n\t"
@@ -1153,11 +1229,48 @@ __global__ void __launch_bounds__(256) blend_backward_s_kernel(BlendArgs a, int 
         BS_STAMP(tr1);
         const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | 4), xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20);
         if (lane == 0) {
-            unsigned long long* o = a.trace + ((size_t)tile * 4 + wave) * 4;
+            unsigned long long* o = a.trace + ((size_t)job * 4 + wave) * 4;       // (front walks: a second table behind the first)
             o[0] = tr0; o[1] = tr1; o[2] = (unsigned long long)hw | ((unsigned long long)xcc << 32); o[3] = tr_n;
         }
     }
 #endif
+}
+
+// SPLIT: a grid of 2 x ntiles workgroups, every quadrant's list walked from both ends (bs_walk).  `adjacent` != 0: workgroups
+// 2 t and 2 t + 1 are the two halves of tile t; 0: all back halves, then all front halves.
+template <bool POSE_ONLY, bool SPLIT>
+__global__ void __launch_bounds__(256) blend_backward_s_kernel(BlendArgs a, int ntiles,
+                                                               const float* __restrict__ final_T,
+                                                               const uint32_t* __restrict__ n_contrib,
+                                                               const float* __restrict__ dL_dcolor,
+                                                               const float* __restrict__ dL_ddepth,
+                                                               const float* __restrict__ out_color,
+                                                               const float* __restrict__ out_depth,
+                                                               float* __restrict__ grad_acc, BsSplit sp, int adjacent) {
+    // per wave: the factor slab [h | w][slot][pixel] and the slots' metadata {cx, cy, index << 6}, every array with the SAME slot
+    // stride so that ONE scalar (slab base + open slot x stride) addresses all three -- 272 bytes, not 256, so that the four rows of
+    // a flush find their metadata words on different LDS banks.  (SQ_LDS_BANK_CONFLICT reads 7.9 M cycles per launch at C5 -- two per
+    // survivor -- with either stride, and with the slot-clearing or the factor store taken out: not isolated, and not worth more.)
+    __shared__ __attribute__((aligned(16))) BsWaveLds s_w[MGS_WG_WAVES];
+    __shared__ __attribute__((aligned(16))) float s_pix[MGS_WG_WAVES][POSE_ONLY ? 1 : 4][16][4];    // [wave][(rgb,) depth][q][4 pixels]
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (!SPLIT) {
+        const int tile = (int)blockIdx.x;
+        if (tile >= ntiles) return;
+        bs_walk<POSE_ONLY, 0>(a, tile, tile, wave, &s_w[wave], &s_pix[wave][0][0][0], final_T, n_contrib, dL_dcolor, dL_ddepth,
+                              out_color, out_depth, grad_acc, sp);
+    } else {
+        const int blk = (int)blockIdx.x;
+        if (blk >= 2 * ntiles) return;
+        const bool front = adjacent ? (blk & 1) != 0 : blk >= ntiles;
+        const int tile = adjacent ? blk >> 1 : (front ? blk - ntiles : blk);
+        if (front)
+            bs_walk<POSE_ONLY, 2>(a, tile, tile + ntiles, wave, &s_w[wave], &s_pix[wave][0][0][0], final_T, n_contrib, dL_dcolor,
+                                  dL_ddepth, out_color, out_depth, grad_acc, sp);
+        else
+            bs_walk<POSE_ONLY, 1>(a, tile, tile, wave, &s_w[wave], &s_pix[wave][0][0][0], final_T, n_contrib, dL_dcolor, dL_ddepth,
+                                  out_color, out_depth, grad_acc, sp);
+    }
 }
 
 // ---- diagnostic: what the backward walk does, counted (not on the hot path; mgs_debug_blend_stats) --------------
@@ -1336,10 +1449,24 @@ int launch_blend_backward_stats(const mgs_camera& cam, const GeometryState& g, c
 // (The wave-per-tile and half-tile-per-wave variants of round 1 lost at every size and are gone; DESIGN.md section 4
 //  keeps their measurements.)
 int g_opt_blend_lds_pad_fwd = 0, g_opt_blend_lds_pad_bwd = 0;      // measurement knobs: dynamic LDS bytes the kernels never touch (fewer workgroups per CU)
+int g_opt_blend_bwd_split = -1;         // mgs_debug_set_option("blend_bwd_split", 1 | 2 | 0 | -1): every quadrant's list walked from both ends by two waves (1: all back halves, then all front halves; 2: the halves of a tile in adjacent workgroups), 0 = unsplit, -1 = the default (see launch_blend_backward); needs blend_bwd_transposed = 2 and the forward's colour and depth images
+int g_opt_blend_bwd_split_min = BS_SPLIT_MIN, g_opt_blend_bwd_split_frac = BS_SPLIT_FRAC;    // shortest list that is split (64-instance steps); the front walk's share of it / 256
 int g_opt_blend_bwd_transposed = 2;     // mgs_debug_set_option("blend_bwd_transposed", 0 | 1 | 2): 2 = scalar side trimmed + EXEC (round 5), 1 = scalar-fetch transposed (round 3), 0 = the per-survivor wave reduction
+// The default of blend_bwd_split, from measurements on the MI355X: the split walk is the faster one at C5,
+// 200 k / 1200x680 and 100 k / VGA, ten-sum and pose-only alike (-3 ... -12 % of the kernel); at 40 k / VGA, where hardly a list
+// reaches the minimum, the idle front workgroups cost 0.2 of 28 us.  Instances per tile there: 646, 164, 202 and 81: split from 128.  The two halves of a tile
+// in adjacent workgroups (2) lose to "all back parts, then all front parts" (1) by 10 %.
+// `num_rendered` is what the caller hands to mgs_backward: the exact instance count, or in capacity mode the CAPACITY (the caller's
+// hint x headroom, 1.2 - 1.5 x the count), so the line moves with the headroom.  Nothing measured hangs on where between 81 and 164
+// it lies: at 81 the two launches take the same time to 0.1 us, and a split launch of lists that are all short only idles.
+int g_dbg_last_bwd_split = -1;          // mgs_debug_last_backward_split(): 1 / 0 = the last s-kernel launch was split / unsplit
+static int bs_split_default(int ntiles, uint64_t num_rendered) {
+    return num_rendered >= (uint64_t)ntiles * 128u ? 1 : 0;
+}
+bool g_opt_blend_bwd_transposed_set = false;    // blend_bwd_transposed was set by hand: 2 then names the UNSPLIT s-kernel (the A/B partner of 1 and 0)
 int launch_blend_backward(const mgs_camera& cam, const GeometryState& g, const BinningState& b,
-                          const ImageState& img, const float* dL_dcolor, const float* dL_ddepth, float* grad_acc,
-                          bool pose_only, hipStream_t s) {
+                          const ImageState& img, const float* dL_dcolor, const float* dL_ddepth, const float* out_color,
+                          const float* out_depth, float* grad_acc, bool pose_only, uint64_t num_rendered, hipStream_t s) {
     BlendArgs a = make_args(cam, g, b, img);
 #ifdef BS_TRACE
     a.trace = g_trace_bwd;
@@ -1347,13 +1474,21 @@ int launch_blend_backward(const mgs_camera& cam, const GeometryState& g, const B
     const int ntiles = a.gx * tiles_y(a.H);
     if (ntiles == 0) return 0;
     if (g_opt_blend_bwd_transposed == 2) {
-        const dim3 grid(ntiles), block(256);
-        if (pose_only)
-            hipLaunchKernelGGL((blend_backward_s_kernel<true>), grid, block, (size_t)g_opt_blend_lds_pad_bwd, s, a, ntiles, img.final_T,
-                               img.n_contrib, dL_dcolor, dL_ddepth, grad_acc);
-        else
-            hipLaunchKernelGGL((blend_backward_s_kernel<false>), grid, block, (size_t)g_opt_blend_lds_pad_bwd, s, a, ntiles, img.final_T,
-                               img.n_contrib, dL_dcolor, dL_ddepth, grad_acc);
+        // the split walk needs the forward's finished colour and depth images: a caller that has none gets the unsplit walk
+        const int opt = g_opt_blend_bwd_split >= 0 ? g_opt_blend_bwd_split : g_opt_blend_bwd_transposed_set ? 0 : bs_split_default(ntiles, num_rendered);
+        bool split = opt != 0 && out_color && out_depth;
+#ifdef BS_TRACE
+        if (a.trace && g_trace_bwd_records < 8ull * (unsigned long long)ntiles) split = false;
+#endif
+        g_dbg_last_bwd_split = split ? 1 : 0;
+        const BsSplit sp{max(g_opt_blend_bwd_split_min, 2), min(max(g_opt_blend_bwd_split_frac, 1), 255)};
+        const dim3 grid(split ? 2 * ntiles : ntiles), block(256);
+        const size_t pad = (size_t)g_opt_blend_lds_pad_bwd;
+#define BS_LAUNCH(P_, S_) hipLaunchKernelGGL((blend_backward_s_kernel<P_, S_>), grid, block, pad, s, a, ntiles, img.final_T, img.n_contrib, \
+                                             dL_dcolor, dL_ddepth, out_color, out_depth, grad_acc, sp, (int)(opt == 2))
+        if (pose_only) { if (split) BS_LAUNCH(true, true); else BS_LAUNCH(true, false); }
+        else { if (split) BS_LAUNCH(false, true); else BS_LAUNCH(false, false); }
+#undef BS_LAUNCH
     } else if (g_opt_blend_bwd_transposed != 0) {
         if (pose_only)
             hipLaunchKernelGGL((blend_backward_t_kernel<true>), dim3(ntiles), dim3(256), 0, s, a, ntiles, img.final_T,
@@ -1391,9 +1526,12 @@ int launch_valu_ceiling(float* out, int iters, hipStream_t s) {
 }  // namespace mgs
 
 #ifdef BS_TRACE
-extern "C" int mgs_trace_set_blend_buffers(void* fwd, void* bwd) {      // diagnostic builds only: device buffers of 4 x tiles x 4 uint64, or NULL
+// diagnostic builds only: device buffers of 4 x tiles records of 4 uint64, or NULL.  `bwd_records`: records in `bwd`; a split launch fills
+// 2 x 4 x tiles (front walks in the second half) and is NOT made while the table is shorter than that (the unsplit walk is traced instead).
+extern "C" int mgs_trace_set_blend_buffers(void* fwd, void* bwd, unsigned long long bwd_records) {
     mgs::g_trace_fwd = (unsigned long long*)fwd;
     mgs::g_trace_bwd = (unsigned long long*)bwd;
+    mgs::g_trace_bwd_records = bwd ? bwd_records : 0;
     return 0;
 }
 #endif

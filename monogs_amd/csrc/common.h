@@ -275,7 +275,9 @@ TileSortArgs tile_sort_args(const mgs_camera& cam, const GeometryState& g, const
 int launch_tile_depth_sort(const mgs_camera& cam, const TileSortArgs& ts, const ImageState& img, const uint32_t* sort_err,
                            hipStream_t s);
 int set_radix_spin_limit(uint32_t limit);
-extern int g_opt_radix_ballot_rank, g_opt_radix_scanned, g_opt_radix_xcd_band, g_opt_radix_tile_items, g_opt_knn_grid_min, g_opt_scan_small, g_opt_dup_slot_major, g_opt_blend_bwd_transposed, g_opt_blend_lds_pad_fwd, g_opt_blend_lds_pad_bwd, g_opt_depth_small;      // test knobs (mgs_debug_set_option)
+extern bool g_opt_blend_bwd_transposed_set;
+extern int g_dbg_last_bwd_split;
+extern int g_opt_radix_ballot_rank, g_opt_radix_scanned, g_opt_radix_xcd_band, g_opt_radix_tile_items, g_opt_knn_grid_min, g_opt_scan_small, g_opt_dup_slot_major, g_opt_blend_bwd_transposed, g_opt_blend_bwd_split, g_opt_blend_bwd_split_min, g_opt_blend_bwd_split_frac, g_opt_blend_lds_pad_fwd, g_opt_blend_lds_pad_bwd, g_opt_depth_small;      // test knobs (mgs_debug_set_option)
 // `sort_err`: the tile sort's error words (NULL: nothing was sorted); a raised word empties every tile and sets
 // MGS_STATUS_TILE_SORT_TIMEOUT in *status (what ranges_kernel did until round 4).  `tile_sort` (per-tile depth order, or
 // NULL): every workgroup first sorts its tile's list (tile_sort.h)
@@ -284,8 +286,8 @@ int launch_blend_forward(const mgs_camera& cam, const GeometryState& g, const Bi
                          int32_t* n_touched, const uint32_t* sort_err, uint32_t* status, const TileSortArgs* tile_sort,
                          hipStream_t s);
 int launch_blend_backward(const mgs_camera& cam, const GeometryState& g, const BinningState& b,
-                          const ImageState& img, const float* dL_dcolor, const float* dL_ddepth,
-                          float* grad_acc, bool pose_only, hipStream_t s);
+                          const ImageState& img, const float* dL_dcolor, const float* dL_ddepth, const float* out_color,
+                          const float* out_depth, float* grad_acc, bool pose_only, uint64_t num_rendered, hipStream_t s);
 int launch_blend_backward_stats(const mgs_camera& cam, const GeometryState& g, const BinningState& b,
                                 const ImageState& img, unsigned long long* stats, hipStream_t s);
 int launch_valu_ceiling(float* out, int iters, hipStream_t s);

@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import weakref
 from typing import NamedTuple, Optional
 
 import torch
@@ -283,6 +284,11 @@ class _RasterizeGaussians(torch.autograd.Function):
             ctx.scratch_used = False
             out5 = torch.empty(5, H, W, dtype=torch.float32, device=dev)
             color, depth, opacity = out5[0:3], out5[3:4], out5[4:5]
+            # The blend backward walks every pixel list from both ends when it is given the finished colour and depth images.
+            # They are outputs: held by a weak reference (a strong one would be a cycle through grad_fn, and save_for_backward
+            # would turn a caller's in-place edit of an output into an error).  A caller that dropped or edited them gets the
+            # walk from the back only -- same gradients to rounding.
+            ctx.out_ref = weakref.ref(out5) if want_bwd else None
             status = torch.empty(1, dtype=torch.int32, device=dev) if P > 0 else None      # this forward's MGS_STATUS_* word
             key = (P, W, H)
             capturing = torch.cuda.is_current_stream_capturing()
@@ -353,6 +359,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.save_for_backward(means3D, sh_ if sh_ is not None else dummy, col_ if col_ is not None else dummy,
                               opac_, sc_ if sc_ is not None else dummy, rot_ if rot_ is not None else dummy,
                               cov_ if cov_ is not None else dummy, radii, arena, binning)
+        ctx.out_version = out5._version
         ctx.mark_non_differentiable(radii, n_touched)
         ctx.set_materialize_grads(False)     # unused output gradients arrive as None instead of three zero-fill kernels
         return color, radii, depth, opacity, n_touched
@@ -401,12 +408,17 @@ class _RasterizeGaussians(torch.autograd.Function):
                 d_tau = torch.empty(6, **f32) if want_tau else None
             timing = _lib.MgsTiming() if _timing_sink is not None else None
             tref = C.byref(timing) if timing is not None else None
+            out5 = ctx.out_ref() if ctx.out_ref is not None else None
+            if out5 is not None and out5._version != ctx.out_version:
+                out5 = None
             _lib.check(lib.mgs_backward(
                 C.byref(cam), P, ctx.num_rendered,
                 _ptr(means3D), _ptr(sh_) if has_sh else None, _ptr(col_) if has_col else None, _ptr(opac_),
                 _ptr(sc_) if has_sr else None, _ptr(rot_) if has_sr else None, _ptr(cov_) if has_cov else None,
                 radii.data_ptr(), geom_p, binning.data_ptr(), img_p,
                 g_color.data_ptr(), g_depth.data_ptr(),
+                out5.data_ptr() if out5 is not None else None,                 # colour [3,H,W], depth [1,H,W] behind it
+                out5.data_ptr() + 12 * H * W if out5 is not None else None,
                 _ptr(d_means2D), _ptr(d_col), _ptr(d_opac), _ptr(d_means3D), _ptr(d_cov), _ptr(d_sh),
                 _ptr(d_scales), _ptr(d_rot), _ptr(d_tau), scratch.data_ptr(), 1 if prepared else 0, tref, _stream()),
                 "mgs_backward")

@@ -2,7 +2,10 @@
 """How far the HIP gradients are from a float64 evaluation of the same function, next to the float32 oracle's own distance
 (BASELINE config 2 with the mapping loss's upstream gradients: tests/test_gpu_parity.py::test_c2_100k_mapping_loss_gradients).
 The float64 / float32 oracle results are cached in /tmp so that kernel variants (MGS_LIB_PATH, MGS_DEBUG_OPTIONS) can be
-compared in one GPU call:   python tools/grad_accuracy.py [label]"""
+compared in one GPU call:   python tools/grad_accuracy.py [label]
+ACC_P / ACC_RADIUS: another map size / mean splat radius in pixels (e.g. 600000 / 3: the per-tile depth-sort path, above 512 k
+Gaussians); ACC_REPEAT: HIP runs per upstream gradient (the float atomics' order differs from run to run: the spread between
+the rows of one label is what a difference between labels has to be read against)."""
 import os
 import sys
 import types
@@ -21,7 +24,9 @@ from test_gpu_parity import _c2_frame, _inputs
 DEV = "cuda:0"
 label = sys.argv[1] if len(sys.argv) > 1 else "default"
 P = int(os.environ.get("ACC_P", "100000"))
-sc = make_scene(P, "fr3_office", seed=1)
+RADIUS = float(os.environ.get("ACC_RADIUS", "6"))
+REPEAT = int(os.environ.get("ACC_REPEAT", "1"))
+sc = make_scene(P, "fr3_office", seed=1, mean_radius_px=RADIUS)
 inp = _inputs(sc)
 st = scene_settings(sc, GaussianRasterizationSettings, device=DEV)
 
@@ -44,7 +49,7 @@ def hip(g_color=None, g_depth=None, vp=None):
     return out, g
 
 
-cache = f"/tmp/grad_accuracy_{P}.pt"
+cache = f"/tmp/grad_accuracy_{P}_{RADIUS:g}.pt"
 if os.path.exists(cache):
     c = torch.load(cache)
 else:
@@ -60,13 +65,14 @@ else:
         c[name + "32"] = rasterize_autograd(inp, ost, a, b, dtype=torch.float32)[1]
     torch.save(c, cache)
 for name, (a, b) in (("loss", (c["gc"], c["gd"])), ("noise", (sc.grad_color, sc.grad_depth))):
-    _, g = hip(a, b)
-    row = []
-    for k in ("means3D", "scales", "rotations", "opacities", "colors_precomp", "means2D", "theta", "rho"):
-        ref = c[name + "64"][k].double()
-        e = lambda x: ((x.reshape(ref.shape).double() - ref).norm() / ref.norm()).item()  # noqa: E731
-        row.append(f"{k} {e(g[k]):.1e}/{e(c[name + '32'][k]):.1e}")
-    print(f"[{label}] upstream = {name:5s} (HIP / float32 oracle, relative L2 vs float64): " + "  ".join(row), flush=True)
+    for _ in range(REPEAT):
+        _, g = hip(a, b)
+        row = []
+        for k in ("means3D", "scales", "rotations", "opacities", "colors_precomp", "means2D", "theta", "rho"):
+            ref = c[name + "64"][k].double()
+            e = lambda x: ((x.reshape(ref.shape).double() - ref).norm() / ref.norm()).item()  # noqa: E731
+            row.append(f"{k} {e(g[k]):.3e}/{e(c[name + '32'][k]):.3e}")
+        print(f"[{label}] upstream = {name:5s} (HIP / float32 oracle, relative L2 vs float64): " + "  ".join(row), flush=True)
 
 # ---- the fused loss's upstream gradients against the PyTorch mirror's, on the same images
 out, _ = hip()

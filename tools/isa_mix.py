@@ -4,7 +4,7 @@
     python tools/isa_mix.py [profiles/isa_mix.json]
 
 Compiles monogs_amd/csrc/blend.hip to gfx950 assembly (hipcc -S, the flags of the Makefile; no GPU needed) and counts, for
-``blend_backward_s_kernel<false>`` (and ``<true>``, the pose-only variant; ``blend_backward_t_kernel<false>``, round 3's, for comparison):
+``blend_backward_s_kernel<false>`` (the unsplit instantiation ``<false, false>``; and ``<true>``, the pose-only variant; ``blend_backward_t_kernel<false>``, round 3's, for comparison):
 
   * per SURVIVOR: the body of the inner (depth-2) loop without the batch flush -- fetch, alpha, per-pixel gradient factors,
     the two LDS stores;
@@ -138,8 +138,8 @@ def main():
         text = open(asm).read()
     res = {"csrc_sha256": csrc_hash(), "batch_size": 4,
            "source": "hipcc -S of monogs_amd/csrc/blend.hip, inner loop of blend_backward_s_kernel, and of its round-3 A/B partner blend_backward_t_kernel (tools/isa_mix.py)"}
-    for tag, prefix in (("blend_backward_s_kernel<false>", "_ZN3mgs23blend_backward_s_kernelILb0EE"),
-                        ("blend_backward_s_kernel<true>", "_ZN3mgs23blend_backward_s_kernelILb1EE"),
+    for tag, prefix in (("blend_backward_s_kernel<false>", "_ZN3mgs23blend_backward_s_kernelILb0ELb0EE"),
+                        ("blend_backward_s_kernel<true>", "_ZN3mgs23blend_backward_s_kernelILb1ELb0EE"),
                         ("blend_backward_t_kernel<false>", "_ZN3mgs23blend_backward_t_kernelILb0EE")):
         surv, flush, copies = analyse(text, prefix)
         res[tag] = {"per_survivor": surv, "per_batch": flush, "survivors_per_loop_trip": copies}

@@ -8,6 +8,8 @@ lifetimes of the four waves of a workgroup differ, how evenly the work (survivor
 span is ramp-up and tail -- the 52 us (backward) / 28 us (forward) that tools/tail_probe.py finds independent of the image size.
 On the per-tile path (C5) the forward's workgroup sorts its tile's list before its waves walk it: a forward wave's start stamp is
 taken before that sort, so its lifetime includes it.
+The backward's table has room for two waves per quadrant: a split launch (blend_bwd_split, e.g. MGS_DEBUG_OPTIONS=
+"blend_bwd_split=1") fills the second half with its front walks, and their lifetimes are printed next to the back walks'.
 """
 import ctypes as C
 import json
@@ -85,20 +87,28 @@ def run(P, intr):
     r = GaussianRasterizer(st)
     tiles = ((st.image_width + 15) // 16) * ((st.image_height + 15) // 16)
     tf = torch.zeros(tiles * 16, dtype=torch.int64, device=dev)
-    tb = torch.zeros(tiles * 16, dtype=torch.int64, device=dev)
+    tb = torch.zeros(2 * tiles * 16, dtype=torch.int64, device=dev)      # [back or whole walks | front walks of a split launch]
     for i in range(6):
         for p in (xyz, rgb, opac, scaling, rot):
             p.grad = None
         if i == 5:
-            lib.mgs_trace_set_blend_buffers(C.c_void_p(tf.data_ptr()), C.c_void_p(tb.data_ptr()))
+            lib.mgs_trace_set_blend_buffers(C.c_void_p(tf.data_ptr()), C.c_void_p(tb.data_ptr()), C.c_uint64(tb.numel() // 4))
         m2 = torch.zeros_like(xyz, requires_grad=True)
         out = r(means3D=xyz, means2D=m2, opacities=opac, colors_precomp=rgb, scales=scaling, rotations=rot)
         torch.autograd.backward([out[0], out[2]], [gc, gd])
     torch.cuda.synchronize()
-    lib.mgs_trace_set_blend_buffers(None, None)
+    lib.mgs_trace_set_blend_buffers(None, None, C.c_uint64(0))
     print(f"# {P} Gaussians, {st.image_width}x{st.image_height}, {tiles} tiles")
     analyse("blend_forward", tf.cpu().numpy().astype(np.uint64))
-    analyse("blend_backward", tb.cpu().numpy().astype(np.uint64))
+    tb = tb.cpu().numpy().astype(np.uint64).reshape(2, -1, 4)
+    analyse("blend_backward", tb)
+    if (tb[1, :, 1] > 0).any():
+        for name, part in (("back walks", tb[0]), ("front walks", tb[1])):
+            ok = part[:, 1] > 0
+            life = (part[ok, 1].astype(np.float64) - part[ok, 0].astype(np.float64)) * 0.01
+            print(json.dumps({"kernel": "blend_backward, " + name, "waves": int(ok.sum()), "survivors": int(part[ok, 3].sum()),
+                              "wave_life_us": {k: round(float(np.percentile(life, p)), 1)
+                                               for k, p in (("p10", 10), ("p50", 50), ("p90", 90), ("max", 100))}}), flush=True)
 
 
 if __name__ == "__main__":
