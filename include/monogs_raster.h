@@ -1,6 +1,7 @@
 /* monogs_raster.h -- C ABI of libmonogs_raster.so (MI355X / gfx950 only).
  *
- * Drop-in boundary for the two native operators MonoGS calls:
+ * Drop-in boundary for the native operators MonoGS calls (the third, fused_ssim -- imported at
+ * /root/reference/gaussian_splatting/utils/loss_utils.py:19 -- is described at mgs_ssim_forward below):
  *
  *   diff_gaussian_rasterization   imported at /root/reference/gaussian_splatting/gaussian_renderer/__init__.py:13-16,
  *                                 settings built at :70-84, called at :130-156
@@ -38,7 +39,7 @@
 extern "C" {
 #endif
 
-#define MGS_ABI_VERSION 11
+#define MGS_ABI_VERSION 12
 #define MGS_TILE 16 /* tile edge in pixels; ranges are per 16x16 tile */
 
 /* GaussianRasterizationSettings, minus `prefiltered` / `debug` which are call flags
@@ -333,6 +334,39 @@ int mgs_loss_grads(int32_t width, int32_t height, int32_t mode, int32_t init, fl
                    const float* gt_depth, const uint8_t* mask, const uint8_t* grad_mask,
                    const float* exposure_a, const float* exposure_b, float* scratch, float* d_render, float* d_depth,
                    void* stream);
+
+/* ---- Fused SSIM and the colour-refinement loss (the `fused_ssim` drop-in) ---------------------------------
+ * SSIM of Wang et al. 2004 as 3DGS code bases use it: per plane (one channel of one image; img1 / img2 are
+ * [planes,H,W] float32), the normalised 11-tap Gaussian window of sigma 1.5 applied separably with zero padding, mean of
+ * the map over all pixels (valid = 0, padding "same") or over the map without its outer 5 pixels (valid != 0, padding
+ * "valid"; needs width, height >= 11).  C1 / C2 are the two stabilising constants (MGS_SSIM_C1 / MGS_SSIM_C2 upstream).
+ * mgs_ssim_forward writes the mean to value_out [device scalar]; with train != 0 it also leaves the three derivative
+ * planes of the map in `scratch` (mgs_ssim_scratch_bytes, same planes / size / train), from which mgs_ssim_backward forms
+ * d_img1[planes,H,W] = grad_out x d(mean)/d(img1) (grad_out: device scalar, NULL = 1).  img2 gets no gradient.
+ * No atomics: per-workgroup partial sums added in a fixed order, values bitwise reproducible.
+ *
+ * Refinement loss (/root/reference/utils/slam_mapper.py:529-539): L = (1 - lambda) mean|render - gt| + lambda (1 - SSIM_valid),
+ * render / gt_rgb [3,H,W].  mgs_refine_loss_forward / _backward are the two halves for an autograd node (loss_out, grad_out:
+ * device scalars); mgs_refine_loss_grads gives the value AND d_render for grad_out = 1 with no host synchronisation.  After
+ * any of the forwards scratch[MGS_SSIM_SCRATCH_LOSS], [.._L1], [.._SSIM] hold the loss, the L1 mean and the SSIM
+ * (scratch: mgs_ssim_scratch_bytes(3, width, height, 1)). */
+#define MGS_SSIM_C1 0.0001f
+#define MGS_SSIM_C2 0.0009f
+#define MGS_SSIM_SCRATCH_LOSS 0
+#define MGS_SSIM_SCRATCH_L1 1
+#define MGS_SSIM_SCRATCH_SSIM 2
+size_t mgs_ssim_scratch_bytes(int32_t planes, int32_t width, int32_t height, int32_t train);
+int mgs_ssim_forward(int32_t planes, int32_t width, int32_t height, int32_t valid, int32_t train, float C1, float C2,
+                     const float* img1, const float* img2, float* scratch, float* value_out, void* stream);
+int mgs_ssim_backward(int32_t planes, int32_t width, int32_t height, int32_t valid, float C1, float C2,
+                      const float* img1, const float* img2, const float* scratch, const float* grad_out,
+                      float* d_img1, void* stream);
+int mgs_refine_loss_forward(int32_t width, int32_t height, float lambda_ssim, const float* render, const float* gt_rgb,
+                            float* scratch, float* loss_out, void* stream);
+int mgs_refine_loss_backward(int32_t width, int32_t height, float lambda_ssim, const float* render, const float* gt_rgb,
+                             const float* scratch, const float* grad_out, float* d_render, void* stream);
+int mgs_refine_loss_grads(int32_t width, int32_t height, float lambda_ssim, const float* render, const float* gt_rgb,
+                          float* scratch, float* d_render, void* stream);
 
 /* ---- Fused pose update (caller-side widening) -------------------------------
  * torch.optim.Adam.step() on (cam_rot_delta lr_rot, cam_trans_delta lr_trans, exposure_a/b lr_exposure)

@@ -11,7 +11,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MGS_LIB_PATH") or os.path.join(_HERE, "lib", "libmonogs_raster.so")   # (override: kernel experiments)
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 c_float_p = C.c_void_p   # device pointers travel as integers (tensor.data_ptr())
 
@@ -71,6 +71,12 @@ SIGNATURES = {
     "mgs_loss_backward": (C.c_int, [C.c_int32] * 4 + [C.c_float] + [C.c_void_p] * 9
                           + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mgs_loss_grads": (C.c_int, [C.c_int32] * 4 + [C.c_float] + [C.c_void_p] * 9 + [C.c_void_p] * 4),
+    "mgs_ssim_scratch_bytes": (C.c_size_t, [C.c_int32] * 4),
+    "mgs_ssim_forward": (C.c_int, [C.c_int32] * 5 + [C.c_float] * 2 + [C.c_void_p] * 5),
+    "mgs_ssim_backward": (C.c_int, [C.c_int32] * 4 + [C.c_float] * 2 + [C.c_void_p] * 6),
+    "mgs_refine_loss_forward": (C.c_int, [C.c_int32] * 2 + [C.c_float] + [C.c_void_p] * 5),
+    "mgs_refine_loss_backward": (C.c_int, [C.c_int32] * 2 + [C.c_float] + [C.c_void_p] * 6),
+    "mgs_refine_loss_grads": (C.c_int, [C.c_int32] * 2 + [C.c_float] + [C.c_void_p] * 5),
     "mgs_backproject": (C.c_int, [C.c_int32] * 3 + [C.c_void_p] * 6 + [C.c_float] * 4 + [C.c_void_p] * 6),
     "mgs_camera_setup": (C.c_int, [C.c_void_p] * 7),
     "mgs_pose_step": (C.c_int, [C.c_void_p] * 12 + [C.c_int32] + [C.c_float] * 7

@@ -150,3 +150,93 @@ def loss_grads(render_image, render_depth, render_opacity, viewpoint, tracking: 
                                       p(depth), p(opac), p(gt_rgb), p(gt_depth), p(mask), p(gm), p(a), p(b), p(scratch),
                                       p(d_render), p(d_depth), _stream()), "mgs_loss_grads")
     return LossGrads(d_render, d_depth, scratch, not init)
+
+
+# ---- colour refinement: (1 - lambda) L1 + lambda (1 - SSIM) ------------------------------------------------------------------
+_R_LOSS, _R_L1, _R_SSIM = 0, 1, 2     # MGS_SSIM_SCRATCH_LOSS / _L1 / _SSIM (include/monogs_raster.h)
+
+
+def _refine_inputs(image, gt_image):
+    from .ssim import _check_pair
+    if image.dim() == 4 and image.shape[0] == 1:
+        image = image[0]
+    if gt_image.dim() == 4 and gt_image.shape[0] == 1:
+        gt_image = gt_image[0]
+    if image.dim() != 3 or image.shape[0] != 3:
+        raise ValueError(f"the refinement loss takes one [3,H,W] image (got {tuple(image.shape)})")
+    _, H, W, _ = _check_pair(image, gt_image, "valid")
+    return _f32(image.detach(), "image"), _f32(gt_image.detach(), "gt_image"), H, W
+
+
+class _RefineLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, image, gt_image, lam):
+        lib = _lib.load()
+        render, gt, H, W = _refine_inputs(image, gt_image)
+        dev = render.device
+        with _device_guard(dev):
+            scratch = torch.empty(lib.mgs_ssim_scratch_bytes(3, W, H, 1) // 4, dtype=torch.float32, device=dev)
+            loss = torch.empty((), dtype=torch.float32, device=dev)
+            _lib.check(lib.mgs_refine_loss_forward(W, H, lam, render.data_ptr(), gt.data_ptr(), scratch.data_ptr(),
+                                                   loss.data_ptr(), _stream()), "mgs_refine_loss_forward")
+        ctx.cfg = (W, H, lam, tuple(image.shape))
+        ctx.save_for_backward(render, gt, scratch)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        lib = _lib.load()
+        render, gt, scratch = ctx.saved_tensors
+        W, H, lam, shape = ctx.cfg
+        with _device_guard(render.device):
+            go = _f32(grad_out.reshape(1), "grad_output")
+            d_render = torch.empty_like(render)
+            _lib.check(lib.mgs_refine_loss_backward(W, H, lam, render.data_ptr(), gt.data_ptr(), scratch.data_ptr(),
+                                                    go.data_ptr(), d_render.data_ptr(), _stream()), "mgs_refine_loss_backward")
+        return d_render.view(shape), None, None
+
+
+def get_loss_refinement(image, gt_image, lambda_ssim=0.2):
+    """The loss of ``Mapper.refinement()`` (/root/reference/utils/slam_mapper.py:529-539) as one autograd scalar:
+    ``(1 - lambda) |image - gt|.mean() + lambda (1 - ssim(image, gt))`` with the reference's ``ssim`` (``padding="valid"``).
+    One forward kernel + finalize, one backward kernel (csrc/ssim.hip); gradient to ``image`` only."""
+    return _RefineLoss.apply(image, gt_image, float(lambda_ssim))
+
+
+class RefineGrads:
+    """Result of ``refinement_loss_grads``: dL/dimage + views of the scalar results on the device."""
+    __slots__ = ("d_render", "scratch")
+
+    def __init__(self, d_render, scratch):
+        self.d_render, self.scratch = d_render, scratch
+
+    @property
+    def loss(self) -> torch.Tensor:
+        return self.scratch[_R_LOSS]
+
+    @property
+    def l1(self) -> torch.Tensor:
+        return self.scratch[_R_L1]
+
+    @property
+    def ssim(self) -> torch.Tensor:
+        return self.scratch[_R_SSIM]
+
+    def backward(self, image):
+        torch.autograd.backward([image], [self.d_render.view(image.shape)])
+
+
+@torch.no_grad()
+def refinement_loss_grads(image, gt_image, lambda_ssim=0.2) -> RefineGrads:
+    """``get_loss_refinement`` as VALUE + GRADIENT (for grad_output = 1) in three launches and no host synchronisation, for
+    loops that call ``torch.autograd.backward([image], [d_render])`` themselves, as ``loss_grads`` does for the SLAM losses.
+    Same numbers as the autograd path, bit for bit."""
+    lib = _lib.load()
+    render, gt, H, W = _refine_inputs(image, gt_image)
+    dev = render.device
+    with _device_guard(dev):
+        scratch = torch.empty(lib.mgs_ssim_scratch_bytes(3, W, H, 1) // 4, dtype=torch.float32, device=dev)
+        d_render = torch.empty_like(render)
+        _lib.check(lib.mgs_refine_loss_grads(W, H, float(lambda_ssim), render.data_ptr(), gt.data_ptr(), scratch.data_ptr(),
+                                             d_render.data_ptr(), _stream()), "mgs_refine_loss_grads")
+    return RefineGrads(d_render, scratch)
