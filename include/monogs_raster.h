@@ -168,9 +168,7 @@ int mgs_debug_set_radix_spin_limit(uint32_t limit);
 /* TEST USE ONLY, process-global, not thread-safe: knobs that force an algorithm path whatever the problem size (-1 restores the default):
  * "radix_scanned" (0 = one kernel per pass with a gather of the earlier tiles' counts, 1 = counted tiles: two kernels per
  * pass, no waiting between workgroups -- honoured from 64 k pairs), "radix_ballot_rank" (1 = rank with wave ballots instead of
- * returning LDS atomics: the reference the sort tests compare with), "scan_small" (0 = the two-launch scan at every size), "depth_small" (1 = maps <= 24 576 Gaussians run
- * depth sort + rectangle gather + scan as ONE single-workgroup launch: measured slower, off by default), "blend_lds_pad_fwd" / "blend_lds_pad_bwd" (dynamic
- * LDS bytes the blend kernels never touch: fewer workgroups per compute unit, a measurement knob),
+ * returning LDS atomics: the reference the sort tests compare with), "scan_small" (0 = the two-launch scan at every size),
  * "dup_slot_major" (0 / 1 = the duplicate kernel's emission balanced by Gaussians / by output slots at every size),
  * "tile_sort_fused" (per-tile path: 1 = default, each blend forward workgroup sorts its own tile's list first; 0 = the
  * per-tile depth sort as a launch of its own between the tile sort and the blend forward; the same lists either way),
@@ -185,8 +183,7 @@ int mgs_debug_set_radix_spin_limit(uint32_t limit);
  * num_rendered, i.e. in capacity mode the CAPACITY, so the line moves with the caller's headroom),
  * "blend_bwd_split_min" / "blend_bwd_split_frac" (the shortest list that is split, in 64-instance steps, default 4; the
  * front walk's share of a list in 256ths, default 32),
- * "radix_xcd_band" (0 = counted tiles in block-id order instead of one contiguous band of tiles per XCD), "radix_tile_items"
- * (8 | 12 | 16 pairs per thread on the counted-tiles path, 0 = by size; set it before any scratch is sized),
+ * "radix_xcd_band" (0 = counted tiles in block-id order instead of one contiguous band of tiles per XCD),
  * "debug_sort_exclusive" (1 = mgs_debug_sort_pairs sorts as under MGS_FLAG_EXCLUSIVE_DEVICE).  Nothing on the launch path
  * consults the environment. */
 int mgs_debug_set_option(const char* name, int64_t value);

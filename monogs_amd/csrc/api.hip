@@ -193,9 +193,6 @@ int mgs_forward_preprocess(const mgs_camera* cam, int32_t P, const float* means3
     if (per_tile) {                         // no global depth sort: the scan runs in index order (binning.hip)
         tm.mark();
         if (int rc = launch_scan(g, P, s, exclusive, g.rect)) return rc;
-    } else if (depth_chain_is_small(P)) {   // one single-workgroup launch: sort, rectangle gather and scan (timed as the depth sort)
-        if (int rc = launch_depth_chain_small(g, P, s)) return rc;
-        tm.mark();
     } else {
         if (int rc = launch_depth_sort(g, P, depth_sort_payload(P, cam->image_width, cam->image_height), s, exclusive)) return rc;
         tm.mark();
@@ -433,7 +430,6 @@ int mgs_debug_sort_pairs(uint32_t* keys, uint32_t* vals, uint32_t* keys_alt, uin
 int mgs_debug_set_option(const char* name, int64_t value) {
     if (name && !strcmp(name, "radix_scanned")) { g_opt_radix_scanned = (int)value; return 0; }
     if (name && !strcmp(name, "radix_ballot_rank")) { g_opt_radix_ballot_rank = (int)value; return 0; }
-    if (name && !strcmp(name, "radix_tile_items")) { g_opt_radix_tile_items = (int)value; return 0; }
     if (name && !strcmp(name, "radix_xcd_band")) { g_opt_radix_xcd_band = (int)value; return 0; }
     if (name && !strcmp(name, "debug_sort_exclusive")) { g_opt_debug_sort_exclusive = (int)value; return 0; }
     if (name && !strcmp(name, "dup_slot_major")) { g_opt_dup_slot_major = (int)value; return 0; }
@@ -446,10 +442,7 @@ int mgs_debug_set_option(const char* name, int64_t value) {
     if (name && !strcmp(name, "blend_bwd_split_min")) { g_opt_blend_bwd_split_min = value < 0 ? 4 : (int)value; return 0; }
     if (name && !strcmp(name, "blend_bwd_split_frac")) { g_opt_blend_bwd_split_frac = value < 0 ? 32 : (int)value; return 0; }
     if (name && !strcmp(name, "scan_small")) { g_opt_scan_small = (int)value; return 0; }
-    if (name && !strcmp(name, "depth_small")) { g_opt_depth_small = (int)value; return 0; }
     if (name && !strcmp(name, "tile_sort_fused")) { g_opt_tile_sort_fused = value < 0 ? 1 : (int)value; return 0; }
-    if (name && !strcmp(name, "blend_lds_pad_fwd")) { g_opt_blend_lds_pad_fwd = (int)value; return 0; }
-    if (name && !strcmp(name, "blend_lds_pad_bwd")) { g_opt_blend_lds_pad_bwd = (int)value; return 0; }
     if (name && !strcmp(name, "knn_grid_min")) { g_opt_knn_grid_min = value > 0x7FFFFFFF ? 0x7FFFFFFF : (int)value; return 0; }
     set_error("mgs_debug_set_option: unknown option");
     return 1;

@@ -26,7 +26,6 @@
 
 namespace mgs {
 
-extern int g_opt_blend_lds_pad_fwd, g_opt_blend_lds_pad_bwd;
 #ifdef BS_TRACE
 // Diagnostic build only (tools/build_variant.sh trace blend.hip -DBS_TRACE; tools/wave_timeline.py): every wave of the two blend
 // kernels leaves {start, end} (s_memrealtime, 100 MHz), its hardware id and the survivors it evaluated in a buffer of its own.
@@ -125,11 +124,7 @@ __device__ __forceinline__ Rec fetch(const BlendArgs& a, uint32_t gid_uniform) {
 //     EXEC = all
 // One asm block (the compiler must never see a narrowed EXEC): 17 scalar + 23 vector instructions per survivor, 19 + 25
 // while a pixel of the quadrant is still in front of half its light (TOUCH: only then can T (1 - alpha) exceed 0.5).
-#ifdef MGS_FWD_SCALAR
-#define MGS_RECOP "s"          // experiment: the survivor's record through two scalar loads (SGPR offset), as the round-5 backward
-#else
-#define MGS_RECOP "v"          // the survivor's record comes back from the per-wave LDS queue in vector registers
-#endif
+// The survivor's record (g) comes back from the per-wave LDS queue in vector registers.
 template <bool TOUCH>
 __device__ __forceinline__ void blend_one(unsigned long long& live, unsigned long long& mask, float& T, uint32_t& last, float& C0, float& C1, float& C2,
                                       float& D, const Rec& g, float power, float alpha, uint32_t pos, int j,
@@ -161,7 +156,7 @@ __device__ __forceinline__ void blend_one(unsigned long long& live, unsigned lon
             : [live] "+s"(live), [mask] "+s"(mask), [T] "+v"(T), [last] "+v"(last), [C0] "+v"(C0), [C1] "+v"(C1), [C2] "+v"(C2), [D] "+v"(D),
               [w] "=&v"(w), [cnt] "=&s"(cnt), [tc] "+v"(touched_cnt)
             : [power] "v"(power), [alpha] "v"(alpha), [tt] "v"(test_T), [amin] "s"(1.0f / 255.0f), [tmin] "s"(0.0001f),
-              [pos] "s"(pos), [cr] MGS_RECOP(g.r), [cg] MGS_RECOP(g.g), [cb] MGS_RECOP(g.b), [cz] MGS_RECOP(g.z), [j] "s"(j)
+              [pos] "s"(pos), [cr] "v"(g.r), [cg] "v"(g.g), [cb] "v"(g.b), [cz] "v"(g.z), [j] "s"(j)
             : "vcc", "scc", "m0");
     } else {
         asm volatile(
@@ -183,7 +178,7 @@ __device__ __forceinline__ void blend_one(unsigned long long& live, unsigned lon
             : [live] "+s"(live), [mask] "+s"(mask), [T] "+v"(T), [last] "+v"(last), [C0] "+v"(C0), [C1] "+v"(C1), [C2] "+v"(C2), [D] "+v"(D),
               [w] "=&v"(w)
             : [power] "v"(power), [alpha] "v"(alpha), [tt] "v"(test_T), [amin] "s"(1.0f / 255.0f), [tmin] "s"(0.0001f),
-              [pos] "s"(pos), [cr] MGS_RECOP(g.r), [cg] MGS_RECOP(g.g), [cb] MGS_RECOP(g.b), [cz] MGS_RECOP(g.z)
+              [pos] "s"(pos), [cr] "v"(g.r), [cg] "v"(g.g), [cb] "v"(g.b), [cz] "v"(g.z)
             : "vcc", "scc");
     }
 }
@@ -252,49 +247,6 @@ __global__ void __launch_bounds__(256) blend_forward_kernel(BlendArgs a, float* 
     // went to L2) and five scalar instructions of address arithmetic: 0.215 -> 0.191 ms at C5, 38.0 -> 34.8 us at 100 k / VGA.
     // (Rounds 2 built the same queue against the mask-algebra kernel and measured no gain: that kernel was bound by its
     // scalar ALU work, not by the fetch.)  No barrier: the queue belongs to one wave and a wave's LDS operations run in order.
-#ifdef MGS_FWD_SCALAR
-    typedef float fv2 __attribute__((ext_vector_type(2)));
-    typedef float fv8 __attribute__((ext_vector_type(8)));
-    const const_float_p recs = MGS_CONST(reinterpret_cast<const float*>(a.rec));
-    auto prefetch = [&](uint32_t i) {
-        gid_n = 0;
-        box_n = make_float4(0.f, 0.f, -1.f, -1.f);
-        if (i < range.y) {
-            gid_n = a.point_list[i];
-            box_n = a.rec[(size_t)gid_n * 4];
-            ell_n = a.rec[(size_t)gid_n * 4 + 3];
-        }
-    };
-    auto walk_step = [&](auto touch_tag, uint32_t base, uint32_t gid_l, unsigned long long mask) {
-        int touched_cnt = 0;
-        const uint32_t goff_l = gid_l << 6;
-        while (mask) {
-            int j;
-            asm volatile("s_ff1_i32_b64 %0, %1\n\ts_bitset0_b64 %1, %0" : "=&s"(j), "+s"(mask));
-            const uint32_t goff = (uint32_t)__builtin_amdgcn_readlane((int)goff_l, j);
-            fv2 r0;
-            fv8 r1;
-            asm volatile("s_load_dwordx2 %0, %2, %3\n\ts_load_dwordx8 %1, %2, %3 offset:0x10\n\ts_waitcnt lgkmcnt(0)"
-                         : "=&s"(r0), "=&s"(r1) : "s"(recs), "s"(goff) : "memory");
-            const Rec g{r0[0], r0[1], r1[0], r1[1], r1[2], r1[3], r1[4], r1[5], r1[6], r1[7]};
-            const float dx = g.px - pxf, dy = g.py - pyf;
-            const float power = dx * (g.ca * dx + g.cb * dy) + (g.cc * dy) * dy;
-            const float alpha = fminf(0.99f, g.op * __builtin_amdgcn_exp2f(power));
-            blend_one<decltype(touch_tag)::value>(live, mask, T, last, C0, C1, C2, D, g, power, alpha,
-                                                  (base - range.x) + (uint32_t)j + 1u, j, touched_cnt);
-        }
-        if (decltype(touch_tag)::value && touched_cnt != 0) atomicAdd(n_touched + gid_l, touched_cnt);
-    };
-    if (range.x < range.y) prefetch(range.x + lane);
-    for (uint32_t base = range.x; base < range.y && live != 0ull; base += WAVE) {
-        const uint32_t gid_l = gid_n;
-        const float4 c = box_n, el = ell_n;
-        prefetch(base + WAVE + lane);
-        const unsigned long long mask = __builtin_amdgcn_ballot_w64(quadrant_hit(c, el, qx0, qy0, live));
-        if ((live & __builtin_amdgcn_ballot_w64(T > 0.5f)) != 0ull) walk_step(std::true_type{}, base, gid_l, mask);
-        else walk_step(std::false_type{}, base, gid_l, mask);
-    }
-#else
     __shared__ __attribute__((aligned(16))) float4 s_queue[MGS_WG_WAVES][WAVE][3];
     // SORT: the tile's sorted indices (<= TDS_CAP), and the sort's reductions; its keys and digit counters alias the queue
     __shared__ uint32_t s_list[TDS_CAP], s_wsum[TDS_WAVES], s_red[2 * TDS_WAVES];
@@ -368,7 +320,6 @@ __global__ void __launch_bounds__(256) blend_forward_kernel(BlendArgs a, float* 
         if ((live & __builtin_amdgcn_ballot_w64(T > 0.5f)) != 0ull) walk_step(std::true_type{}, base, gid_l, mask);
         else walk_step(std::false_type{}, base, gid_l, mask);
     }
-#endif
 #ifdef BS_TRACE
     if (a.trace) {
         unsigned long long tr1;
@@ -420,20 +371,12 @@ int launch_blend_forward(const mgs_camera& cam, const GeometryState& g, const Bi
     if (ntiles == 0) return 0;
     const dim3 grid(ntiles), block(256);
     const TileSortArgs ts = tile_sort ? *tile_sort : TileSortArgs{};
-#ifdef MGS_FWD_SCALAR
-    // (no record queue to hold the sort's scratch: the per-tile sort keeps its own launch in this experiment)
     if (tile_sort)
-        if (int rc = launch_tile_depth_sort(cam, ts, img, sort_err, s)) return rc;
-    hipLaunchKernelGGL(blend_forward_kernel<false>, grid, block, (size_t)g_opt_blend_lds_pad_fwd, s, a, out_color, out_depth,
-                       out_opacity, img.final_T, img.n_contrib, n_touched, img.ranges, sort_err, status, ts);
-#else
-    if (tile_sort)
-        hipLaunchKernelGGL(blend_forward_kernel<true>, grid, block, (size_t)g_opt_blend_lds_pad_fwd, s, a, out_color, out_depth,
+        hipLaunchKernelGGL(blend_forward_kernel<true>, grid, block, 0, s, a, out_color, out_depth,
                            out_opacity, img.final_T, img.n_contrib, n_touched, img.ranges, sort_err, status, ts);
     else
-        hipLaunchKernelGGL(blend_forward_kernel<false>, grid, block, (size_t)g_opt_blend_lds_pad_fwd, s, a, out_color, out_depth,
+        hipLaunchKernelGGL(blend_forward_kernel<false>, grid, block, 0, s, a, out_color, out_depth,
                            out_opacity, img.final_T, img.n_contrib, n_touched, img.ranges, sort_err, status, ts);
-#endif
     MGS_HIP(hipGetLastError());
     return 0;
 }
@@ -1448,7 +1391,6 @@ int launch_blend_backward_stats(const mgs_camera& cam, const GeometryState& g, c
 
 // (The wave-per-tile and half-tile-per-wave variants of round 1 lost at every size and are gone; DESIGN.md section 4
 //  keeps their measurements.)
-int g_opt_blend_lds_pad_fwd = 0, g_opt_blend_lds_pad_bwd = 0;      // measurement knobs: dynamic LDS bytes the kernels never touch (fewer workgroups per CU)
 int g_opt_blend_bwd_split = -1;         // mgs_debug_set_option("blend_bwd_split", 1 | 2 | 0 | -1): every quadrant's list walked from both ends by two waves (1: all back halves, then all front halves; 2: the halves of a tile in adjacent workgroups), 0 = unsplit, -1 = the default (see launch_blend_backward); needs blend_bwd_transposed = 2 and the forward's colour and depth images
 int g_opt_blend_bwd_split_min = BS_SPLIT_MIN, g_opt_blend_bwd_split_frac = BS_SPLIT_FRAC;    // shortest list that is split (64-instance steps); the front walk's share of it / 256
 int g_opt_blend_bwd_transposed = 2;     // mgs_debug_set_option("blend_bwd_transposed", 0 | 1 | 2): 2 = scalar side trimmed + EXEC (round 5), 1 = scalar-fetch transposed (round 3), 0 = the per-survivor wave reduction
@@ -1483,8 +1425,7 @@ int launch_blend_backward(const mgs_camera& cam, const GeometryState& g, const B
         g_dbg_last_bwd_split = split ? 1 : 0;
         const BsSplit sp{max(g_opt_blend_bwd_split_min, 2), min(max(g_opt_blend_bwd_split_frac, 1), 255)};
         const dim3 grid(split ? 2 * ntiles : ntiles), block(256);
-        const size_t pad = (size_t)g_opt_blend_lds_pad_bwd;
-#define BS_LAUNCH(P_, S_) hipLaunchKernelGGL((blend_backward_s_kernel<P_, S_>), grid, block, pad, s, a, ntiles, img.final_T, img.n_contrib, \
+#define BS_LAUNCH(P_, S_) hipLaunchKernelGGL((blend_backward_s_kernel<P_, S_>), grid, block, 0, s, a, ntiles, img.final_T, img.n_contrib, \
                                              dL_dcolor, dL_ddepth, out_color, out_depth, grad_acc, sp, (int)(opt == 2))
         if (pose_only) { if (split) BS_LAUNCH(true, true); else BS_LAUNCH(true, false); }
         else { if (split) BS_LAUNCH(false, true); else BS_LAUNCH(false, false); }

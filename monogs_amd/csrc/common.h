@@ -216,9 +216,6 @@ inline float* backward_tau_part(void* scratch, int P) { return backward_grad_acc
 inline float* backward_tau_out(void* scratch, int P) { return backward_tau_part(scratch, P) + (size_t)TAU_SLOTS * 16; }
 // `rects`: the rectangles in the order the scan runs in (rect_sorted after a depth sort, rect by index on the per-tile path)
 int launch_scan(const GeometryState& g, int P, hipStream_t s, bool exclusive, const uint2* rects);
-// small maps: depth sort + rectangle gather + scan in ONE single-workgroup launch (binning.hip); replaces launch_depth_sort + launch_scan
-bool depth_chain_is_small(int P);
-int launch_depth_chain_small(const GeometryState& g, int P, hipStream_t s);
 // `r_cap`: capacity of the binning buffers; `count` (device): [0] live instance count min(R, r_cap), [1] overflow flag
 // `per_tile`: emit in Gaussian-index order with the depth bits packed into the pairs (binning_path() == 1)
 int launch_duplicate(const mgs_camera& cam, int P, const GeometryState& g, const BinningState& b, uint64_t r_cap,
@@ -277,7 +274,7 @@ int launch_tile_depth_sort(const mgs_camera& cam, const TileSortArgs& ts, const 
 int set_radix_spin_limit(uint32_t limit);
 extern bool g_opt_blend_bwd_transposed_set;
 extern int g_dbg_last_bwd_split;
-extern int g_opt_radix_ballot_rank, g_opt_radix_scanned, g_opt_radix_xcd_band, g_opt_radix_tile_items, g_opt_knn_grid_min, g_opt_scan_small, g_opt_dup_slot_major, g_opt_blend_bwd_transposed, g_opt_blend_bwd_split, g_opt_blend_bwd_split_min, g_opt_blend_bwd_split_frac, g_opt_blend_lds_pad_fwd, g_opt_blend_lds_pad_bwd, g_opt_depth_small;      // test knobs (mgs_debug_set_option)
+extern int g_opt_radix_ballot_rank, g_opt_radix_scanned, g_opt_radix_xcd_band, g_opt_knn_grid_min, g_opt_scan_small, g_opt_dup_slot_major, g_opt_blend_bwd_transposed, g_opt_blend_bwd_split, g_opt_blend_bwd_split_min, g_opt_blend_bwd_split_frac;      // test knobs (mgs_debug_set_option)
 // `sort_err`: the tile sort's error words (NULL: nothing was sorted); a raised word empties every tile and sets
 // MGS_STATUS_TILE_SORT_TIMEOUT in *status (what ranges_kernel did until round 4).  `tile_sort` (per-tile depth order, or
 // NULL): every workgroup first sorts its tile's list (tile_sort.h)

@@ -121,7 +121,7 @@ static inline bool rs_scanned(uint64_t n) {
 // Which depth order the forward builds (binning.hip): 1 = per tile (tile_depth_sort_kernel) wherever the map's depth sort
 // would take the counted-tiles path -- or at any size when the radix_scanned knob is 1 -- and the tile sort's keys have
 // room for the high depth bits beside a tile id of <= 16 bits, the values for the low ones beside the index:
-// P <= 2^(37 - tile bits).  0 = the global depth sort (one sweep, depth_chain_small, or counted tiles with the knob at 0).
+// P <= 2^(37 - tile bits).  0 = the global depth sort (one sweep, or counted tiles with the knob at 0).
 int binning_path(int P, int W, int H) {
     if (P <= 0) return 0;
     const bool large = g_opt_radix_scanned >= 0 ? g_opt_radix_scanned == 1 : (uint64_t)P > RS_ONE_SWEEP_MAX;
@@ -134,11 +134,8 @@ int binning_path(int P, int W, int H) {
 // lives (tile sort at C5, 5.27 M pairs = 1287 tiles of 4096 against 1024 resident: tile starts at 0 and at 14 us).  4096-pair
 // tiles: 84-92 VGPRs + 24 KB of LDS = 4-5 workgroups per CU; 3072-pair tiles: 72 VGPRs + 20 KB = 7 per CU (1792), and 1716
 // tiles at C5 (82.7 us against 85.9; 2048-pair tiles lose it again to the doubled count tables, 104.6 us).
-int g_opt_radix_tile_items = 0;     // mgs_debug_set_option("radix_tile_items", 8 | 12 | 16): pairs per thread on the counted-tiles path (0: by size)
 static inline int rs_tile_items(uint64_t n, bool scanned) {
     if (!scanned) return rs_items(n);
-    if (g_opt_radix_tile_items == RS_ITEMS_MID || g_opt_radix_tile_items == RS_ITEMS_WIDE || g_opt_radix_tile_items == RS_ITEMS)
-        return g_opt_radix_tile_items;
     return n > 1024ull * RS_THREADS * RS_ITEMS ? RS_ITEMS_WIDE : RS_ITEMS;
 }
 static inline uint32_t rs_tiles(uint64_t n, bool scanned) {
@@ -914,7 +911,6 @@ template <int DB, bool PAYLOAD>
 static void rs_launch_pass_items(const RsPassArgs& a, int items, bool scanned, uint32_t tiles, bool ballot, hipStream_t s) {
     if (scanned) {
         if (items == RS_ITEMS_WIDE) rs_launch_pass<RS_ITEMS_WIDE, DB, true, PAYLOAD>(a, tiles, ballot, s);
-        else if (items == RS_ITEMS_MID) rs_launch_pass<RS_ITEMS_MID, DB, true, PAYLOAD>(a, tiles, ballot, s);
         else rs_launch_pass<RS_ITEMS, DB, true, PAYLOAD>(a, tiles, ballot, s);
     } else if constexpr (!PAYLOAD && DB == 8) {        // (payloads and 9-bit digits only exist on the counted-tiles path)
         if (items == RS_ITEMS_SMALL) rs_launch_pass<RS_ITEMS_SMALL, 8, false, false>(a, tiles, ballot, s);
@@ -1001,8 +997,6 @@ static int rs_run(const RsPlan& pl, const RsBuffers& b, uint64_t n, void* temp, 
             h.wide = t.wide; h.detect = (pl.depth && p == 0) ? 1 : 0; h.only_if_wide = a.cond == 2 ? 1 : 0;
             if (items == RS_ITEMS_WIDE) {
                 if (pl.db[p] == 9) rs_launch_tile_hist<RS_ITEMS_WIDE, 9>(h, s); else rs_launch_tile_hist<RS_ITEMS_WIDE, 8>(h, s);
-            } else if (items == RS_ITEMS_MID) {
-                if (pl.db[p] == 9) rs_launch_tile_hist<RS_ITEMS_MID, 9>(h, s); else rs_launch_tile_hist<RS_ITEMS_MID, 8>(h, s);
             } else {
                 if (pl.db[p] == 9) rs_launch_tile_hist<RS_ITEMS, 9>(h, s); else rs_launch_tile_hist<RS_ITEMS, 8>(h, s);
             }

@@ -1,5 +1,5 @@
 #!/bin/bash
-# A/B of mgs_debug_set_option knobs on the GPU box: tools/ab_options.sh "" "blend_wgs_per_cu=3" ...  Prints the stage
+# A/B of mgs_debug_set_option knobs on the GPU box: tools/ab_options.sh "" "dup_slot_major=1" ...  Prints the stage
 # times at C5 and at 100 k Gaussians / VGA and the captured tracking / mapping rates of the synthetic TUM-like run.
 for o in "$@"; do
   export MGS_DEBUG_OPTIONS="$o"
