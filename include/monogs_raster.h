@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define MGS_ABI_VERSION 12
+#define MGS_ABI_VERSION 13
 #define MGS_TILE 16 /* tile edge in pixels; ranges are per 16x16 tile */
 
 /* GaussianRasterizationSettings, minus `prefiltered` / `debug` which are call flags
@@ -118,10 +118,11 @@ float* mgs_backward_tau(void* backward_scratch, int32_t P);
  * upstream forward does, because the caller must size the binning scratch from it.
  * Exactly one of (shs, colors_precomp) and exactly one of ((scales, rotations), cov3D_precomp) is non-NULL.
  * `prepare_backward`: NULL, or the scratch (mgs_backward_bytes(P)) of the ONE backward that will follow this forward.
- * The per-Gaussian kernel then also clears what that backward accumulates into -- the 64-byte gradient line of every
- * VISIBLE Gaussian (the others are never touched), the pose-gradient slots and the six floats at
- * mgs_backward_tau(scratch, P) -- and mgs_backward may be called with scratch_prepared = 1: no clearing launch and no
- * 64 B x P fill per backward. */
+ * The forward then also clears what that backward accumulates into: the per-Gaussian kernel the pose-gradient slots and the
+ * six floats at mgs_backward_tau(scratch, P), and the blend forward of the render call that follows (mgs_forward_render,
+ * mgs_forward_render_capacity) the P 64-byte gradient lines -- the scratch is prepared once BOTH calls have run, and
+ * mgs_backward may then be called with scratch_prepared = 1: no clearing launch per backward.  The address travels in the
+ * geometry scratch and is good for ONE render call: a later render of the same geometry scratch clears nothing. */
 int mgs_forward_preprocess(const mgs_camera* cam, int32_t P,
                            const float* means3D,        /* [P,3] */
                            const float* shs,            /* [P,M,3] or NULL */
@@ -284,6 +285,16 @@ int mgs_debug_last_backward_split(void);
 #define MGS_BLEND_STATS_WORDS 24
 int mgs_debug_blend_stats(const mgs_camera* cam, int32_t P, uint64_t num_rendered, const void* geometry,
                           const void* binning, const void* image, uint64_t* stats_dev, void* stream);
+
+/* Diagnostic (not on the hot path): the default blend backward (blend_backward_s_kernel) does not cull for itself, it walks the
+ * survivor masks the blend forward left in the binning scratch.  This walks every quadrant's list as that backward does, back to
+ * front, and counts into stats_dev[MGS_BLEND_MASK_STATS_WORDS] (device uint64): [0] 64-instance steps, [1] instances the
+ * backward's own cull would keep (what mgs_debug_blend_stats calls survivors), [2] set bits of the forward's masks inside the
+ * walked range (what the backward fetches and evaluates), [3] instances the own cull keeps and the forward's mask lacks: 0, or
+ * the backward would lose contributions. */
+#define MGS_BLEND_MASK_STATS_WORDS 4
+int mgs_debug_blend_mask_stats(const mgs_camera* cam, int32_t P, uint64_t num_rendered, const void* geometry,
+                               const void* binning, const void* image, uint64_t* stats_dev, void* stream);
 
 /* visible[P] (1 byte each) = view-space z > 0.2 (upstream markVisible; unused by MonoGS). */
 int mgs_mark_visible(int32_t P, const float* means3D, const float* viewmatrix, const float* projmatrix,

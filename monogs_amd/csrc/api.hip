@@ -41,6 +41,7 @@ GeometryState GeometryState::carve(void* base, int P) {
     g.tile_hist = (uint32_t*)take(p, 4 * 256 * sizeof(uint32_t));
     g.sort_temp_bytes = radix_depth_temp_bytes((uint64_t)P);
     g.sort_temp = take(p, g.sort_temp_bytes);           // 256-aligned, directly behind tile_hist
+    g.prepare = (unsigned long long*)take(p, 2 * sizeof(unsigned long long));
     g.end = p;
     return g;
 }
@@ -63,9 +64,13 @@ ImageState ImageState::carve(void* base, int W, int H) {
     return s;
 }
 
+size_t BinningState::fwd_mask_rows(uint64_t R, int W, int H) {
+    return (size_t)(R / 64) + (size_t)tiles_x(W) * tiles_y(H) + 1;
+}
 size_t BinningState::bytes(uint64_t R, int W, int H) {
     const size_t r = (size_t)(R ? R : 1);
-    return align_up(r * 4, 256) * 4 + align_up(mgs::sort_temp_bytes(R, tile_bits(W, H)), 256) + 256 + 256;
+    return align_up(r * 4, 256) * 4 + align_up(mgs::sort_temp_bytes(R, tile_bits(W, H)), 256) + 256 +
+           align_up(fwd_mask_rows(R, W, H) * 4 * sizeof(unsigned long long), 256) + 256;
 }
 BinningState BinningState::carve(void* base, uint64_t R, int W, int H) {
     const size_t r = (size_t)(R ? R : 1);
@@ -81,6 +86,7 @@ BinningState BinningState::carve(void* base, uint64_t R, int W, int H) {
     b.sort_temp_bytes = mgs::sort_temp_bytes(R, tile_bits(W, H));
     b.sort_temp = take(p, b.sort_temp_bytes);
     b.count = (uint32_t*)take(p, 2 * sizeof(uint32_t));
+    b.fwd_masks = (unsigned long long*)take(p, fwd_mask_rows(R, W, H) * 4 * sizeof(unsigned long long));   // behind everything older
     return b;
 }
 
@@ -266,7 +272,7 @@ static int forward_render_impl(const mgs_camera* cam, int32_t P, uint64_t R, boo
     tm.mark();
     if (g_dbg_fwd_events[0]) MGS_HIP(hipEventRecord(g_dbg_fwd_events[0], s));
     if (int rc = launch_blend_forward(*cam, g, b, img, out_color, out_depth, out_opacity, n_touched, sort_err, overflow,
-                                      fused ? &ts : nullptr, s)) return rc;
+                                      fused ? &ts : nullptr, P, s)) return rc;
     if (g_dbg_fwd_events[1]) MGS_HIP(hipEventRecord(g_dbg_fwd_events[1], s));
     tm.mark();
     if (timing) {
@@ -381,6 +387,20 @@ int mgs_debug_blend_stats(const mgs_camera* cam, int32_t P, uint64_t R, const vo
     ImageState img = ImageState::carve(const_cast<void*>(image), W, H);
     BinningState b = BinningState::carve(const_cast<void*>(binning), R, W, H);
     return launch_blend_backward_stats(*cam, g, b, img, (unsigned long long*)stats_dev, s);
+}
+
+int mgs_debug_blend_mask_stats(const mgs_camera* cam, int32_t P, uint64_t R, const void* geometry, const void* binning,
+                               const void* image, uint64_t* stats_dev, void* stream) {
+    if (check_cam(cam)) return 1;
+    if (!geometry || !image || !stats_dev || (R > 0 && !binning)) { set_error("bad arguments"); return 1; }
+    hipStream_t s = (hipStream_t)stream;
+    MGS_HIP(zero_fill(stats_dev, MGS_BLEND_MASK_STATS_WORDS * sizeof(uint64_t), s));
+    if (P == 0 || R == 0) return 0;
+    const int W = cam->image_width, H = cam->image_height;
+    GeometryState g = GeometryState::carve(const_cast<void*>(geometry), P);
+    ImageState img = ImageState::carve(const_cast<void*>(image), W, H);
+    BinningState b = BinningState::carve(const_cast<void*>(binning), R, W, H);
+    return launch_blend_mask_stats(*cam, g, b, img, (unsigned long long*)stats_dev, s);
 }
 
 int mgs_debug_valu_ceiling(float* out, int32_t iters, void* stream) {

@@ -211,8 +211,15 @@ __global__ void __launch_bounds__(256) duplicate_kernel(int P, const uint2* __re
                                                         uint32_t* __restrict__ count, uint32_t* __restrict__ overflow,
                                                         const uint32_t* __restrict__ depth_err, int offsets_global,
                                                         uint32_t* __restrict__ hist /* [4][256] or NULL */, int hist_passes,
-                                                        int n_threads /* of this launch */, int slot_major) {
+                                                        int n_threads /* of this launch */, int slot_major,
+                                                        unsigned long long* __restrict__ prepare /* GeometryState::prepare or NULL */) {
     const int i = blockIdx.x * 256 + threadIdx.x;          // (launched with 256 threads; blockDim would be a packet fetch)
+    // the accumulator preprocess was asked to prepare goes to THIS render call's blend forward, and to no later one: the scratch
+    // belongs to one backward, and a second render of the same geometry must not write into memory the caller may have freed
+    if (i == 0 && prepare) {
+        prepare[1] = prepare[0];
+        prepare[0] = 0ull;
+    }
     const int lane = threadIdx.x & 63;
     // scratch of the tile sort that follows (was its own launch)
     grid_zero(zero_ptr, zero_words, (size_t)n_threads, 256);
@@ -441,7 +448,8 @@ int launch_duplicate(const mgs_camera& cam, int P, const GeometryState& g, const
                        (uint32_t)(r_cap > 0xFFFFFFFFull ? 0xFFFFFFFFull : r_cap), n_touched, img.ranges, ntiles, zero_ptr,
                        zero_words, count, overflow, depth_err,
                        (P > 0 && scan_is_small(P)) ? 1 : 0,
-                       count_digits ? g.tile_hist : nullptr, (sort_bits + 7) / 8, n_threads, slot_major ? 1 : 0);
+                       count_digits ? g.tile_hist : nullptr, (sort_bits + 7) / 8, n_threads, slot_major ? 1 : 0,
+                       P > 0 ? g.prepare : nullptr);
     MGS_HIP(hipGetLastError());
     return 0;
 }

@@ -11,7 +11,8 @@
 //   1. lane l loads instance l of the step: the Gaussian index (coalesced) and float4 #0 of its
 //      64-byte record, {px, py, ex, ey};
 //   2. lane l tests the alpha >= 1/255 bounding box (px +- ex, py +- ey) against the wave's quadrant;
-//      __ballot compacts the survivors into a 64-bit mask held in scalar registers;
+//      __ballot compacts the survivors into a 64-bit mask held in scalar registers (the forward also leaves the mask in a table
+//      for the backward wave of the same quadrant, which then needs no test of its own: blend_backward_s_kernel);
 //   3. the wave pops survivors off the mask; the survivor's record arrives -- forward: with broadcast reads from a
 //      per-wave LDS queue that the lanes filled with the records they prefetched; backward: through the scalar cache
 //      (v_readlane of the index, s_load_dwordx2 + s_load_dwordx8) -- and all 64 lanes (pixels) evaluate it.
@@ -54,8 +55,15 @@ struct BlendArgs {
     const uint32_t* __restrict__ point_list;
     const uint2* __restrict__ ranges;
     const float* __restrict__ bg;
+    unsigned long long* fwd_masks;             // BinningState::fwd_masks: [row][quadrant], the forward's survivor masks
     int W, H, gx;
 };
+// Row of the mask table that step b of `tile` takes, its list starting at range_x: range_x / 64 + tile + b.  No two tiles share
+// a row: a list [x, x + n), x = 64 a + r, n = 64 c + s, takes c + (s > 0) rows from a + tile, and the next tile that has a list
+// starts at a row >= a + c + (r + s) / 64 + tile + 1 (empty tiles in between only add to `tile`).
+__device__ __forceinline__ size_t fwd_mask_word(uint32_t range_x, int tile, int wave) {
+    return ((size_t)(range_x / WAVE) + (size_t)tile) * 4 + (size_t)wave;
+}
 
 // Does the alpha >= 1/255 ellipse of an instance reach the 8x8 pixel quadrant whose first pixel is (qx0, qy0)?
 // First the padded bounding box (rejects most), then the exact minimum of the ellipse's quadratic form over the
@@ -196,8 +204,26 @@ __global__ void __launch_bounds__(256) blend_forward_kernel(BlendArgs a, float* 
                                                             int32_t* __restrict__ n_touched,
                                                             uint2* ranges_rw /* = a.ranges: read AND written here, through this pointer only */,
                                                             const uint32_t* __restrict__ sort_err,
-                                                            uint32_t* __restrict__ status, TileSortArgs ts) {
+                                                            uint32_t* __restrict__ status, TileSortArgs ts,
+                                                            const unsigned long long* __restrict__ prepare /* GeometryState::prepare or NULL */,
+                                                            int P, int lines_per_tile /* ceil(P / tiles) */) {
     MGS_TILE_WAVE(a.gx * ((a.H + TILE - 1) / TILE), tile, wave, ws)
+    // The backward that follows adds into one 64-byte gradient line per Gaussian.  The forward that was told of it
+    // (mgs_forward_preprocess's prepare_backward) clears those lines HERE, every workgroup a contiguous share of the P lines with
+    // 16-byte stores (a wave's store covers one contiguous KB): this kernel is issue-bound and leaves most of the memory system
+    // idle, while the per-Gaussian kernel that used to clear them runs at the copy ceiling.  All P lines,
+    // not the visible ones only: no read, and nothing reads the line of a culled Gaussian.  Before anything that depends on the
+    // tile: an empty tile clears its share too.  The address (0: nothing to clear) was left in the geometry scratch by
+    // preprocess and moved to [1] by duplicate_kernel, both earlier kernels: a scalar load through the constant address space.
+    if (prepare) {
+        float* const acc = reinterpret_cast<float*>((uintptr_t)MGS_CONST_U64(prepare)[1]);
+        if (acc) {
+            const int first = tile * lines_per_tile;
+            const int n4 = 4 * min(lines_per_tile, P - first);              // 16-byte pieces of this workgroup's share (<= 0: none)
+            float4* const base = reinterpret_cast<float4*>(acc + (size_t)first * GRAD_FLOATS);
+            for (int i = (int)threadIdx.x; i < n4; i += 256) base[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    }
     const int tx = tile % a.gx, ty = tile / a.gx;
     const int lane = threadIdx.x & 63;
     const bool first_of_tile = wave == 0 && lane == 0;
@@ -309,6 +335,12 @@ __global__ void __launch_bounds__(256) blend_forward_kernel(BlendArgs a, float* 
         }
         if (decltype(touch_tag)::value && touched_cnt != 0) atomicAdd(n_touched + gid_l, touched_cnt);
     };
+    // The step's survivor mask is also left for the backward (blend_backward_s_kernel walks these instead of culling again: its
+    // `alive` set at a step is a subset of `live` here, and quadrant_hit is monotone in it).  One 8-byte store per step, of the mask as
+    // the ballot left it (walk_step works on a copy that it cuts short when the quadrant is done); every step entered here is written, and the backward enters no other.
+    // (the range came through a vector load: readfirstlane puts the row's address, wave-uniform, into scalar registers)
+    unsigned long long* const mask_row = a.fwd_masks + fwd_mask_word((uint32_t)__builtin_amdgcn_readfirstlane((int)range.x), tile, wave);
+    uint32_t mask_off = 0;                          // byte offset of the step's row from the list's first (wave-uniform)
     if (range.x < range.y) prefetch(range.x + lane);
     for (uint32_t base = range.x; base < range.y && live != 0ull; base += WAVE) {
         const uint32_t gid_l = gid_n;
@@ -319,6 +351,12 @@ __global__ void __launch_bounds__(256) blend_forward_kernel(BlendArgs a, float* 
         // a pixel counts as "touched" by an instance when T (1 - alpha) > 0.5: impossible once every live pixel has T <= 0.5
         if ((live & __builtin_amdgcn_ballot_w64(T > 0.5f)) != 0ull) walk_step(std::true_type{}, base, gid_l, mask);
         else walk_step(std::false_type{}, base, gid_l, mask);
+        // The whole mask of the step, not what walk_step got through.  (Stored here, where the fewest vector registers are live:
+        //  lane 0 alone; the table row as the SGPR base and the step as the 32-bit offset: a per-lane 64-bit address and a store
+        //  right behind the ballot each cost the <true> instantiation its eighth wave)
+        if (__builtin_amdgcn_inverse_ballot_w64(1ull))
+            asm volatile("global_store_dwordx2 %0, %1, %2" ::"v"(mask_off), "v"(mask), "s"(mask_row) : "memory");
+        mask_off += 4u * (uint32_t)sizeof(unsigned long long);
     }
 #ifdef BS_TRACE
     if (a.trace) {
@@ -353,6 +391,7 @@ static BlendArgs make_args(const mgs_camera& cam, const GeometryState& g, const 
     a.point_list = b.vals_sorted;
     a.ranges = img.ranges;
     a.bg = cam.bg;
+    a.fwd_masks = b.fwd_masks;
     a.W = cam.image_width;
     a.H = cam.image_height;
     a.gx = tiles_x(a.W);
@@ -362,7 +401,7 @@ static BlendArgs make_args(const mgs_camera& cam, const GeometryState& g, const 
 int launch_blend_forward(const mgs_camera& cam, const GeometryState& g, const BinningState& b,
                          const ImageState& img, float* out_color, float* out_depth, float* out_opacity,
                          int32_t* n_touched, const uint32_t* sort_err, uint32_t* status, const TileSortArgs* tile_sort,
-                         hipStream_t s) {
+                         int P, hipStream_t s) {
     BlendArgs a = make_args(cam, g, b, img);
 #ifdef BS_TRACE
     a.trace = g_trace_fwd;
@@ -371,12 +410,17 @@ int launch_blend_forward(const mgs_camera& cam, const GeometryState& g, const Bi
     if (ntiles == 0) return 0;
     const dim3 grid(ntiles), block(256);
     const TileSortArgs ts = tile_sort ? *tile_sort : TileSortArgs{};
+    // (P == 0: nothing was preprocessed and the geometry scratch may be NULL)
+    const unsigned long long* const prepare = P > 0 ? g.prepare : nullptr;
+    const int lines_per_tile = (P + ntiles - 1) / ntiles;
     if (tile_sort)
         hipLaunchKernelGGL(blend_forward_kernel<true>, grid, block, 0, s, a, out_color, out_depth,
-                           out_opacity, img.final_T, img.n_contrib, n_touched, img.ranges, sort_err, status, ts);
+                           out_opacity, img.final_T, img.n_contrib, n_touched, img.ranges, sort_err, status, ts, prepare, P,
+                           lines_per_tile);
     else
         hipLaunchKernelGGL(blend_forward_kernel<false>, grid, block, 0, s, a, out_color, out_depth,
-                           out_opacity, img.final_T, img.n_contrib, n_touched, img.ranges, sort_err, status, ts);
+                           out_opacity, img.final_T, img.n_contrib, n_touched, img.ranges, sort_err, status, ts, prepare, P,
+                           lines_per_tile);
     MGS_HIP(hipGetLastError());
     return 0;
 }
@@ -977,20 +1021,14 @@ __device__ __forceinline__ void bs_walk(const BlendArgs& a, const int tile, cons
 #endif
 
     const int q = lane & 15;
-    const int fxi = qx0i + 4 * (q & 1), fyi = qy0i + (q >> 1);
-    if (lane < 16) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const bool in_i = (fxi + i) < a.W && fyi < a.H;
-            const size_t px_i = (size_t)fyi * a.W + fxi + i;
-            if (!POSE_ONLY) {
-                s_pix_ws[(0 * 16 + q) * 4 + i] = in_i ? dL_dcolor[px_i] : 0.f;
-                s_pix_ws[(1 * 16 + q) * 4 + i] = in_i ? dL_dcolor[HW + px_i] : 0.f;
-                s_pix_ws[(2 * 16 + q) * 4 + i] = in_i ? dL_dcolor[2 * HW + px_i] : 0.f;
-            }
-            s_pix_ws[((POSE_ONLY ? 0 : 3) * 16 + q) * 4 + i] = in_i ? dL_ddepth[px_i] : 0.f;
-        }
+    // dL/dpixel for the flush, [channel][q][4 pixels]: entry [ch][q][i] is the pixel (4 (q & 1) + i, q >> 1) of the quadrant, the
+    // one lane 4 q + i holds in g0 / g1 / g2 / gd (0 outside the image) -- so [ch][lane], from registers
+    if (!POSE_ONLY) {
+        s_pix_ws[0 * 64 + lane] = g0;
+        s_pix_ws[1 * 64 + lane] = g1;
+        s_pix_ws[2 * 64 + lane] = g2;
     }
+    s_pix_ws[(POSE_ONLY ? 0 : 3) * 64 + lane] = gd;
     const int slot = POSE_ONLY ? bt_slot6(q) : bt_slot10(q);
     const uint32_t slot_bytes = slot < 0 ? 0u : (uint32_t)slot * 4u;
     const unsigned long long m_out = __builtin_amdgcn_ballot_w64(slot >= 0);
@@ -1002,30 +1040,38 @@ __device__ __forceinline__ void bs_walk(const BlendArgs& a, const int tile, cons
     float zero = 0.f;
     asm volatile("" : "+v"(zero));  // (a VGPR holding 0: data operand of the slot-clearing LDS store)
 
+    // The survivors of a step are NOT found here: they are the forward's, bit j of the word the forward wave of this quadrant left
+    // for the step = instance j survived its cull (fwd_mask_word).  That set holds every instance a cull of this walk's own would
+    // keep -- the pixels alive here (last contributor at or behind the step) were live there, and the cull is monotone in them --
+    // and what it holds beyond them has no active pixel: evaluate() takes no slot for it.  The word comes through the scalar cache
+    // (the forward is an earlier kernel), requested one step ahead with the lanes' indices and centres.
+    const const_u64_p mask_row = MGS_CONST_U64(a.fwd_masks) + fwd_mask_word((uint32_t)__builtin_amdgcn_readfirstlane((int)range.x), tile, wave);
     uint32_t gid_n = 0;
-    float4 box_n = make_float4(0.f, 0.f, -1.f, -1.f), ell_n = make_float4(0.f, 0.f, 0.f, 0.f);
+    float2 ctr_n = make_float2(0.f, 0.f);
+    unsigned long long mask_n = 0ull;
     auto prefetch = [&](int b) {                    // lane l takes instance 63 - l of step b (front walk: instance l)
+        // (first: the word is then on its way while the lanes wait for their indices.  The step behind the walk's last is
+        //  requested too and never used: clamped, it is a row of this tile either way)
+        mask_n = mask_row[(size_t)max(b, 0) * 4];
         gid_n = 0;
-        box_n = make_float4(0.f, 0.f, -1.f, -1.f);
         const uint32_t i = range.x + (uint32_t)b * WAVE + (uint32_t)(FRONT ? lane : 63 - lane);
         if (b >= (FRONT ? 0 : b_lo) && i < end) {
             gid_n = a.point_list[i];
-            box_n = a.rec[(size_t)gid_n * 4];
-            ell_n = a.rec[(size_t)gid_n * 4 + 3];
+            ctr_n = *reinterpret_cast<const float2*>(a.rec + (size_t)gid_n * 4);      // the centre: for the flush
         }
     };
     const int b_first = FRONT ? 0 : (int)((maxc - 1) / WAVE), b_step = FRONT ? 1 : -1;
     prefetch(b_first);
     for (int b = b_first; FRONT ? b < b_lo : b >= b_lo; b += b_step) {
-        const float4 c = box_n, el = ell_n;
-        v3f meta = {c.x, c.y, __uint_as_float(gid_n << 6)};        // what the lane notes for the flush if its instance survives
+        v3f meta = {ctr_n.x, ctr_n.y, __uint_as_float(gid_n << 6)};        // what the lane notes for the flush if its instance survives
+        unsigned long long mask = mask_n;
         prefetch(b + b_step);
-        const unsigned long long alive = __builtin_amdgcn_ballot_w64(last >= (uint32_t)b * WAVE + 1u);
-        // (the quadrant origin as floats is re-derived per step from the scalar integers: kept across the walk the two floats
-        //  sit in vector registers, and the kernel has exactly 64)
-        int qxs = qx0i, qys = qy0i;
-        asm volatile("" : "+s"(qxs), "+s"(qys));
-        unsigned long long mask = __builtin_amdgcn_ballot_w64(quadrant_hit(c, el, (float)qxs, (float)qys, alive));
+        if (!FRONT) {
+            // list positions beyond the last contributor of the quadrant (only the walk's first step has any), then lane l = instance 63 - l;
+            // the front walk ends on a whole step
+            if (b == b_first) mask &= ~0ull >> (63u - ((maxc - 1u) & 63u));
+            mask = __builtin_bitreverse64(mask);
+        }
         // lane j holds the instance with list position k_first + 63 - j: a pixel takes it only if that is <= last,
         // i.e. j >= 63 + k_first - last
         // (front walk: lane j holds position k_first + j, taken if j <= last - k_first; the lowest set bit is the frontmost)
@@ -1385,6 +1431,60 @@ int launch_blend_backward_stats(const mgs_camera& cam, const GeometryState& g, c
     if (ntiles == 0) return 0;
     hipLaunchKernelGGL(blend_backward_stats_kernel, dim3(ntiles), dim3(256), 0, s, a, ntiles, img.n_contrib, stats);
     hipLaunchKernelGGL(blend_group_stats_kernel, dim3(ntiles), dim3(256), 0, s, a, ntiles, img.n_contrib, stats);
+    MGS_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---- diagnostic: the forward's survivor masks against the backward's own cull (not on the hot path; mgs_debug_blend_mask_stats)
+// blend_backward_s_kernel walks the masks the forward left (BinningState::fwd_masks) instead of culling for itself.  This walks
+// every quadrant's list as the unsplit backward does and runs the cull the backward used to run -- the one blend_backward_stats_kernel
+// and the two older backward kernels still run -- beside the forward's word of the step, trimmed to the walk's range as bs_walk
+// trims it: stats[0] steps, [1] instances the own cull keeps, [2] set bits of the forward's masks, [3] instances the own cull
+// keeps and the mask lacks (0: the masks cover the cull).  [2] - [1] is what the backward now evaluates for nothing.
+__global__ void __launch_bounds__(256) blend_mask_stats_kernel(BlendArgs a, int ntiles, const uint32_t* __restrict__ n_contrib,
+                                                               unsigned long long* __restrict__ stats) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int tile = (int)blockIdx.x;
+    if (tile >= ntiles) return;
+    const int tx = tile % a.gx, ty = tile / a.gx;
+    const uint2 range = a.ranges[tile];
+    if (range.y <= range.x) return;
+    const int qx0i = tx * TILE + (wave & 1) * SUB, qy0i = ty * TILE + (wave >> 1) * SUB;
+    const int pxi = qx0i + (lane & 7), pyi = qy0i + (lane >> 3);
+    const bool inside = pxi < a.W && pyi < a.H;
+    const float qx0 = (float)qx0i, qy0 = (float)qy0i;
+    const uint32_t last = inside ? n_contrib[(size_t)pyi * a.W + pxi] : 0u;
+    const uint32_t maxc = wave_max_u32(last);
+    if (maxc == 0) return;
+    const uint32_t end = range.x + maxc;
+    const unsigned long long* const mask_row = a.fwd_masks + fwd_mask_word(range.x, tile, wave);
+    unsigned long long c0 = 0, c1 = 0, c2 = 0, c3 = 0;
+    const int b_first = (int)((maxc - 1) / WAVE);
+    for (int b = b_first; b >= 0; --b) {
+        const uint32_t i = range.x + (uint32_t)b * WAVE + lane;
+        float4 box = make_float4(0.f, 0.f, -1.f, -1.f), el = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (i < end) {
+            const uint32_t gid_l = a.point_list[i];
+            box = a.rec[(size_t)gid_l * 4];
+            el = a.rec[(size_t)gid_l * 4 + 3];
+        }
+        const unsigned long long alive = __builtin_amdgcn_ballot_w64(last >= (uint32_t)b * WAVE + 1u);
+        const unsigned long long own = __builtin_amdgcn_ballot_w64(quadrant_hit(box, el, qx0, qy0, alive));
+        unsigned long long fwd = mask_row[(size_t)b * 4];
+        if (b == b_first) fwd &= ~0ull >> (63u - ((maxc - 1u) & 63u));
+        c0 += 1;
+        c1 += __popcll(own);
+        c2 += __popcll(fwd);
+        c3 += __popcll(own & ~fwd);
+    }
+    if (lane < 4) atomicAdd(stats + lane, lane == 0 ? c0 : lane == 1 ? c1 : lane == 2 ? c2 : c3);
+}
+int launch_blend_mask_stats(const mgs_camera& cam, const GeometryState& g, const BinningState& b,
+                            const ImageState& img, unsigned long long* stats, hipStream_t s) {
+    const BlendArgs a = make_args(cam, g, b, img);
+    const int ntiles = a.gx * tiles_y(a.H);
+    if (ntiles == 0) return 0;
+    hipLaunchKernelGGL(blend_mask_stats_kernel, dim3(ntiles), dim3(256), 0, s, a, ntiles, img.n_contrib, stats);
     MGS_HIP(hipGetLastError());
     return 0;
 }

@@ -48,10 +48,14 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 // reading them (kernel boundaries invalidate the scalar cache).
 #if defined(__HIP_DEVICE_COMPILE__)
 typedef const float __attribute__((address_space(4))) * const_float_p;
+typedef const unsigned long long __attribute__((address_space(4))) * const_u64_p;
 #define MGS_CONST(p) ((mgs::const_float_p)(p))
+#define MGS_CONST_U64(p) ((mgs::const_u64_p)(p))
 #else
 typedef const float* const_float_p;
+typedef const unsigned long long* const_u64_p;
 #define MGS_CONST(p) (p)
+#define MGS_CONST_U64(p) (p)
 #endif
 
 // ---- 64-lane inclusive scan (u32 add) on the DPP data path: 4 row shifts + 2 row broadcasts, ~60 cycles, instead of
@@ -140,6 +144,9 @@ struct GeometryState {
                               //          once the instance count is known)
     void* sort_temp;          // depth sort scratch (directly behind tile_hist: preprocess clears all three in one sweep)
     size_t sort_temp_bytes;
+    unsigned long long* prepare;   // [2] the backward accumulator whose gradient lines the NEXT blend forward clears, or 0:
+                              //     [0] written by preprocess (mgs_forward_preprocess's prepare_backward), moved to [1] by
+                              //     duplicate_kernel and read there by blend_forward_kernel -- one render call per hand-over
     char* end;                // one past the last carved byte
     static size_t bytes(int P);
     static GeometryState carve(void* base, int P);
@@ -164,6 +171,10 @@ struct BinningState {
     void* sort_temp;
     size_t sort_temp_bytes;
     uint32_t* count;           // [2] capacity mode: live instance count, overflow flag
+    unsigned long long* fwd_masks;   // [R / 64 + tiles + 1][4] the blend forward's survivor masks, one word per (64-instance step,
+                               //     quadrant): step b of a tile whose list starts at x has the row x / 64 + tile + b, which
+                               //     no other tile's step has; written by blend_forward_kernel, walked by blend_backward_s_kernel
+    static size_t fwd_mask_rows(uint64_t R, int W, int H);
     static size_t bytes(uint64_t R, int W, int H);
     static BinningState carve(void* base, uint64_t R, int W, int H);
 };
@@ -214,6 +225,8 @@ constexpr int TAU_SLOTS = 256;              // one 64-byte line each
 inline float* backward_grad_acc(void* scratch) { return (float*)align_up((size_t)scratch, 256); }
 inline float* backward_tau_part(void* scratch, int P) { return backward_grad_acc(scratch) + (size_t)P * GRAD_FLOATS; }
 inline float* backward_tau_out(void* scratch, int P) { return backward_tau_part(scratch, P) + (size_t)TAU_SLOTS * 16; }
+// `prepare_grad_acc` (or NULL): the pose part behind the accumulator is cleared by the kernel itself; the accumulator's address is
+// left in g.prepare[0] for the render call that follows, whose blend forward clears the P gradient lines (blend.hip)
 // `rects`: the rectangles in the order the scan runs in (rect_sorted after a depth sort, rect by index on the per-tile path)
 int launch_scan(const GeometryState& g, int P, hipStream_t s, bool exclusive, const uint2* rects);
 // `r_cap`: capacity of the binning buffers; `count` (device): [0] live instance count min(R, r_cap), [1] overflow flag
@@ -281,12 +294,14 @@ extern int g_opt_radix_ballot_rank, g_opt_radix_scanned, g_opt_radix_xcd_band, g
 int launch_blend_forward(const mgs_camera& cam, const GeometryState& g, const BinningState& b,
                          const ImageState& img, float* out_color, float* out_depth, float* out_opacity,
                          int32_t* n_touched, const uint32_t* sort_err, uint32_t* status, const TileSortArgs* tile_sort,
-                         hipStream_t s);
+                         int P, hipStream_t s);
 int launch_blend_backward(const mgs_camera& cam, const GeometryState& g, const BinningState& b,
                           const ImageState& img, const float* dL_dcolor, const float* dL_ddepth, const float* out_color,
                           const float* out_depth, float* grad_acc, bool pose_only, uint64_t num_rendered, hipStream_t s);
 int launch_blend_backward_stats(const mgs_camera& cam, const GeometryState& g, const BinningState& b,
                                 const ImageState& img, unsigned long long* stats, hipStream_t s);
+int launch_blend_mask_stats(const mgs_camera& cam, const GeometryState& g, const BinningState& b,
+                            const ImageState& img, unsigned long long* stats, hipStream_t s);
 int launch_valu_ceiling(float* out, int iters, hipStream_t s);
 struct GeomBackwardArgs {
     const float *means3D, *shs, *colors_precomp, *opacities, *scales, *rotations, *cov3D_precomp;

@@ -175,7 +175,8 @@ struct PreArgs {
     uint32_t* zero_ptr;       // scratch of the depth sort that follows: cleared here instead of by its own launch
     size_t zero_words;
     float* grad_acc;          // optional: accumulator of the backward that will follow ([P][16] + pose slots + 16): the
-                              //           lines of the visible Gaussians and the pose part are cleared here
+                              //           pose part is cleared here, the P lines by the blend forward that follows, which
+    unsigned long long* prepare;   //      finds the accumulator's address (or 0: nothing to clear) in prepare[0]
 };
 
 // 16-byte per-lane loads where the caller's tensor allows it (torch allocations are 256-byte aligned; a sliced view may not be)
@@ -288,6 +289,7 @@ __global__ void __launch_bounds__(256) preprocess_forward_kernel(PreArgs a) {
         float4* t4 = reinterpret_cast<float4*>(a.grad_acc + (size_t)a.P * GRAD_FLOATS);
         for (int i = threadIdx.x; i < (TAU_SLOTS + 1) * 4; i += 256) t4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
+    if (idx == 0) a.prepare[0] = (unsigned long long)(uintptr_t)a.grad_acc;      // (a forward without prepare_backward: 0)
     if (idx >= a.P) return;
     // ---- every per-Gaussian input is requested up front: ONE memory round trip before the arithmetic starts (a load
     //      placed behind each early exit used to cost a dependent round trip of its own; the 32 bytes this reads for a
@@ -352,24 +354,9 @@ __global__ void __launch_bounds__(256) preprocess_forward_kernel(PreArgs a) {
             rec[0] = o.r0; rec[1] = o.r1; rec[2] = o.r2; rec[3] = o.r3;
         }
     }
-    if (a.grad_acc) {
-        // The blend backward adds into the 64-byte gradient line of a visible Gaussian and the per-Gaussian backward reads
-        // it: those lines (only) are cleared here.  A full wave clears its 64 lines together -- lane l writes 16 bytes of
-        // the lines (l >> 2) + 16 k, k = 0..3, so each store instruction covers one contiguous KB minus the invisible
-        // Gaussians' holes (a lane writing its own line issued four 16-byte stores 64 bytes apart: +40 us at 2 M).
-        const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-        const int lane = threadIdx.x & 63, wave_first = idx - lane;
-        if (wave_first + WAVE <= a.P) {                       // wave-uniform: every lane is here
-            const unsigned long long vm = __builtin_amdgcn_ballot_w64(vis);
-            float4* base = reinterpret_cast<float4*>(a.grad_acc + (size_t)wave_first * GRAD_FLOATS);
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if ((vm >> ((lane >> 2) + 16 * k)) & 1ull) base[k * WAVE + lane] = z4;
-        } else if (vis) {
-            float4* ga = reinterpret_cast<float4*>(a.grad_acc + (size_t)idx * GRAD_FLOATS);
-            ga[0] = z4; ga[1] = z4; ga[2] = z4; ga[3] = z4;
-        }
-    }
+    // (The gradient lines of the accumulator are NOT cleared here: this kernel runs at the copy ceiling, where their 64 bytes
+    //  per Gaussian cost 17 us at 2 M.  The blend forward of the render call that follows clears them while the memory
+    //  system is mostly idle -- blend.hip, through a.prepare.)
 }
 
 int launch_preprocess_forward(const mgs_camera& cam, int P, const float* means3D, const float* shs,
@@ -382,6 +369,7 @@ int launch_preprocess_forward(const mgs_camera& cam, int P, const float* means3D
     a.V = cam.viewmatrix; a.PM = cam.projmatrix; a.campos = cam.campos;
     a.rec = g.rec; a.depth_key = g.depth_key;
     a.grad_acc = prepare_grad_acc;
+    a.prepare = g.prepare;
     a.rot_aligned16 = rotations && ((size_t)rotations % 16 == 0);
     a.clamped = g.clamped; a.rect = g.rect; a.radii = radii;
     a.tanfovx = cam.tanfovx; a.tanfovy = cam.tanfovy;

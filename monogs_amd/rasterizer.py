@@ -455,6 +455,25 @@ def debug_blend_stats(color: torch.Tensor) -> dict:
                 active_le2=v[5], active_le4=v[6], active_le8=v[7], group_streams=groups)
 
 
+def debug_blend_mask_stats(color: torch.Tensor) -> dict:
+    """Diagnostic: the survivor masks the blend forward that produced ``color`` left for its backward, against the cull the
+    backward would run for itself (``mgs_debug_blend_mask_stats``; call before ``backward()`` frees the saved scratch).
+    Synchronises."""
+    fn = color.grad_fn
+    if fn is None or not hasattr(fn, "raster_settings"):
+        raise RuntimeError("debug_blend_mask_stats needs the colour image of a differentiable rasteriser forward")
+    lib = _lib.load()
+    means3D, _, _, _, _, _, _, _, arena, binning = fn.saved_tensors
+    out = torch.zeros(4, dtype=torch.int64, device=means3D.device)       # MGS_BLEND_MASK_STATS_WORDS
+    with _device_guard(means3D.device):
+        _lib.check(lib.mgs_debug_blend_mask_stats(C.byref(fn.cam), means3D.shape[0], fn.num_rendered,
+                                                  arena.data_ptr() + fn.geom_off, binning.data_ptr(),
+                                                  arena.data_ptr() + fn.img_off, out.data_ptr(), _stream()),
+                   "mgs_debug_blend_mask_stats")
+    v = out.tolist()
+    return dict(steps=v[0], own_cull=v[1], forward_masks=v[2], missing=v[3])
+
+
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                         theta, rho, raster_settings):
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
