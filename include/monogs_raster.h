@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define MGS_ABI_VERSION 13
+#define MGS_ABI_VERSION 14
 #define MGS_TILE 16 /* tile edge in pixels; ranges are per 16x16 tile */
 
 /* GaussianRasterizationSettings, minus `prefiltered` / `debug` which are call flags
@@ -482,6 +482,62 @@ int mgs_activate_backward(int32_t P, int32_t scale_dim, const float* rot_raw, co
  * be one of the sources): the gradients that the N keyframe renders of a mapping window return for the same map tensor,
  * summed in ONE launch instead of the autograd engine's N - 1 pairwise adds per tensor (monogs_amd.window.fan_out). */
 int mgs_sum_buffers(int32_t n_src, const float* const* src, float* dst, uint64_t count, void* stream);
+
+/* ---- Keyframe selection and window management on the device (ABI v14) ----------------------------------------
+ * The three quantities /root/reference/utils/slam_tracker.py:192-284,412-452 decides from, and the decision, without a host
+ * synchronisation: every call is stream-ordered, keeps no state between calls, assumes nothing about the contents of its
+ * scratch or outputs on entry and can be captured in a hipGraph.  Counting is integer only: results are bitwise reproducible.
+ *
+ * mgs_masked_median: get_median_depth(depth, mask) (/root/reference/utils/slam_utils.py:149-157) with a free lower bound.
+ *   Element i counts when values[i] > lo and (mask == NULL or mask[i] != 0); mask is a FLOAT array (the reference passes the
+ *   opacity image to logical_and).  With c counted elements *out_median is the one of ascending rank (c - 1) / 2 -- torch's
+ *   lower median -- and *out_count = c.  c == 0 (n == 0 included) writes NaN and 0; the reference's torch.median raises on
+ *   an empty tensor instead.  Exact radix select on an order-preserving 32-bit key (any finite floats, lo = -inf allowed),
+ *   three digit passes, six launches whatever the data.  NaN values are out of contract; 0 <= n < 2^32.
+ *   scratch: mgs_median_scratch_bytes(n) bytes of device memory (a pure function of n, monotone).
+ * mgs_covisibility: counts[k] = { |A and B_k|, |A or B_k|, |A|, |B_k| } (uint32[K][4]) for the current frame's set A and the
+ *   K <= 32 window keyframes' sets B_k.  A is given as EXACTLY ONE of cur_n_touched (int32[P], packed on the fly as > 0) and
+ *   cur_bits (ceil(P/64) words); the rows have the layout of mgs_window_stats' visibility_bits.  kf_bits / kf_words are HOST
+ *   arrays of K device pointers / row lengths in words: a row shorter than ceil(P/64) words is zero-extended (the map grew
+ *   since it was written), bits at or beyond P never count.  cur_bits_out (optional, ceil(P/64) words) receives the packed
+ *   current row with a zero tail, ready to be kept as that frame's row if it becomes a keyframe.  K == 0 or P == 0 returns 0
+ *   without a launch.  One memset node + one launch.
+ * mgs_keyframe_decide: one wave.  poses: HOST array of 2 (K + 1) device pointers R[3,3] (row-major), T[3] (world->camera),
+ *   the current frame first, then the K window keyframes, most recent first; counts as mgs_covisibility writes them for the
+ *   same order; median: device float (mgs_masked_median's result).  With t(.) the translation of a 4x4 matrix:
+ *     IoU = |A and B_0| / |A or B_0| (float32),  d = || t(T_cur T_0^-1) ||
+ *     create = !check_overlap ? true : K < window_size ? IoU < kf_overlap
+ *              : (IoU < kf_overlap && d > kf_min_translation * median) || d > kf_translation * median
+ *     create_kf = create && frames_since_last_kf >= kf_interval
+ *   Eviction is computed as if the frame were added: new list = [cur] + window.  For the positions i >= n_dont_touch,
+ *   r_i = |A and B_i| / min(|A|, |B_i|); every r_i <= (window_full ? kf_cutoff : 0.4) is a candidate and only the LAST one
+ *   (largest i) is removed.  If the list is then still longer than window_size, of the remaining i >= n_dont_touch the first
+ *   maximum of  sqrt(|| t(T_i T_cur^-1) ||) * sum_{j >= n_dont_touch, j != i} 1 / (|| t(T_i T_j^-1) || + 1e-6)  is removed.
+ *   A zero denominator gives NaN, NaN compares false: nothing is created or removed by it.
+ *   out[8] (uint32) = { create_kf, removed_by_cutoff, removed_by_size, IoU bits, d bits, median bits, 0, 0 }; the removed
+ *   slots are positions in the new list, (uint32)-1 = none.  1 <= K <= 32, window_size >= 1, n_dont_touch >= 1.
+ * Argument errors of all three return 1 with a message, before anything is launched. */
+typedef struct MgsKeyframeParams {
+    int32_t K;                     /* keyframes in the window */
+    int32_t window_size;
+    int32_t window_full;           /* the tracker's is_window_full */
+    int32_t check_overlap;         /* check_viewpoints_overlap */
+    int32_t kf_interval;
+    int32_t frames_since_last_kf;  /* cur_frame_idx - last_keyframe_idx */
+    float kf_translation;          /* 0.08 */
+    float kf_min_translation;      /* 0.05 */
+    float kf_overlap;              /* 0.9 */
+    float kf_cutoff;
+    int32_t n_dont_touch;          /* 2 */
+} MgsKeyframeParams;
+size_t mgs_median_scratch_bytes(uint64_t n);
+int mgs_masked_median(const float* values, const float* mask /* [n] or NULL */, uint64_t n, float lo, void* scratch,
+                      float* out_median, uint32_t* out_count, void* stream);
+int mgs_covisibility(int32_t P, const int32_t* cur_n_touched, const uint64_t* cur_bits, int32_t K,
+                     const uint64_t* const* kf_bits, const uint64_t* kf_words, uint64_t* cur_bits_out,
+                     uint32_t* counts /* [K][4] */, void* stream);
+int mgs_keyframe_decide(const MgsKeyframeParams* params, const uint32_t* counts, const float* median,
+                        const float* const* poses, uint32_t* out /* [8] */, void* stream);
 
 #ifdef __cplusplus
 }

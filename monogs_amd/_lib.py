@@ -11,7 +11,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MGS_LIB_PATH") or os.path.join(_HERE, "lib", "libmonogs_raster.so")   # (override: kernel experiments)
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 c_float_p = C.c_void_p   # device pointers travel as integers (tensor.data_ptr())
 
@@ -33,6 +33,13 @@ class MgsTiming(C.Structure):
 
     def as_dict(self):
         return {n: float(getattr(self, n)) for n, _ in self._fields_}
+
+
+class MgsKeyframeParams(C.Structure):
+    _fields_ = [("K", C.c_int32), ("window_size", C.c_int32), ("window_full", C.c_int32), ("check_overlap", C.c_int32),
+                ("kf_interval", C.c_int32), ("frames_since_last_kf", C.c_int32),
+                ("kf_translation", C.c_float), ("kf_min_translation", C.c_float), ("kf_overlap", C.c_float),
+                ("kf_cutoff", C.c_float), ("n_dont_touch", C.c_int32)]
 
 
 # symbol -> (restype, argtypes); exactly the declarations of include/monogs_raster.h
@@ -93,6 +100,12 @@ SIGNATURES = {
     "mgs_activate_backward": (C.c_int, [C.c_int32, C.c_int32] + [C.c_void_p] * 10),
     "mgs_knn_scratch_bytes": (C.c_size_t, [C.c_int32]),
     "mgs_dist2_knn": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mgs_median_scratch_bytes": (C.c_size_t, [C.c_uint64]),
+    "mgs_masked_median": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_float] + [C.c_void_p] * 4),
+    "mgs_covisibility": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
+                                   C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mgs_keyframe_decide": (C.c_int, [C.POINTER(MgsKeyframeParams), C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p,
+                                      C.c_void_p]),
 }
 
 _lib = None

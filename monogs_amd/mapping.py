@@ -543,6 +543,21 @@ class WindowMapper:
             out[kf_ids[k]] = W.unpack_bits(words.view(torch.uint8), p.P)
         self.occ_aware_visibility = out
 
+    def packed_visibility(self) -> Optional[Dict[int, torch.Tensor]]:
+        """Read-only: the rows of ``occ_aware_visibility`` as the statistics launch of the LAST iteration packed them
+        (kf id -> int64[ceil(P/64)], bit i of word w = ``n_touched[64 w + i] > 0``), views of the plan's buffer, nothing
+        unpacked -- what ``monogs_amd.keyframe_window.KeyframeWindow.set_visibility`` and ``mgs_covisibility`` consume.
+        None when those rows no longer describe the map (no plan, or map surgery changed its size since)."""
+        p = self._plan
+        kf_ids = list(self.occ_aware_visibility)
+        if p is None or len(kf_ids) != p.n or p.P != len(self.gmap):
+            return None
+        out = {}
+        for k, kf in enumerate(kf_ids):
+            src = p.bits if not self.sharded else p.gout[k % self.world, (p.P + 1) // 2:].view(p.rows, p.words)
+            out[kf] = src[k // self.world]
+        return out
+
     # ---- one call = Mapper.optimize_map(cur_kf_list, prune, iters) ------------------------------------------------------
     def optimize_map(self, viewpoints: Sequence, kf_ids: Optional[Sequence[int]] = None, prune: bool = False,
                      iters: int = 1, init: bool = False) -> bool:

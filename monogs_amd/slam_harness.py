@@ -480,7 +480,8 @@ def run_slam(n_frames=12, intrinsics="fr3_office", tracking_itr_num=100, mapping
              kf_interval=4, init_itr_num=300, n_gaussians=60000, device="cuda:0", log=None,
              init_downsample=8, kf_downsample=16, point_size=1.0, graph_tracking=False, graph_mapping=False,
              track_lookahead=1, map_surgery=False, reference_lrs=False, prune_after_mapping=None,
-             scene="cloud", reference_densify=False, eager_probe=0, exclusive_device=False):
+             scene="cloud", reference_densify=False, eager_probe=0, exclusive_device=False,
+             kf_selection="interval", check_viewpoints_overlap=False, kf_trace=None):
     """Returns a dict with tracking / mapping FPS, iterations and the trajectory error.
 
     Mapping runs through ``monogs_amd.mapping.WindowMapper`` -- the SAME ``optimize_map`` / ``initialize_map`` the sharded
@@ -498,7 +499,16 @@ def run_slam(n_frames=12, intrinsics="fr3_office", tracking_itr_num=100, mapping
     keyframe, scale^2 = dist2 x min(0.05, 0.01 x median depth) (/root/reference/gaussian_splatting/scene/gaussian_model.py:166-178)
     -- instead of ``init_downsample`` / ``kf_downsample`` / ``point_size``.
     ``eager_probe`` > 0: after the run, that many tracking iterations of the UNMODIFIED caller loop
-    (/root/reference/utils/slam_tracker.py:138-176) against the final map, timed (``eager_tracking`` in the result)."""
+    (/root/reference/utils/slam_tracker.py:138-176) against the final map, timed (``eager_tracking`` in the result).
+    ``kf_selection``: "interval" (default) = every ``kf_interval``-th frame is a keyframe and the second-oldest leaves a full
+    window; "overlap" = the tracker's own decision (/root/reference/utils/slam_tracker.py:412-452, ``add_to_window``) through
+    ``monogs_amd.keyframe_window.KeyframeWindow``: three launches and one read-back per tracked frame, the window handed to
+    the mapper most recent first as the reference does, ``check_viewpoints_overlap`` as the tracker's flag (False in the
+    fork: every ``kf_interval``-th frame, evictions by overlap and camera distance); adds ``keyframes_selected``,
+    ``evicted_by_cutoff`` and ``evicted_by_size`` to the result.  ``kf_trace``: a list that receives, per tracked frame, CPU
+    copies of what the decision was made from and the decision (tests)."""
+    if kf_selection not in ("interval", "overlap"):
+        raise ValueError('kf_selection must be "interval" or "overlap"')
     from .gaussian_map import REFERENCE_LRS, REFERENCE_LR_SCHEDULE
     from .mapping import WindowMapper
     if prune_after_mapping is None:
@@ -520,6 +530,20 @@ def run_slam(n_frames=12, intrinsics="fr3_office", tracking_itr_num=100, mapping
     mapper.map_surgery = bool(map_surgery)
     mapper.time_replays = True
     window: List[Viewpoint] = []
+    kfw = None
+    if kf_selection == "overlap":
+        from .keyframe_window import KeyframeWindow, unpack_visibility
+        kfw = KeyframeWindow(window_size, check_viewpoints_overlap=check_viewpoints_overlap, kf_interval=kf_interval)
+        stats_kf = dict(keyframes_selected=0, evicted_by_cutoff=0, evicted_by_size=0)
+
+    def sync_visibility():
+        """The mapper's visibility rows of the window's keyframes, packed as its statistics launch left them."""
+        rows = mapper.packed_visibility()
+        if rows is None:                      # map surgery changed the map since: the mapper's (pruned) bool rows
+            rows = mapper.occ_aware_visibility
+        for k, r in rows.items():
+            if k in kfw.cur_kf_list:
+                kfw.set_visibility(k, r)
     per_frame, map_loss, window_sizes = [], [], []      # (frame, tracking iterations); (first, last) mapping loss per call
     size_trace = []                                     # (frame, Gaussians in the map after that keyframe's mapping)
     stats = dict(kf_extend_s=0.0, track_capture_s=0.0, track_s=0.0, track_iters=0, tracked=0, map_s=0.0, map_iters=0,
@@ -561,6 +585,9 @@ def run_slam(n_frames=12, intrinsics="fr3_office", tracking_itr_num=100, mapping
             window.append(vp)
             map_window(init_itr_num, init=True)
             size_trace.append((0, len(gmap)))
+            if kfw is not None:
+                kfw.bootstrap(vp.frame_idx, vp)
+                sync_visibility()
             sync(); stats["map_s"] += time.perf_counter() - t0
             stats["keyframes"] += 1
             continue
@@ -593,17 +620,44 @@ def run_slam(n_frames=12, intrinsics="fr3_office", tracking_itr_num=100, mapping
         for p in gmap.params():
             p.grad = None
         # ---- keyframe + mapping
-        if i % kf_interval == 0:
+        if kfw is not None:
             sync(); t0 = time.perf_counter()
             with torch.no_grad():
                 pkg = _render(vp, intr, gmap, bg)
+            if kf_trace is not None:
+                P = int(pkg["n_touched"].numel())
+                snap = dict(frame=i, window_before=list(kfw.cur_kf_list), is_window_full=kfw.is_window_full,
+                            n_touched=pkg["n_touched"].cpu(), depth=pkg["depth"].cpu(), opacity=pkg["opacity"].cpu(),
+                            visibility={k: unpack_visibility(kfw.visibility[k], P).cpu() for k in kfw.cur_kf_list},
+                            poses={k: (v.R.detach().cpu().clone(), v.T.detach().cpu().clone())
+                                   for k, v in [(i, vp)] + [(k, kfw.viewpoints[k]) for k in kfw.cur_kf_list]})
+            dec = kfw.observe(vp.frame_idx, vp, pkg)
+            if kf_trace is not None:
+                kf_trace.append(dict(snap, decision=dec, record=kfw.last_record, window_after=list(kfw.cur_kf_list)))
+            is_kf = dec.create_kf
+            if is_kf:
+                stats_kf["keyframes_selected"] += 1
+                stats_kf["evicted_by_cutoff"] += int(kfw.last_record.removed_by_cutoff >= 0)
+                stats_kf["evicted_by_size"] += int(kfw.last_record.removed_by_size >= 0)
+        else:
+            is_kf = i % kf_interval == 0
+            if is_kf:
+                sync(); t0 = time.perf_counter()
+                with torch.no_grad():
+                    pkg = _render(vp, intr, gmap, bg)
+        if is_kf:
             sync(); te0 = time.perf_counter()
             gmap.extend_from_frame(vp, intr, render_opacity=pkg["opacity"], render_depth=pkg["depth"], **extend_kw(False))
             sync(); stats["kf_extend_s"] += time.perf_counter() - te0
-            window.append(vp)
-            if len(window) > window_size:
-                window.pop(1)
+            if kfw is not None:
+                window[:] = [kfw.viewpoints[k] for k in kfw.cur_kf_list]
+            else:
+                window.append(vp)
+                if len(window) > window_size:
+                    window.pop(1)
             map_window(mapping_itr_num)
+            if kfw is not None:
+                sync_visibility()
             sync(); stats["map_s"] += time.perf_counter() - t0
             stats["keyframes"] += 1
             size_trace.append((i, len(gmap)))
@@ -622,6 +676,9 @@ def run_slam(n_frames=12, intrinsics="fr3_office", tracking_itr_num=100, mapping
     err = torch.stack([(-(f.R.t() @ f.T) + (f.R_gt.t() @ f.T_gt)).norm() for f in frames[1:]])
     ms = mapper.stats
     out = dict(stats)
+    if kfw is not None:
+        out.update(stats_kf, kf_selection=kf_selection, check_viewpoints_overlap=bool(check_viewpoints_overlap),
+                   final_window=list(kfw.cur_kf_list))
     sl = gmap.surgery_log
     out["surgery"] = dict(
         densify_and_prune_calls=len(sl), cloned=sum(e["cloned"] for e in sl), split_net=sum(e["split_net"] for e in sl),

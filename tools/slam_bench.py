@@ -42,6 +42,11 @@ if __name__ == "__main__":
                          "300 iterations per keyframe, window 30")
     ap.add_argument("--lookahead", type=int, default=1, choices=[0, 1],
                     help="with --graph: read the convergence flag of tracking iteration n-1 while n runs")
+    ap.add_argument("--kf-selection", default="interval", choices=["interval", "overlap"],
+                    help="overlap: keyframes and evictions decided on the device (monogs_amd.keyframe_window) instead of every "
+                         "--kf-interval-th frame")
+    ap.add_argument("--check-overlap", action="store_true",
+                    help="with --kf-selection overlap: the tracker's check_viewpoints_overlap (upstream MonoGS; False in the fork)")
     a = ap.parse_args()
     from monogs_amd.slam_harness import run_slam
     cfg = dict(CONFIGS[a.config])
@@ -56,7 +61,7 @@ if __name__ == "__main__":
     out = run_slam(n_frames=a.frames, init_itr_num=init_iters, n_gaussians=a.gaussians, graph_tracking=a.graph,
                    graph_mapping=a.graph and not a.eager_mapping, track_lookahead=a.lookahead, map_surgery=a.surgery,
                    reference_lrs=a.reference_lrs, scene="room" if a.room else "cloud", reference_densify=a.reference_densify,
-                   eager_probe=a.eager_probe, log=lambda s: print("[slam]", s, file=sys.stderr, flush=True), **cfg)
+                   eager_probe=a.eager_probe, kf_selection=a.kf_selection, check_viewpoints_overlap=a.check_overlap, log=lambda s: print("[slam]", s, file=sys.stderr, flush=True), **cfg)
     out["workload"] = f"synthetic {a.config}-like sequence, {a.frames} frames" + (" (fork's hard-coded run configuration)" if a.fork else "")
     for k in ("poses", "camera_centers", "camera_centers_gt"):      # tensors: not JSON
         out.pop(k, None)
