@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define MGS_ABI_VERSION 14
+#define MGS_ABI_VERSION 15
 #define MGS_TILE 16 /* tile edge in pixels; ranges are per 16x16 tile */
 
 /* GaussianRasterizationSettings, minus `prefiltered` / `debug` which are call flags
@@ -538,6 +538,28 @@ int mgs_covisibility(int32_t P, const int32_t* cur_n_touched, const uint64_t* cu
                      uint32_t* counts /* [K][4] */, void* stream);
 int mgs_keyframe_decide(const MgsKeyframeParams* params, const uint32_t* counts, const float* median,
                         const float* const* poses, uint32_t* out /* [8] */, void* stream);
+
+/* ---- Image metrics of a rendered frame (ABI v15) -------------------------------------------------------------
+ * What eval_rendering (/root/reference/utils/eval_utils.py:169-183) computes per evaluated frame, in ONE pass over the render
+ * and its ground truth (both [3,H,W]) and a one-workgroup finalize:
+ *   clamped_out = clamp(render, 0, 1)                                         (:169)
+ *   u8_out[y][x][c] = (uint8)(clamped_out[c][y][x] * 255.0f), a truncation    (:172; [H,W,3], may be NULL)
+ *   over the elements with gt > 0, elementwise over the three planes (:180-182): mse = mean (clamped_out - gt)^2,
+ *   psnr = 20 log10(1 / sqrt(mse))   (/root/reference/gaussian_splatting/utils/image_utils.py:19-21)
+ *   row_out (device float[4]) = { psnr, <not touched>, mse, count }
+ * Slot 1 is the caller's: the SSIM of :183 is mgs_ssim_forward(3, width, height, 1, 0, MGS_SSIM_C1, MGS_SSIM_C2, clamped_out,
+ * gt, ..., row_out + 1) on the same stream.  count == 0 writes NaN for mse and psnr (the mgs_masked_median convention; the
+ * reference's mean of an empty tensor is NaN as well); mse == 0 gives psnr = +inf.  The sums are carried in double through
+ * per-workgroup partials added in a fixed order: no atomics, no clear launch, bitwise reproducible, mse within 1e-6 relative of
+ * a float64 evaluation; count is exact (stored as float: up to 2^24 elements).  16-byte accesses when the three float bases
+ * are 16-byte aligned, u8_out 4-byte aligned and width x height a multiple of 4, a scalar path otherwise.
+ * scratch: mgs_metrics_scratch_bytes(width, height) bytes, 8-byte aligned, contents irrelevant on entry.
+ * A NULL pointer (other than u8_out), width < 1 or height < 1 returns 1 with a message, before anything is launched;
+ * 3 x width x height must stay below 2^31. */
+size_t mgs_metrics_scratch_bytes(int32_t width, int32_t height);
+int mgs_image_metrics(int32_t width, int32_t height, const float* render /* [3,H,W] */, const float* gt /* [3,H,W] */,
+                      float* clamped_out /* [3,H,W] */, uint8_t* u8_out /* [H,W,3] or NULL */, void* scratch,
+                      float* row_out /* device float[4] */, void* stream);
 
 #ifdef __cplusplus
 }

@@ -11,7 +11,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MGS_LIB_PATH") or os.path.join(_HERE, "lib", "libmonogs_raster.so")   # (override: kernel experiments)
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 c_float_p = C.c_void_p   # device pointers travel as integers (tensor.data_ptr())
 
@@ -106,6 +106,8 @@ SIGNATURES = {
                                    C.c_void_p, C.c_void_p, C.c_void_p]),
     "mgs_keyframe_decide": (C.c_int, [C.POINTER(MgsKeyframeParams), C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p,
                                       C.c_void_p]),
+    "mgs_metrics_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "mgs_image_metrics": (C.c_int, [C.c_int32, C.c_int32] + [C.c_void_p] * 7),
 }
 
 _lib = None

@@ -81,6 +81,13 @@ def sync_free_enabled() -> bool:
     return bool(_sync_free["enabled"])
 
 
+def reserve_capacity(P: int, W: int, H: int, R: int) -> None:
+    """Set the capacity hint of shape ``(P, W, H)`` to ``R`` instances: the next capacity-mode forwards of that shape (a
+    hipGraph capture among them) size their binning scratch from it (x headroom).  For a captured iteration that serves
+    several cameras: an exact forward overwrites the hint with ITS count, so measure every camera and reserve the maximum."""
+    _remember_hint((int(P), int(W), int(H)), int(R))
+
+
 # MGS_FLAG_EXCLUSIVE_DEVICE (include/monogs_raster.h): the caller vouches that nothing else runs on the device beside the
 # forwards issued while this is on -- one process, one stream.  Off by default: MonoGS shares one GPU between three processes.
 _call_flags = {"exclusive": False}
@@ -147,6 +154,16 @@ def check_overflow() -> bool:
 def clear_graph_flags():
     """Forget the overflow flags of captured graphs (call when those graphs are destroyed)."""
     _State.graph.clear()
+
+
+def accumulate_graph_flag(sticky: torch.Tensor) -> None:
+    """Inside a capture, right after a forward: ``sticky |= status`` (device int32[1]) as a captured op, and ``check_overflow()``
+    reads ``sticky`` in place of that forward's own word.  A forward REWRITES its status word, so a graph that is replayed many
+    times between two checks shows the last replay's only; with this the check sees an overflow (or a sort timeout) of any
+    replay since the caller last zeroed ``sticky`` -- what a graph that serves cameras of different instance counts needs."""
+    key, flag = _State.graph[-1]
+    sticky.bitwise_or_(flag)
+    _State.graph[-1] = (key, sticky)
 
 
 # ---- optional per-stage timing (bench.py) --------------------------------------------------

@@ -481,7 +481,7 @@ def run_slam(n_frames=12, intrinsics="fr3_office", tracking_itr_num=100, mapping
              init_downsample=8, kf_downsample=16, point_size=1.0, graph_tracking=False, graph_mapping=False,
              track_lookahead=1, map_surgery=False, reference_lrs=False, prune_after_mapping=None,
              scene="cloud", reference_densify=False, eager_probe=0, exclusive_device=False,
-             kf_selection="interval", check_viewpoints_overlap=False, kf_trace=None):
+             kf_selection="interval", check_viewpoints_overlap=False, kf_trace=None, refine_iters=0, eval_render=False):
     """Returns a dict with tracking / mapping FPS, iterations and the trajectory error.
 
     Mapping runs through ``monogs_amd.mapping.WindowMapper`` -- the SAME ``optimize_map`` / ``initialize_map`` the sharded
@@ -506,7 +506,13 @@ def run_slam(n_frames=12, intrinsics="fr3_office", tracking_itr_num=100, mapping
     the mapper most recent first as the reference does, ``check_viewpoints_overlap`` as the tracker's flag (False in the
     fork: every ``kf_interval``-th frame, evictions by overlap and camera distance); adds ``keyframes_selected``,
     ``evicted_by_cutoff`` and ``evicted_by_size`` to the result.  ``kf_trace``: a list that receives, per tracked frame, CPU
-    copies of what the decision was made from and the decision (tests)."""
+    copies of what the decision was made from and the decision (tests).
+    ``eval_render``: what the reference reports at the end of a run (/root/reference/slam.py, utils/eval_utils.py) --
+    ``eval = {"before_opt", "final"}`` from ``monogs_amd.evaluation.eval_rendering`` (PSNR over gt > 0 and SSIM on every fifth
+    non-keyframe; "final" is taken after the refinement when there is one) and ``ate`` from ``eval_ate`` over the keyframes
+    (unaligned, as the reference computes it).  ``refine_iters`` > 0: that many
+    iterations of ``Mapper.refinement`` over all keyframes through ``monogs_amd.refinement.Refiner`` (captured when
+    ``graph_mapping``); adds ``refinement`` (the driver's dict + ``it_per_s``).  Both default to off: nothing changes."""
     if kf_selection not in ("interval", "overlap"):
         raise ValueError('kf_selection must be "interval" or "overlap"')
     from .gaussian_map import REFERENCE_LRS, REFERENCE_LR_SCHEDULE
@@ -577,8 +583,10 @@ def run_slam(n_frames=12, intrinsics="fr3_office", tracking_itr_num=100, mapping
 
     tgraph = None
     loss = torch.zeros(())
+    kf_list: List[int] = []                             # every keyframe of the run (the reference's viewpoints_dict / kf_indices)
     for i, vp in enumerate(frames):
         if i == 0:
+            kf_list.append(0)
             vp.update_RT(vp.R_gt, vp.T_gt)
             sync(); t0 = time.perf_counter()
             gmap.extend_from_frame(vp, intr, init=True, **extend_kw(True))
@@ -660,6 +668,7 @@ def run_slam(n_frames=12, intrinsics="fr3_office", tracking_itr_num=100, mapping
                 sync_visibility()
             sync(); stats["map_s"] += time.perf_counter() - t0
             stats["keyframes"] += 1
+            kf_list.append(i)
             size_trace.append((i, len(gmap)))
             if tgraph is not None:                   # the map changed: the captured tracking graph is stale
                 tgraph.close()
@@ -673,9 +682,31 @@ def run_slam(n_frames=12, intrinsics="fr3_office", tracking_itr_num=100, mapping
 
     if graph_tracking and tgraph is not None:
         tgraph.close()
+    extra = {}
+    if eval_render or refine_iters:
+        from .evaluation import eval_ate, eval_rendering
+        from .refinement import Refiner
+        mapper._drop_plan()             # (its captured graphs and their overflow flags go before the refinement captures its own)
+        for p in gmap.params():
+            p.grad = None
+        if eval_render:
+            extra["eval"] = dict(before_opt=eval_rendering(frames, gmap, intr, bg, kf_list, tag="before_opt"))
+        if refine_iters:
+            refiner = Refiner(gmap, intr, bg, use_graph=graph_mapping)
+            sync(); t0 = time.perf_counter()
+            res = refiner.refine([frames[k] for k in kf_list], iters=int(refine_iters))
+            sync()
+            res["it_per_s"] = int(refine_iters) / max(time.perf_counter() - t0, 1e-9)
+            refiner.close()
+            extra["refinement"] = res
+        if eval_render:
+            extra["eval"]["final"] = (eval_rendering(frames, gmap, intr, bg, kf_list, tag="final") if refine_iters
+                                      else extra["eval"]["before_opt"])
+            extra["ate"] = eval_ate(frames, kf_ids=kf_list)
     err = torch.stack([(-(f.R.t() @ f.T) + (f.R_gt.t() @ f.T_gt)).norm() for f in frames[1:]])
     ms = mapper.stats
     out = dict(stats)
+    out.update(extra)
     if kfw is not None:
         out.update(stats_kf, kf_selection=kf_selection, check_viewpoints_overlap=bool(check_viewpoints_overlap),
                    final_window=list(kfw.cur_kf_list))

@@ -47,6 +47,10 @@ if __name__ == "__main__":
                          "--kf-interval-th frame")
     ap.add_argument("--check-overlap", action="store_true",
                     help="with --kf-selection overlap: the tracker's check_viewpoints_overlap (upstream MonoGS; False in the fork)")
+    ap.add_argument("--refine", type=int, default=0, metavar="N",
+                    help="after the run: N iterations of the colour refinement (Mapper.refinement runs 26000), captured with --graph")
+    ap.add_argument("--eval", action="store_true",
+                    help="PSNR / SSIM on every fifth non-keyframe before and after the refinement, and the ATE statistics")
     a = ap.parse_args()
     from monogs_amd.slam_harness import run_slam
     cfg = dict(CONFIGS[a.config])
@@ -61,7 +65,8 @@ if __name__ == "__main__":
     out = run_slam(n_frames=a.frames, init_itr_num=init_iters, n_gaussians=a.gaussians, graph_tracking=a.graph,
                    graph_mapping=a.graph and not a.eager_mapping, track_lookahead=a.lookahead, map_surgery=a.surgery,
                    reference_lrs=a.reference_lrs, scene="room" if a.room else "cloud", reference_densify=a.reference_densify,
-                   eager_probe=a.eager_probe, kf_selection=a.kf_selection, check_viewpoints_overlap=a.check_overlap, log=lambda s: print("[slam]", s, file=sys.stderr, flush=True), **cfg)
+                   eager_probe=a.eager_probe, kf_selection=a.kf_selection, check_viewpoints_overlap=a.check_overlap,
+                   refine_iters=a.refine, eval_render=a.eval, log=lambda s: print("[slam]", s, file=sys.stderr, flush=True), **cfg)
     out["workload"] = f"synthetic {a.config}-like sequence, {a.frames} frames" + (" (fork's hard-coded run configuration)" if a.fork else "")
     for k in ("poses", "camera_centers", "camera_centers_gt"):      # tensors: not JSON
         out.pop(k, None)
