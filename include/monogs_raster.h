@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define MGS_ABI_VERSION 15
+#define MGS_ABI_VERSION 16
 #define MGS_TILE 16 /* tile edge in pixels; ranges are per 16x16 tile */
 
 /* GaussianRasterizationSettings, minus `prefiltered` / `debug` which are call flags
@@ -560,6 +560,68 @@ size_t mgs_metrics_scratch_bytes(int32_t width, int32_t height);
 int mgs_image_metrics(int32_t width, int32_t height, const float* render /* [3,H,W] */, const float* gt /* [3,H,W] */,
                       float* clamped_out /* [3,H,W] */, uint8_t* u8_out /* [H,W,3] or NULL */, void* scratch,
                       float* row_out /* device float[4] */, void* stream);
+
+/* ---- Frame ingest: from a decoded frame to what the tracker is handed (ABI v16) --------------------------------
+ * What MonocularDataset.__getitem__ (/root/reference/utils/dataset.py:410-508) and CameraExtrinsics.compute_grad_mask
+ * (/root/reference/utils/camera_utils.py:184-212 with utils/slam_utils.py:6-40) do per frame, stream-ordered on the caller's
+ * stream: no host synchronisation, no state between calls, nothing assumed about the contents of scratch or outputs on entry,
+ * capturable in a hipGraph as a linear chain of kernel nodes.
+ *
+ * mgs_grad_mask: compute_grad_mask of a float [3,H,W] image on the device.
+ *   gray = (r + g + b) / 3                                                                  (camera_utils.py:187)
+ *   gv, gh = the Scharr responses [[3,10,3],[0,0,0],[-3,-10,-3]] and [[3,0,-3],[10,0,-10],[3,0,-3]] of the grey image
+ *            reflect-padded by one pixel, both times 1/32                                   (slam_utils.py:6-23)
+ *   valid  = all nine padded neighbours have |gray| > eps                                   (slam_utils.py:26-40)
+ *   intensity = sqrt((gv valid)^2 + (gh valid)^2)  -> intensity_out (float [H,W], may be NULL)     (:190-192)
+ *   grad_mask_out (uint8 [H,W], 0/1) = intensity > __fmul_rn(median, edge_threshold), median the LOWER median of all
+ *            H W intensities (torch.median), found by mgs_masked_median with lo = -inf and no mask   (:211-212)
+ *   The reference fixes edge_threshold = 1.1 (MGS_EDGE_THRESHOLD) and eps = 0.01 (MGS_GRAD_EPS).  intensity is within 1e-6
+ *   absolute of a float64 evaluation for images in [0, 1].  Eight launches: one intensity, the median's six, one threshold.
+ *   scratch: mgs_grad_mask_scratch_bytes(width, height) bytes (pure, monotone in both), 16-byte aligned.
+ *   Needs width >= 2 and height >= 2 (reflect padding); 3 x width x height must stay below 2^31.
+ *
+ * mgs_frame_prepare: one preparation launch, then the eight of mgs_grad_mask on rgb_out: nine in all.
+ *   colour, no maps:  rgb_out[c][y][x] = float32(double(v) / 255.0), the reference's `image / 255.0` cast to float32
+ *            (dataset.py:460-465; the clamp to [0, 1] is then a no-op).
+ *   colour, with maps (map_x, map_y float [H][W], source coordinates per destination pixel, dataset.py:452-453): the 8-bit
+ *            pixel is first resampled as an 8-bit INTER_LINEAR remap with float maps and a constant-zero border does, in
+ *            integers: sx = round-half-even(32 map_x), ix = sx >> 5 (arithmetic: -0.5 gives -1), ax = sx & 31, likewise y;
+ *            weights (32-ax)(32-ay)32, ax(32-ay)32, (32-ax)ay 32, ax ay 32 (sum 2^15) on the taps (iy,ix), (iy,ix+1), (iy+1,ix),
+ *            (iy+1,ix+1); a tap outside the image contributes 0; out = (sum + 2^14) >> 15 per channel.  Bit-exact against an
+ *            integer restatement.  No map value whatsoever -- huge, infinite, NaN -- makes the kernel read outside the
+ *            source image: such pixels are 0.  cv2 is not available to this project: parity with cv2.remap is UNPINNED.
+ *   depth:   depth_out = float32(double(v) / depth_scale) (dataset.py:431,468).  Depth and segmentation are NOT remapped:
+ *            the reference undistorts the colour image only.
+ *   mask:    mask_out (uint8 [H,W]) = 1, except 0 where segmentation is given and bit `id` of masked_ids is set
+ *            (dataset.py:445-449).  Without segmentation the mask is all ones (the reference leaves `mask` unbound there).
+ *   16-byte accesses when every base given is 16-byte aligned and width is a multiple of 4, a scalar route otherwise (the
+ *   gradient-mask launches choose by rgb_out, grad_mask_out and intensity_out alone).
+ *   Refused with 1 and a message before anything is launched: a NULL required pointer (rgb_u8, rgb_out, mask_out,
+ *   grad_mask_out, scratch), only one of the two maps, depth_u16 without depth_out or the reverse, depth given with
+ *   depth_scale <= 0 or not finite, width or height < 2. */
+#define MGS_EDGE_THRESHOLD 1.1f
+#define MGS_GRAD_EPS 0.01f
+typedef struct MgsFramePrepare {
+    int32_t width, height;
+    const uint8_t* rgb_u8;        /* [H][W][3] */
+    const float* map_x;           /* [H][W] or NULL */
+    const float* map_y;           /* [H][W] or NULL: both or neither */
+    const uint16_t* depth_u16;    /* [H][W] or NULL */
+    double depth_scale;           /* read when depth_u16 is given */
+    const uint8_t* segmentation;  /* [H][W] ids or NULL */
+    uint32_t masked_ids[8];       /* bit (id & 31) of word (id >> 5) set: id is masked out */
+    float* rgb_out;               /* [3][H][W] */
+    float* depth_out;             /* [H][W], given exactly when depth_u16 is */
+    uint8_t* mask_out;            /* [H][W] */
+    uint8_t* grad_mask_out;       /* [H][W] */
+    float* intensity_out;         /* [H][W] or NULL */
+    float edge_threshold, eps;    /* MGS_EDGE_THRESHOLD, MGS_GRAD_EPS */
+    void* scratch;                /* mgs_grad_mask_scratch_bytes(width, height) bytes, 16-byte aligned */
+} MgsFramePrepare;
+size_t mgs_grad_mask_scratch_bytes(int32_t width, int32_t height);
+int mgs_grad_mask(int32_t width, int32_t height, const float* rgb /* [3,H,W] */, float edge_threshold, float eps,
+                  void* scratch, uint8_t* grad_mask_out /* [H,W] */, float* intensity_out /* [H,W] or NULL */, void* stream);
+int mgs_frame_prepare(const MgsFramePrepare* params, void* stream);
 
 #ifdef __cplusplus
 }

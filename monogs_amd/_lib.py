@@ -11,7 +11,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MGS_LIB_PATH") or os.path.join(_HERE, "lib", "libmonogs_raster.so")   # (override: kernel experiments)
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 c_float_p = C.c_void_p   # device pointers travel as integers (tensor.data_ptr())
 
@@ -40,6 +40,14 @@ class MgsKeyframeParams(C.Structure):
                 ("kf_interval", C.c_int32), ("frames_since_last_kf", C.c_int32),
                 ("kf_translation", C.c_float), ("kf_min_translation", C.c_float), ("kf_overlap", C.c_float),
                 ("kf_cutoff", C.c_float), ("n_dont_touch", C.c_int32)]
+
+
+class MgsFramePrepare(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("rgb_u8", C.c_void_p), ("map_x", C.c_void_p), ("map_y", C.c_void_p),
+                ("depth_u16", C.c_void_p), ("depth_scale", C.c_double), ("segmentation", C.c_void_p),
+                ("masked_ids", C.c_uint32 * 8), ("rgb_out", C.c_void_p), ("depth_out", C.c_void_p), ("mask_out", C.c_void_p),
+                ("grad_mask_out", C.c_void_p), ("intensity_out", C.c_void_p), ("edge_threshold", C.c_float), ("eps", C.c_float),
+                ("scratch", C.c_void_p)]
 
 
 # symbol -> (restype, argtypes); exactly the declarations of include/monogs_raster.h
@@ -108,6 +116,9 @@ SIGNATURES = {
                                       C.c_void_p]),
     "mgs_metrics_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "mgs_image_metrics": (C.c_int, [C.c_int32, C.c_int32] + [C.c_void_p] * 7),
+    "mgs_grad_mask_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "mgs_grad_mask": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_float, C.c_float] + [C.c_void_p] * 4),
+    "mgs_frame_prepare": (C.c_int, [C.POINTER(MgsFramePrepare), C.c_void_p]),
 }
 
 _lib = None

@@ -18,7 +18,8 @@ exactly as the reference does:
 The camera objects are duck-typed stand-ins for the reference's CameraIntrinsics / CameraExtrinsics
 (/root/reference/utils/camera_utils.py:8-79,82-221).  The datasets of configs 3-4 are not available offline; frames come
 from an opaque box room ray-cast analytically (``make_room_sequence``: what bench.py runs, survives the reference's
-pruning) or, historically, from a seeded cloud of Gaussians rendered by the same rasteriser (``make_sequence``).
+pruning) or, historically, from a seeded cloud of Gaussians rendered by the same rasteriser (``make_sequence``).  A sequence
+on disk comes in through ``run_slam(sequence=monogs_amd.dataset.dataset_frames(...))``.
 """
 from __future__ import annotations
 
@@ -65,14 +66,15 @@ def scharr_grad_mask(rgb: torch.Tensor, edge_threshold: float = 1.1, eps: float 
 
 
 class Viewpoint:
-    def __init__(self, idx, rgb, depth, device, gt_R=None, gt_T=None):
+    def __init__(self, idx, rgb, depth, device, gt_R=None, gt_T=None, mask=None, grad_mask=None):
         self.frame_idx, self.device = idx, device
         self.R = torch.eye(3, device=device)
         self.T = torch.zeros(3, device=device)
         self.R_gt, self.T_gt = gt_R, gt_T
         self.rgb, self.depth = rgb, depth
-        self.mask = torch.ones_like(depth, dtype=torch.bool)
-        self.grad_mask = scharr_grad_mask(rgb)
+        # (a dataset frame brings both from monogs_amd.frame_ingest; the synthetic generators bring neither)
+        self.mask = torch.ones_like(depth, dtype=torch.bool) if mask is None else mask
+        self.grad_mask = scharr_grad_mask(rgb) if grad_mask is None else grad_mask
         z = lambda n, v=0.0: torch.nn.Parameter(torch.full((n,), v, device=device))  # noqa: E731
         self.cam_rot_delta, self.cam_trans_delta = z(3), z(3)
         self.exposure_a, self.exposure_b = z(1), z(1)
@@ -481,7 +483,8 @@ def run_slam(n_frames=12, intrinsics="fr3_office", tracking_itr_num=100, mapping
              init_downsample=8, kf_downsample=16, point_size=1.0, graph_tracking=False, graph_mapping=False,
              track_lookahead=1, map_surgery=False, reference_lrs=False, prune_after_mapping=None,
              scene="cloud", reference_densify=False, eager_probe=0, exclusive_device=False,
-             kf_selection="interval", check_viewpoints_overlap=False, kf_trace=None, refine_iters=0, eval_render=False):
+             kf_selection="interval", check_viewpoints_overlap=False, kf_trace=None, refine_iters=0, eval_render=False,
+             sequence=None):
     """Returns a dict with tracking / mapping FPS, iterations and the trajectory error.
 
     Mapping runs through ``monogs_amd.mapping.WindowMapper`` -- the SAME ``optimize_map`` / ``initialize_map`` the sharded
@@ -512,14 +515,19 @@ def run_slam(n_frames=12, intrinsics="fr3_office", tracking_itr_num=100, mapping
     non-keyframe; "final" is taken after the refinement when there is one) and ``ate`` from ``eval_ate`` over the keyframes
     (unaligned, as the reference computes it).  ``refine_iters`` > 0: that many
     iterations of ``Mapper.refinement`` over all keyframes through ``monogs_amd.refinement.Refiner`` (captured when
-    ``graph_mapping``); adds ``refinement`` (the driver's dict + ``it_per_s``).  Both default to off: nothing changes."""
+    ``graph_mapping``); adds ``refinement`` (the driver's dict + ``it_per_s``).  Both default to off: nothing changes.
+    ``sequence``: a ``(frames, intr)`` pair, e.g. from ``monogs_amd.dataset.dataset_frames``, that replaces the synthetic
+    generator; ``n_frames`` is then its length and ``scene`` / ``intrinsics`` / ``n_gaussians`` are ignored."""
     if kf_selection not in ("interval", "overlap"):
         raise ValueError('kf_selection must be "interval" or "overlap"')
     from .gaussian_map import REFERENCE_LRS, REFERENCE_LR_SCHEDULE
     from .mapping import WindowMapper
     if prune_after_mapping is None:
         prune_after_mapping = bool(map_surgery)
-    if scene == "room":
+    if sequence is not None:
+        frames, intr = sequence
+        n_frames = len(frames)
+    elif scene == "room":
         frames, intr = make_room_sequence(n_frames, intrinsics, device=device)
     else:
         frames, intr = make_sequence(n_frames, intrinsics, n_gaussians, device=device)

@@ -3,6 +3,8 @@
 stand-in; the TUM / Replica sequences are not available offline).  Prints one JSON line.
   python tools/slam_bench.py --config tum      # 640x480, tracking 100 / mapping 150 / window 8 / kf 5
   python tools/slam_bench.py --config replica  # 1200x680, tracking 100 / mapping 150 / window 10 / kf 4
+  python tools/slam_bench.py --config tum --dataset CONFIG.yaml --frames 200 [--stride 2]
+      # a TUM / Replica sequence on disk (monogs_amd.dataset): size and intrinsics from the YAML, iteration counts from --config
 """
 import argparse
 import json
@@ -51,6 +53,10 @@ if __name__ == "__main__":
                     help="after the run: N iterations of the colour refinement (Mapper.refinement runs 26000), captured with --graph")
     ap.add_argument("--eval", action="store_true",
                     help="PSNR / SSIM on every fifth non-keyframe before and after the refinement, and the ATE statistics")
+    ap.add_argument("--dataset", default=None, metavar="CONFIG.yaml",
+                    help="run on the TUM / Replica sequence this reference-style YAML names (Dataset.type, dataset_path, "
+                         "Calibration) instead of a synthetic one: --frames frames from the first, every --stride-th")
+    ap.add_argument("--stride", type=int, default=1, help="with --dataset: take every N-th frame")
     a = ap.parse_args()
     from monogs_amd.slam_harness import run_slam
     cfg = dict(CONFIGS[a.config])
@@ -62,12 +68,18 @@ if __name__ == "__main__":
                  ("kf_interval", a.kf_interval)):
         if v is not None:
             cfg[k] = v
-    out = run_slam(n_frames=a.frames, init_itr_num=init_iters, n_gaussians=a.gaussians, graph_tracking=a.graph,
+    sequence = None
+    if a.dataset:
+        from monogs_amd.dataset import dataset_frames, load_dataset
+        sequence = dataset_frames(load_dataset(a.dataset, device="cuda:0"), a.frames, device="cuda:0", stride=a.stride)
+        cfg.pop("intrinsics")                           # (the YAML's calibration is the camera)
+    out = run_slam(sequence=sequence, n_frames=a.frames, init_itr_num=init_iters, n_gaussians=a.gaussians, graph_tracking=a.graph,
                    graph_mapping=a.graph and not a.eager_mapping, track_lookahead=a.lookahead, map_surgery=a.surgery,
                    reference_lrs=a.reference_lrs, scene="room" if a.room else "cloud", reference_densify=a.reference_densify,
                    eager_probe=a.eager_probe, kf_selection=a.kf_selection, check_viewpoints_overlap=a.check_overlap,
                    refine_iters=a.refine, eval_render=a.eval, log=lambda s: print("[slam]", s, file=sys.stderr, flush=True), **cfg)
-    out["workload"] = f"synthetic {a.config}-like sequence, {a.frames} frames" + (" (fork's hard-coded run configuration)" if a.fork else "")
+    what = f"{a.dataset}, every {a.stride}. frame" if a.dataset else f"synthetic {a.config}-like sequence"
+    out["workload"] = f"{what}, {a.frames} frames" + (" (fork's hard-coded run configuration)" if a.fork else "")
     for k in ("poses", "camera_centers", "camera_centers_gt"):      # tensors: not JSON
         out.pop(k, None)
     print(json.dumps(out))
