@@ -32,7 +32,6 @@ all-gathers them before the map is handed on (:553-556).
 from __future__ import annotations
 
 import contextlib
-import math
 import time
 from typing import Dict, List, Optional, Sequence
 
@@ -43,8 +42,8 @@ from . import _lib, camera as cam, fused_losses, rasterizer as _rast, window as 
 from .gaussian_map import GaussianMap
 from .gaussian_optim import activate, fan_out, window_stats
 from .pose_optim import PoseAdam
-from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, _device_guard, _stream
-from .renderer import render
+from .rasterizer import GaussianRasterizer, _device_guard, _stream
+from .renderer import raster_settings, render
 
 BUCKET_COLS = 16          # floats per Gaussian in the exchange bucket (see the module docstring)
 _GRAD_COLS = 14
@@ -88,6 +87,7 @@ class _Plan:
         self.radii: List = []
         self.n_touched: List = []
         self.graphs = None              # (front, back) or (whole,) once captured
+        self.graph_flags = None         # owner of the status words of every forward those graphs captured
         self.iter_dev = torch.zeros(1, dtype=torch.int32, device=dev)
         # pipelined exchange (WindowMapper.exchange = "per_keyframe"): one gradient bucket per owned keyframe, reduced on
         # its own while the next keyframe renders; `slot_graphs`: one captured (render, loss, backward) per owned keyframe
@@ -96,6 +96,13 @@ class _Plan:
         self.pipelined = bool(mapper.sharded and mapper.exchange == "per_keyframe" and self.rows > 1)
         self.slot_flat = [torch.zeros(P * _GRAD_COLS, **f32) for _ in range(self.rows)] if self.pipelined else []
         self.slot_graphs = None
+
+    def drop_graphs(self):
+        """The captured graphs go, and with them the status words of their forwards: check_overflow() stops reading them."""
+        self.graphs = self.slot_graphs = None
+        if self.graph_flags is not None:
+            self.graph_flags.release()
+        self.graph_flags = None
 
     def grad_view(self, col0: int, cols: int):
         P = self.P
@@ -206,8 +213,8 @@ class WindowMapper:
         return p
 
     def _drop_plan(self):
-        if self._plan is not None and self._plan.graphs is not None:
-            _rast.clear_graph_flags()
+        if self._plan is not None:
+            self._plan.drop_graphs()
         self._plan = None
 
     # ---- the two halves of an iteration -----------------------------------------------------------------------------
@@ -315,13 +322,7 @@ class WindowMapper:
 
     def _rasterize(self, vp, xyz, rot, scales3, opac, feat, holder):
         """The rasteriser call of ``render()`` (/root/reference/gaussian_splatting/gaussian_renderer/__init__.py:52-156)."""
-        intr = self.intr
-        view, full, campos = cam.cached_camera_tensors(vp, vp.R, vp.T, intr.projection_matrix)
-        rs = GaussianRasterizationSettings(
-            image_height=int(intr.height), image_width=int(intr.width),
-            tanfovx=math.tan(intr.FoVx * 0.5), tanfovy=math.tan(intr.FoVy * 0.5), bg=self.bg, scale_modifier=1.0,
-            viewmatrix=view, projmatrix=full, projmatrix_raw=intr.projection_matrix, sh_degree=0, campos=campos,
-            prefiltered=False, debug=False)
+        rs = raster_settings(self.intr, self.bg, *cam.cached_camera_tensors(vp, vp.R, vp.T, self.intr.projection_matrix))
         color, radii, depth, _, n_touched = GaussianRasterizer(rs)(
             means3D=xyz, means2D=holder, opacities=opac, colors_precomp=feat, scales=scales3, rotations=rot,
             theta=vp.cam_rot_delta, rho=vp.cam_trans_delta)
@@ -484,7 +485,9 @@ class WindowMapper:
                     # chunk of where it happened instead of at the end of the run.
                     while n_left > 0:
                         if p.graphs is None:
-                            self._capture(p, viewpoints, pose_steps, lr_update)
+                            p.graph_flags = _rast.graph_flags()
+                            with p.graph_flags:
+                                self._capture(p, viewpoints, pose_steps, lr_update)
                         n = min(n_left, self.max_replays_per_capture)
                         self._replay(p, n)
                         self.nr_iters += n
@@ -492,7 +495,10 @@ class WindowMapper:
                         if _rast.check_overflow():
                             raise RuntimeError("binning capacity overflow inside the captured mapping iteration")
                         if n_left > 0:
-                            p.graphs = p.slot_graphs = None
+                            p.drop_graphs()
+                            # (the capture left ITS gradient tensors in the pose / exposure parameters' .grad, holding the last
+                            #  replay's values: the eager backward would add to them)
+                            self._zero_grads(p, viewpoints)
                             self._sync_schedule(p)
                             self._iterate_eager(p, viewpoints, pose_steps, lr_update, None, parallel=False)
                             n_left -= 1

@@ -18,6 +18,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from .raster_status import (GraphFlags, StatusLedger, STATUS_CAPACITY_OVERFLOW,  # noqa: F401  (re-exported)
+                            STATUS_DEPTH_SORT_TIMEOUT, STATUS_TILE_SORT_TIMEOUT)
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -39,38 +41,22 @@ class GaussianRasterizationSettings(NamedTuple):
 # ---- sync-free ("capacity") mode ----------------------------------------------------------------
 # The exact path (the default: what an unmodified MonoGS gets) reads the instance count R back to the host once per
 # forward, as upstream does, to size the binning scratch.  It keeps ONE thing between calls: the status word of the last
-# exact forward, which the next forward's count read-back collects at its own synchronisation (`_State.exact_pending`), so
-# that a radix-sort look-back timeout -- the one failure of the exact path -- is raised one forward later instead of never.
+# exact forward, which the next forward's count read-back collects at its own synchronisation, so that a radix-sort
+# look-back timeout -- the one failure of the exact path -- is raised one forward later instead of never.
 #
 # Capacity mode is opt-in (`set_sync_free(True)`, or implied by a hipGraph capture): the scratch is sized from the LAST count
 # seen for the same (P, W, H) times a headroom factor, the kernels read the live count on the device, and nothing in forward +
 # backward synchronises the host -- which is what lets a whole tracking / mapping iteration be captured in a hipGraph.  An
 # overflow (R > capacity) drops instances and sets a device flag; `check_overflow()` (one sync, e.g. next to the convergence
-# test of the pose step) reports it and raises the capacity so the caller can redo the iteration.  That mode needs memory
-# across calls by construction (the hints); it is bounded: at most HINTS_MAX shapes, at most PENDING_MAX unread flags.
+# test of the pose step) reports it and raises the capacity so the caller can redo the iteration.
+#
+# What is remembered between calls -- the hints, the unread words -- lives in ONE `raster_status.StatusLedger` (`_ledger`);
+# its docstring says what is kept, for how long and within which bounds.  The words of CAPTURED forwards have owners:
+# whoever captures takes a handle (`graph_flags()`), captures inside `with handle:` and calls `handle.release()` when the
+# graphs are destroyed; `check_overflow()` reads the words of every live handle, and releasing one leaves the others alone.
+# A capture outside any handle lands in one anonymous handle, which only the release-everything teardown below forgets.
 _sync_free = {"enabled": False, "headroom": 1.5}
-HINTS_MAX, PENDING_MAX = 64, 1024
-
-
-class _State:
-    capacity_hint: dict = {}
-    pending: list = []            # (key, flag) of capacity-mode forwards not yet checked
-    graph: list = []              # flags of forwards recorded inside a hipGraph capture: re-checked on every call
-    exact_pending = None          # (key, flag, device index, raw stream) of the last exact forward, or None
-    exact_other: list = []        # the same of exact forwards whose successor ran on ANOTHER stream: only check_overflow() reads them
-    exact_failed = 0              # status bits collected from earlier exact forwards, raised by the next forward / check
-
-
-_capacity_hint = _State.capacity_hint
-_pending_overflow = _State.pending
-_graph_overflow = _State.graph
-
-
-def _remember_hint(key, R):
-    h = _State.capacity_hint
-    if key not in h and len(h) >= HINTS_MAX:
-        h.pop(next(iter(h)))
-    h[key] = R
+_ledger = StatusLedger()
 
 
 def set_sync_free(enabled: bool, headroom: float = 1.5):
@@ -81,11 +67,33 @@ def sync_free_enabled() -> bool:
     return bool(_sync_free["enabled"])
 
 
+@contextlib.contextmanager
+def exact_counts():
+    """``with exact_counts():`` forwards inside run on the exact path (capacity mode off); the mode and its headroom are what
+    they were afterwards.  For a driver that measures instance counts in the middle of a capacity-mode run."""
+    was = dict(_sync_free)
+    _sync_free["enabled"] = False
+    try:
+        yield
+    finally:
+        _sync_free.update(was)
+
+
 def reserve_capacity(P: int, W: int, H: int, R: int) -> None:
     """Set the capacity hint of shape ``(P, W, H)`` to ``R`` instances: the next capacity-mode forwards of that shape (a
     hipGraph capture among them) size their binning scratch from it (x headroom).  For a captured iteration that serves
     several cameras: an exact forward overwrites the hint with ITS count, so measure every camera and reserve the maximum."""
-    _remember_hint((int(P), int(W), int(H)), int(R))
+    _ledger.remember_hint((int(P), int(W), int(H)), int(R))
+
+
+def capacity_hint(P: int, W: int, H: int) -> Optional[int]:
+    """The capacity hint of shape ``(P, W, H)``: the instance count of its last exact forward, what `reserve_capacity` set or
+    what an overflow doubled it to.  None if there is none."""
+    return _ledger.hint((int(P), int(W), int(H)))
+
+
+def forget_capacity(P: int, W: int, H: int) -> None:
+    _ledger.forget_hint((int(P), int(W), int(H)))
 
 
 # MGS_FLAG_EXCLUSIVE_DEVICE (include/monogs_raster.h): the caller vouches that nothing else runs on the device beside the
@@ -104,66 +112,24 @@ def exclusive_device(on: bool = True):
         _call_flags["exclusive"] = prev
 
 
-STATUS_CAPACITY_OVERFLOW, STATUS_DEPTH_SORT_TIMEOUT, STATUS_TILE_SORT_TIMEOUT = 1, 2, 4     # MGS_STATUS_* (monogs_raster.h)
-
-
-def _raise_sort_failure(bits):
-    which = [n for b, n in ((STATUS_DEPTH_SORT_TIMEOUT, "depth sort"), (STATUS_TILE_SORT_TIMEOUT, "tile sort")) if bits & b]
-    raise RuntimeError(f"rasteriser: a look-back spin of the {' and the '.join(which)} timed out; "
-                       "the renders since the last check are invalid")
-
-
-def _drain_exact_other(n: int) -> None:
-    """Nobody calls check_overflow(): read the oldest ``n`` status words of exact forwards that ran on other streams (synchronising
-    the devices they ran on) and keep their sort-timeout bits in ``exact_failed``, which the next forward raises -- the list
-    stays bounded without losing the one signal it exists to deliver."""
-    old, _State.exact_other = _State.exact_other[:n], _State.exact_other[n:]
-    for d in {e[2] for e in old}:
-        torch.cuda.synchronize(d)
-    for e in old:
-        _State.exact_failed |= int(e[1].item()) & (STATUS_DEPTH_SORT_TIMEOUT | STATUS_TILE_SORT_TIMEOUT)
-
-
 def check_overflow() -> bool:
-    """Reads the status words of the forwards issued since the last call (synchronises).  True if a capacity-mode
-    forward dropped instances -- the capacity hints of the offending shapes are doubled, redo the iteration.  Raises
-    if a radix-sort look-back timed out in any forward (exact or capacity mode): its blend order, hence its images
-    and gradients, are invalid."""
-    hit, sort_fail = False, _State.exact_failed
-    _State.exact_failed = 0
-    exact = _State.exact_other + ([_State.exact_pending] if _State.exact_pending is not None else [])
-    _State.exact_pending = None
-    _State.exact_other = []
-    # a status word is written by its forward's kernels on the stream (and device) that forward ran on; `.item()` only waits
-    # for the CURRENT stream, so drain the devices involved first
-    for d in {e[2] for e in exact} | {f.device.index for _, f in _State.pending + _State.graph}:
-        torch.cuda.synchronize(d)
-    todo = _State.pending + _State.graph + [(e[0], e[1]) for e in exact]
-    for key, flag in todo:
-        v = int(flag.item())
-        if v & STATUS_CAPACITY_OVERFLOW:
-            hit = True
-            _remember_hint(key, max(2 * _State.capacity_hint.get(key, 1), 1024))
-        sort_fail |= v & (STATUS_DEPTH_SORT_TIMEOUT | STATUS_TILE_SORT_TIMEOUT)
-    _State.pending.clear()
-    if sort_fail:
-        _raise_sort_failure(sort_fail)
-    return hit
+    """Reads the status words of the forwards issued since the last call, and of every captured forward whose handle is
+    live (synchronises).  True if a capacity-mode forward dropped instances -- the capacity hints of the offending shapes
+    are doubled, redo the iteration.  Raises if a radix-sort look-back timed out in any forward (exact or capacity mode):
+    its blend order, hence its images and gradients, are invalid."""
+    return _ledger.check()
+
+
+def graph_flags() -> GraphFlags:
+    """A handle that owns the status words of the forwards captured inside ``with handle:``.  ``handle.release()`` when the
+    graphs are destroyed; ``handle.accumulate(sticky)`` for a graph whose replays between two checks must all be seen."""
+    return _ledger.graph_flags()
 
 
 def clear_graph_flags():
-    """Forget the overflow flags of captured graphs (call when those graphs are destroyed)."""
-    _State.graph.clear()
-
-
-def accumulate_graph_flag(sticky: torch.Tensor) -> None:
-    """Inside a capture, right after a forward: ``sticky |= status`` (device int32[1]) as a captured op, and ``check_overflow()``
-    reads ``sticky`` in place of that forward's own word.  A forward REWRITES its status word, so a graph that is replayed many
-    times between two checks shows the last replay's only; with this the check sees an overflow (or a sort timeout) of any
-    replay since the caller last zeroed ``sticky`` -- what a graph that serves cameras of different instance counts needs."""
-    key, flag = _State.graph[-1]
-    sticky.bitwise_or_(flag)
-    _State.graph[-1] = (key, sticky)
+    """Teardown for tests and tools: release EVERY handle, the anonymous one of bare ``torch.cuda.graph`` captures included.
+    A driver releases its own handle instead."""
+    _ledger.release_all()
 
 
 # ---- optional per-stage timing (bench.py) --------------------------------------------------
@@ -309,13 +275,12 @@ class _RasterizeGaussians(torch.autograd.Function):
             status = torch.empty(1, dtype=torch.int32, device=dev) if P > 0 else None      # this forward's MGS_STATUS_* word
             key = (P, W, H)
             capturing = torch.cuda.is_current_stream_capturing()
-            hint = _State.capacity_hint.get(key)
+            hint = _ledger.hint(key)
             if capturing and hint is None:
                 raise RuntimeError("graph capture needs a capacity hint: run one eager forward with the same "
                                    "(P, W, H) first")
-            if _State.exact_failed and not capturing:
-                bits, _State.exact_failed = _State.exact_failed, 0
-                _raise_sort_failure(bits)
+            if not capturing:
+                _ledger.raise_failures()
             if (capturing or _sync_free["enabled"]) and hint is not None and P > 0:
                 # ---- capacity mode: no read-back, no stream sync, one crossing of the FFI boundary
                 R = max(int(hint * _sync_free["headroom"]) + 4096, 4096)
@@ -324,38 +289,27 @@ class _RasterizeGaussians(torch.autograd.Function):
                     C.byref(cam), P, _ptr(means3D), _ptr(sh_), _ptr(col_), _ptr(opac_), _ptr(sc_), _ptr(rot_), _ptr(cov_),
                     geom_p, radii.data_ptr(), bwd_p, R, binning.data_ptr(), img_p, color.data_ptr(), depth.data_ptr(),
                     opacity.data_ptr(), n_touched.data_ptr(), status.data_ptr(), tref, _stream()), "mgs_forward_capacity")
-                (_State.graph if capturing else _State.pending).append((key, status))
-                if len(_State.pending) > PENDING_MAX:      # nobody is checking: keep the list bounded
-                    del _State.pending[:PENDING_MAX // 2]
+                _ledger.record_capacity(key, status, capturing)
                 ctx.overflow = status
             else:
                 num_rendered, prev_bits = C.c_uint64(0), C.c_uint32(0)
-                prev = _State.exact_pending
                 here = (torch._C._cuda_getDevice(), _stream())
-                if prev is not None and (prev[2], prev[3]) != here:
-                    # the earlier forward ran on another stream / device: this stream's read-back is not ordered behind its
-                    # kernels (the header's contract is "an EARLIER forward on this stream"), so its word waits for check_overflow()
-                    _State.exact_other.append(prev)
-                    if len(_State.exact_other) > PENDING_MAX:
-                        _drain_exact_other(PENDING_MAX // 2)      # (read, never dropped: a sort timeout must not pass unseen)
-                    prev = None
+                prev = _ledger.exact_rider(*here)           # the previous exact forward's word, if it ran on this stream
                 _lib.check(lib.mgs_forward_preprocess(
                     C.byref(cam), P, _ptr(means3D), _ptr(sh_), _ptr(col_), _ptr(opac_), _ptr(sc_), _ptr(rot_),
                     _ptr(cov_), geom_p, radii.data_ptr(), bwd_p, C.byref(num_rendered),
-                    prev[1].data_ptr() if prev is not None else None, C.byref(prev_bits) if prev is not None else None,
+                    prev.data_ptr() if prev is not None else None, C.byref(prev_bits) if prev is not None else None,
                     tref, _stream()), "mgs_forward_preprocess")
-                _State.exact_pending = None
-                if prev_bits.value & (STATUS_DEPTH_SORT_TIMEOUT | STATUS_TILE_SORT_TIMEOUT):
-                    _raise_sort_failure(prev_bits.value)       # the PREVIOUS exact forward's sort timed out: never silent
+                _ledger.exact_rider_read(prev_bits.value)   # the PREVIOUS exact forward's sort timed out: raised here
                 R = int(num_rendered.value)
-                _remember_hint(key, R)
+                _ledger.remember_hint(key, R)
                 binning = torch.empty(lib.mgs_binning_bytes(R, W, H), **u8)
                 _lib.check(lib.mgs_forward_render(
                     C.byref(cam), P, R, geom_p, binning.data_ptr(), img_p, color.data_ptr(),
                     depth.data_ptr(), opacity.data_ptr(), n_touched.data_ptr(), _ptr(status), tref, _stream()),
                     "mgs_forward_render")
                 if status is not None:      # (the depth sort's flag was already checked at the count read-back)
-                    _State.exact_pending = (key, status, here[0], here[1])
+                    _ledger.record_exact(key, status, *here)
                 ctx.overflow = None
             if rs.debug:                    # upstream's debug flag: synchronise and check right after the forward
                 check_overflow()

@@ -23,7 +23,6 @@ chunk (instances were dropped: its images and gradients are wrong), the copies a
 """
 from __future__ import annotations
 
-import math
 import random
 from typing import Dict, List, Optional, Sequence
 
@@ -31,7 +30,8 @@ import torch
 
 from . import _lib, camera as cam, fused_losses, rasterizer as _rast
 from .gaussian_map import GaussianMap
-from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, _device_guard, _stream
+from .rasterizer import GaussianRasterizer, _device_guard, _stream
+from .renderer import raster_settings
 
 
 class Refiner:
@@ -52,6 +52,7 @@ class Refiner:
         self.last_grads = None
         self.last_radii = None           # radii of the last iteration's render (int32[P])
         self._graph = None
+        self._graph_flags = None         # owner of the captured forward's status word (one handle per capture)
         self._buf = None
         self._vps: List = []
         self._iters = self._done = self._window = 0
@@ -99,14 +100,7 @@ class Refiner:
 
     def _rasterize(self, cam3, xyz, rot, scales3, opac, feat, holder, theta, rho):
         """The rasteriser call of ``render()`` (/root/reference/gaussian_splatting/gaussian_renderer/__init__.py:52-156)."""
-        intr = self.intr
-        view, full, campos = cam3
-        rs = GaussianRasterizationSettings(
-            image_height=int(intr.height), image_width=int(intr.width),
-            tanfovx=math.tan(intr.FoVx * 0.5), tanfovy=math.tan(intr.FoVy * 0.5), bg=self.bg, scale_modifier=1.0,
-            viewmatrix=view, projmatrix=full, projmatrix_raw=intr.projection_matrix, sh_degree=0, campos=campos,
-            prefiltered=False, debug=False)
-        color, radii, depth, _, _ = GaussianRasterizer(rs)(
+        color, radii, depth, _, _ = GaussianRasterizer(raster_settings(self.intr, self.bg, *cam3))(
             means3D=xyz, means2D=holder, opacities=opac, colors_precomp=feat, scales=scales3, rotations=rot,
             theta=theta, rho=rho)
         return color, radii, depth
@@ -122,7 +116,7 @@ class Refiner:
         color, radii, depth = self._rasterize(cam3, xyz, rot, sc3, opac, feat, h, b["theta"], b["rho"])
         if torch.cuda.is_current_stream_capturing():
             # a forward rewrites its status word: the chunk's check must see an overflow of ANY replay, whichever keyframe it drew
-            _rast.accumulate_graph_flag(b["sticky"])
+            self._graph_flags.accumulate(b["sticky"])
         rg = fused_losses.refinement_loss_grads(color, rgb, self.lambda_ssim)
         torch.autograd.backward([color, depth], [rg.d_render, b["zero_depth"]])
         b["rg"], self.last_radii = rg, radii
@@ -165,18 +159,14 @@ class Refiner:
     def _measure(self, b, vps) -> int:
         """One exact no-grad forward per keyframe at the current map: the largest instance count."""
         gmap, key = self.gmap, (b["P"], int(self.intr.width), int(self.intr.height))
-        was, headroom = _rast.sync_free_enabled(), _rast._sync_free["headroom"]
-        _rast.set_sync_free(False, headroom)
-        try:
+        with _rast.exact_counts():
             self._activations(b)
             most = 0
             for vp in vps:
                 cam3 = cam.cached_camera_tensors(vp, vp.R, vp.T, self.intr.projection_matrix)
                 self._rasterize(cam3, gmap._xyz.detach(), b["rot"], b["scales3"], b["opac"], gmap._rgb.detach(),
                                 b["holder"].detach(), None, None)
-                most = max(most, int(_rast._capacity_hint[key]))
-        finally:
-            _rast.set_sync_free(was, headroom)
+                most = max(most, int(_rast.capacity_hint(*key)))
         return most
 
     def _capture(self, b, vps, at_least: int = 0):
@@ -185,15 +175,16 @@ class Refiner:
         _rast.reserve_capacity(b["P"], W, H, max(int(self._measure(b, vps) * scale), int(at_least)))
         self.gmap.optimizer.zero_grad(set_to_none=True)
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):          # one stream, no side streams; a memory pool of its own, released with the graph
+        self._graph_flags = _rast.graph_flags()
+        with self._graph_flags, torch.cuda.graph(g):   # one stream, no side streams; a memory pool of its own, released with the graph
             self._iteration(b, b["rgb"], b["cam3"])
         self._graph = g
         self.stats["captures"] += 1
 
     def _drop_graph(self):
-        if self._graph is not None:
-            _rast.clear_graph_flags()
-        self._graph = None
+        if self._graph_flags is not None:
+            self._graph_flags.release()
+        self._graph = self._graph_flags = None
         if self._buf is not None:
             self._buf.pop("rg", None)
         self.gmap.optimizer.zero_grad(set_to_none=True)
@@ -255,7 +246,7 @@ class Refiner:
             if _rast.check_overflow():
                 # instances were dropped somewhere in the chunk: back to its start, a capture with the capacity that
                 # check_overflow() doubled (or what the keyframes measure now, if that is more), the same chunk again
-                doubled = int(_rast._capacity_hint.get((b["P"], W, H), 0))
+                doubled = int(_rast.capacity_hint(b["P"], W, H) or 0)
                 with torch.no_grad():
                     for t, s in zip(self._state(b), snap):
                         t.copy_(s)

@@ -26,6 +26,16 @@ def _camera_center(world_view: torch.Tensor) -> torch.Tensor:
     return -(world_view[:3, :3] @ world_view[3, :3])
 
 
+def raster_settings(intr, bg, view, full, campos, scale_modifier=1.0) -> GaussianRasterizationSettings:
+    """The settings of ``render()`` (gaussian_renderer/__init__.py:70-84) from the intrinsics, the background and the three
+    camera tensors: precomputed colours (``sh_degree=0``), not prefiltered, no debug read-back."""
+    return GaussianRasterizationSettings(
+        image_height=int(intr.height), image_width=int(intr.width),
+        tanfovx=math.tan(intr.FoVx * 0.5), tanfovy=math.tan(intr.FoVy * 0.5), bg=bg, scale_modifier=scale_modifier,
+        viewmatrix=view, projmatrix=full, projmatrix_raw=intr.projection_matrix, sh_degree=0, campos=campos,
+        prefiltered=False, debug=False)
+
+
 def render(viewpoint_camera, cam_intrinsics, means, rotations, scales, opacity, features, bg_color,
            scaling_modifier=1.0, override_color=None, mask=None):
     if means.shape[0] == 0:
@@ -34,8 +44,6 @@ def render(viewpoint_camera, cam_intrinsics, means, rotations, scales, opacity, 
     # (a leaf: the reference adds `+ 0` and calls retain_grad(); `.grad` is populated either way, with one kernel less)
     screenspace_points = torch.zeros_like(means, dtype=means.dtype, requires_grad=True, device=means.device)
 
-    tanfovx = math.tan(cam_intrinsics.FoVx * 0.5)
-    tanfovy = math.tan(cam_intrinsics.FoVy * 0.5)
     projection_matrix = cam_intrinsics.projection_matrix
     R, T = getattr(viewpoint_camera, "R", None), getattr(viewpoint_camera, "T", None)
     if (torch.is_tensor(R) and torch.is_tensor(T) and R.is_cuda and T.is_cuda and R.shape == (3, 3) and T.shape == (3,)
@@ -48,17 +56,13 @@ def render(viewpoint_camera, cam_intrinsics, means, rotations, scales, opacity, 
         full_proj = (world_view.unsqueeze(0).bmm(projection_matrix.unsqueeze(0))).squeeze(0)
         campos = _camera_center(world_view)
 
-    raster_settings = GaussianRasterizationSettings(
-        image_height=int(cam_intrinsics.height), image_width=int(cam_intrinsics.width),
-        tanfovx=tanfovx, tanfovy=tanfovy, bg=bg_color, scale_modifier=scaling_modifier,
-        viewmatrix=world_view, projmatrix=full_proj, projmatrix_raw=projection_matrix,
-        sh_degree=0, campos=campos, prefiltered=False, debug=False)
+    settings = raster_settings(cam_intrinsics, bg_color, world_view, full_proj, campos, scaling_modifier)
 
     # isotropic map: the reference expands with scales.repeat(1, 3) here (gaussian_renderer/__init__.py:101-104); the
     # kernels take the [P,1] tensor as it is (mgs_camera.scale_dim = 1) and sum the three gradients themselves
     colors = features if override_color is None else override_color
 
-    rasterizer = GaussianRasterizer(raster_settings=raster_settings)
+    rasterizer = GaussianRasterizer(raster_settings=settings)
     sel = (lambda t: t[mask]) if mask is not None else (lambda t: t)
     # The reference's `mask` branch unpacks 4 outputs and then reads an undefined n_touched
     # (gaussian_renderer/__init__.py:131-143,167); no caller passes a mask.  Here the branch works.

@@ -30,8 +30,8 @@ from typing import List
 import torch
 
 from . import camera as cam
-from .renderer import render
-from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer
+from .renderer import raster_settings, render
+from .rasterizer import GaussianRasterizer
 from . import fused_losses
 from .gaussian_map import GaussianMap
 from .gaussian_optim import activate
@@ -152,10 +152,11 @@ class TrackingGraph:
         # `exclusive`: this process owns the device and the replays run one after the other on one stream, so the small sorts
         # may skip their ticket atomics (MGS_FLAG_EXCLUSIVE_DEVICE) -- NOT what a tracker beside a mapper process may assume.
         self.graphs = []
+        self.graph_flags = _r.graph_flags()          # owner of the two captured forwards' status words, until close()
         for slot in range(2):
             self.opt.zero_grad()
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g), _r.exclusive_device(exclusive):
+            with self.graph_flags, torch.cuda.graph(g), _r.exclusive_device(exclusive):
                 self._iteration(host_flag=self.flags[slot])      # graph `slot` reports into its own pinned word
             self.graphs.append(g)
         self.graph = self.graphs[0]
@@ -166,13 +167,7 @@ class TrackingGraph:
     def _iteration(self, host_flag=None):
         # render() without what tracking never reads: no screen-space gradient holder, no visibility filter
         xyz, rot, sca3, opa, col = self.map
-        view, full, campos = self.cam3
-        rs = GaussianRasterizationSettings(
-            image_height=int(self.intr.height), image_width=int(self.intr.width),
-            tanfovx=math.tan(self.intr.FoVx * 0.5), tanfovy=math.tan(self.intr.FoVy * 0.5), bg=self.bg, scale_modifier=1.0,
-            viewmatrix=view, projmatrix=full, projmatrix_raw=self.intr.projection_matrix, sh_degree=0, campos=campos,
-            prefiltered=False, debug=False)
-        color, _, depth, opacity, _ = GaussianRasterizer(rs)(
+        color, _, depth, opacity, _ = GaussianRasterizer(raster_settings(self.intr, self.bg, *self.cam3))(
             means3D=xyz, means2D=self.zero2d, opacities=opa, colors_precomp=col, scales=sca3, rotations=rot,
             theta=self.svp.cam_rot_delta, rho=self.svp.cam_trans_delta)
         self.opt.zero_grad()
@@ -218,7 +213,7 @@ class TrackingGraph:
         return n_done
 
     def close(self):
-        self._r.clear_graph_flags()
+        self.graph_flags.release()
         self.graph = None
         self.graphs = []
 
@@ -367,8 +362,6 @@ def eager_tracking_probe(frames, intr, gmap, bg, iters: int, profile_flavour=Non
     import os
     from . import rasterizer as _r
     profile_flavour = profile_flavour or os.environ.get("MGS_PROBE_PROFILE")
-    was = _r.sync_free_enabled()
-    _r.set_sync_free(False)
     vp = frames[-1]
     keep = (vp.R.clone(), vp.T.clone(), vp.exposure_a.data.clone(), vp.exposure_b.data.clone())
     out = {}
@@ -383,7 +376,7 @@ def eager_tracking_probe(frames, intr, gmap, bg, iters: int, profile_flavour=Non
             vp.cam_rot_delta.data.zero_(); vp.cam_trans_delta.data.zero_()
         for p in gmap.params():
             p.grad = None
-    try:
+    with _r.exact_counts():          # (the caller's mode and headroom are restored whatever happens inside)
         leaves = None
         for name in ("torch_losses", "fused_losses", "fused_pose_step", "render_loss_backward", "seam_only"):
             if name == "seam_only":
@@ -470,8 +463,6 @@ def eager_tracking_probe(frames, intr, gmap, bg, iters: int, profile_flavour=Non
         out["seam_only"]["stages_ms"] = st
         _r.check_overflow()
         restore()
-    finally:
-        _r.set_sync_free(was)
     out["gaussians"], out["width"], out["height"] = len(gmap), int(intr.width), int(intr.height)
     out["note"] = ("eager, exact instance count (one read-back per forward), map tensors require grad (ten-sum backward), fixed "
                    "iteration count against the final map of the run")

@@ -172,10 +172,10 @@ def test_capacity_overflow(native_lib):
     R.set_sync_free(False)
     _grads(sc)                                         # exact path: records the capacity hint
     try:
-        full = R._capacity_hint[key]
+        full = R.capacity_hint(*key)
         res = {}
         for mode in (0, 1):
-            R._capacity_hint[key] = full // 2
+            R.reserve_capacity(*key, full // 2)
             R.set_sync_free(True, headroom=1.0)
             with _Split(native_lib, mode):
                 res[mode] = _grads(sc)
@@ -185,7 +185,7 @@ def test_capacity_overflow(native_lib):
         _hold(res[1][1], res[0][1], "capacity overflow")
     finally:
         R.set_sync_free(False)
-        R._capacity_hint.pop(key, None)
+        R.forget_capacity(*key)
 
 
 def test_second_backward_through_one_forward(native_lib):

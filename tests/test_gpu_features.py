@@ -262,14 +262,14 @@ def test_capacity_mode_matches_exact_path(native_lib):
         assert close(gm_a, gm_b) and close(gt_a, gt_b)
         # starve the capacity: the flag must fire, nothing may crash
         key = (20000, 640, 480)
-        R._capacity_hint[key] = 1000
+        R.reserve_capacity(*key, 1000)
         R.set_sync_free(True, headroom=1.0)
         run()
         assert R.check_overflow()
-        assert R._capacity_hint[key] >= 2000
+        assert R.capacity_hint(*key) >= 2000
     finally:
         R.set_sync_free(False)
-        R._capacity_hint.pop((20000, 640, 480), None)
+        R.forget_capacity(20000, 640, 480)
 
 
 def test_radix_lookback_timeout_is_reported_in_every_mode(native_lib):
@@ -294,7 +294,7 @@ def test_radix_lookback_timeout_is_reported_in_every_mode(native_lib):
         assert lib.mgs_debug_set_radix_spin_limit(0) == 0
         with pytest.raises(_lib.MonoGSNativeError, match="look-back"):
             GaussianRasterizer(st)(**args)               # exact path: depth-sort flag read at the existing sync
-        R._pending_overflow.clear()
+        R._ledger.pending.clear()
         R.set_sync_free(True)
         GaussianRasterizer(st)(**args)                   # capacity path: no sync inside ...
         with pytest.raises(RuntimeError, match="timed out"):
@@ -302,7 +302,7 @@ def test_radix_lookback_timeout_is_reported_in_every_mode(native_lib):
     finally:
         lib.mgs_debug_set_radix_spin_limit(0xFFFFFFFF)
         R.set_sync_free(False)
-        R._pending_overflow.clear()
+        R._ledger.pending.clear()
     out = GaussianRasterizer(st)(**args)                 # bound restored: clean again, same image
     assert not R.check_overflow()
     assert torch.equal(out[0], ref[0])
@@ -422,17 +422,17 @@ def test_exact_path_reports_an_earlier_forwards_status_at_its_own_read_back(nati
     R.check_overflow()
     R.set_sync_free(False)
     ref = GaussianRasterizer(st)(**args)
-    assert R._State.exact_pending is not None and int(R._State.exact_pending[1].item()) == 0
-    R._State.exact_pending[1].fill_(R.STATUS_TILE_SORT_TIMEOUT)      # what ranges_kernel leaves after a timed-out tile sort
+    assert R._ledger.exact_pending is not None and int(R._ledger.exact_pending[1].item()) == 0
+    R._ledger.exact_pending[1].fill_(R.STATUS_TILE_SORT_TIMEOUT)      # what ranges_kernel leaves after a timed-out tile sort
     with pytest.raises(RuntimeError, match="tile sort"):
         GaussianRasterizer(st)(**args)                                # raised by the next forward, at ITS synchronisation
-    assert R._State.exact_pending is None
+    assert R._ledger.exact_pending is None
     out = GaussianRasterizer(st)(**args)                              # and only once
     assert torch.equal(out[0], ref[0])
     assert not R.check_overflow()
     # the same word through check_overflow()
     GaussianRasterizer(st)(**args)
-    R._State.exact_pending[1].fill_(R.STATUS_TILE_SORT_TIMEOUT)
+    R._ledger.exact_pending[1].fill_(R.STATUS_TILE_SORT_TIMEOUT)
     with pytest.raises(RuntimeError, match="tile sort"):
         R.check_overflow()
     assert not R.check_overflow()
@@ -572,16 +572,16 @@ def test_exact_status_words_of_other_streams_wait_for_check_overflow(native_lib)
     side = torch.cuda.Stream()
     with torch.no_grad():
         a = GaussianRasterizer(st)(**args)                       # current stream: its word is pending
-        assert R._State.exact_pending is not None and not R._State.exact_other
+        assert R._ledger.exact_pending is not None and not R._ledger.exact_other
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
             b = GaussianRasterizer(st)(**args)                   # another stream: the first word is parked, not read
-        assert len(R._State.exact_other) == 1 and R._State.exact_pending is not None
+        assert len(R._ledger.exact_other) == 1 and R._ledger.exact_pending is not None
         side.synchronize()
         c = GaussianRasterizer(st)(**args)                       # back on the first stream: the side stream's word is parked too
-        assert len(R._State.exact_other) == 2
+        assert len(R._ledger.exact_other) == 2
     assert not R.check_overflow()                                # reads all three after draining the device
-    assert R._State.exact_pending is None and not R._State.exact_other
+    assert R._ledger.exact_pending is None and not R._ledger.exact_other
     assert torch.equal(a[0], b[0]) and torch.equal(a[0], c[0])
 
 
@@ -754,6 +754,119 @@ def test_graph_scratch_is_not_recycled_by_eager_allocations(native_lib):
         del eager
     assert not _r.check_overflow()
     _r.clear_graph_flags()
+
+
+def _full_cover_scene(P):
+    """64 x 64 pixels = 16 tiles, every Gaussian in front of the camera inside the image and 50 px wide (sigma): each one
+    touches all 16 tiles, so a forward has 16 P instances."""
+    sc = make_scene(P, dict(fx=200.0, fy=200.0, cx=32.0, cy=32.0, W=64, H=64), seed=P, near_fraction=0.0)
+    g = torch.Generator().manual_seed(P)
+    pc = torch.cat([0.5 * torch.rand(P, 2, generator=g) - 0.25, torch.full((P, 1), 2.0)], 1)     # camera frame
+    return sc._replace(means3D=((pc - sc.t[None, :]) @ sc.R).contiguous(), scales=torch.full((P, 1), 0.5))
+
+
+def test_two_capture_owners_keep_their_own_status_words(native_lib):
+    """Two maps (two hint keys), one captured forward of each under a handle of its own; the second is starved of capacity.
+    Releasing the FIRST handle leaves the second one's overflow visible (and only its key doubled); releasing the second
+    leaves nothing.  Capacity overflow is a reported condition (truncated lists, a flag), as in test_capacity_mode_matches_exact_path."""
+    from monogs_amd import rasterizer as R
+    from monogs_amd.rasterizer import GaussianRasterizer
+    sizes = (1024, 1025)
+    dev = lambda t: t.to(DEV)  # noqa: E731
+    st, args = {}, {}
+    for P in sizes:
+        sc = _full_cover_scene(P)
+        st[P] = _hip_st(sc)
+        args[P] = dict(means3D=dev(sc.means3D), means2D=torch.zeros(P, 3, device=DEV), opacities=dev(sc.opacities),
+                       colors_precomp=dev(sc.colors), scales=dev(sc.scales), rotations=dev(sc.rotations))
+
+    def forward(P):
+        with torch.no_grad():
+            return GaussianRasterizer(st[P])(**args[P])[0]
+
+    R.check_overflow()
+    R.set_sync_free(False)
+    handles = {}
+    try:
+        counts = {}
+        for P in sizes:
+            forward(P)                                   # exact: leaves its instance count as the hint of (P, 64, 64)
+            counts[P] = R.capacity_hint(P, 64, 64)
+        assert not R.check_overflow()
+        print(f"instance counts: {counts}")
+        # capacity mode never reserves fewer than 4096 + hint slots: the second map must need at least twice that with hint 1
+        assert counts[1025] >= 2 * (4096 + 1), counts
+        R.reserve_capacity(1025, 64, 64, 1)
+        R.set_sync_free(True, headroom=1.0)
+        graphs = {}
+        for P in sizes:
+            handles[P], graphs[P] = R.graph_flags(), torch.cuda.CUDAGraph()
+            with handles[P], torch.cuda.graph(graphs[P]):
+                forward(P)
+        for P in sizes:
+            graphs[P].replay()
+        torch.cuda.synchronize()
+        assert len(handles[1024]) == 1 and len(handles[1025]) == 1
+        handles[1024].release()
+        assert R.check_overflow() is True
+        assert R.capacity_hint(1025, 64, 64) >= 1024 and R.capacity_hint(1024, 64, 64) == counts[1024]
+        handles[1025].release()
+        assert R.check_overflow() is False
+    finally:
+        R.set_sync_free(False)
+        for P, h in handles.items():
+            h.release()
+        for P in sizes:
+            R.forget_capacity(P, 64, 64)
+
+
+def test_tracking_graph_close_leaves_other_owners_words_alone(native_lib):
+    """A handle with one captured forward, then a ``TrackingGraph`` built and closed: `close()` forgets the two words of the
+    tracking graphs and nothing else -- a flag planted in the first handle's word is still reported."""
+    from monogs_amd import rasterizer as R
+    from monogs_amd.gaussian_map import GaussianMap
+    from monogs_amd.rasterizer import GaussianRasterizer
+    from monogs_amd.renderer import raster_settings
+    from monogs_amd.slam_harness import TrackingGraph, make_sequence
+    frames, intr = make_sequence(1, "fr3_office", n_gaussians=20000, device=DEV)
+    vp = frames[0]
+    vp.update_RT(vp.R_gt.clone(), vp.T_gt.clone())
+    gmap = GaussianMap(DEV)
+    gmap.extend_from_frame(vp, intr, downsample=8, init=True, point_size=1.0)
+    bg = torch.zeros(3, device=DEV)
+    P = len(gmap)
+    with torch.no_grad():
+        rs = raster_settings(intr, bg, *cam.fused_camera_matrices(vp.R, vp.T, intr.projection_matrix))
+        args = dict(means3D=gmap.get_xyz.detach(), means2D=torch.zeros(P, 3, device=DEV), opacities=gmap.get_opacity.detach(),
+                    colors_precomp=gmap.get_features.detach(), scales=gmap.get_scaling.detach(), rotations=gmap.get_rotation.detach())
+
+    def forward():
+        with torch.no_grad():
+            return GaussianRasterizer(rs)(**args)[0]
+
+    R.check_overflow()
+    R.set_sync_free(False)
+    ref = forward().clone()                              # exact: records the capacity hint of this map size
+    mine, graph = R.graph_flags(), torch.cuda.CUDAGraph()
+    try:
+        with mine, torch.cuda.graph(graph):
+            img = forward()
+        graph.replay()
+        torch.cuda.synchronize()
+        assert torch.equal(img, ref) and len(mine) == 1
+        tg = TrackingGraph(vp, intr, gmap, bg)
+        assert len(tg.graph_flags) == 2 and len(mine) == 1          # its two graphs' words went to ITS handle
+        assert len(R._ledger.captured_words()) == 3
+        tg.close()
+        assert len(tg.graph_flags) == 0 and R._ledger.captured_words() == mine.words
+        assert not R.check_overflow()
+        mine.words[0][1].fill_(R.STATUS_CAPACITY_OVERFLOW)
+        assert R.check_overflow()                        # the first handle's word is still read
+        mine.release()
+        assert not R.check_overflow() and R._ledger.captured_words() == []
+    finally:
+        mine.release()
+        R.forget_capacity(P, 640, 480)
 
 
 def test_pose_only_backward_matches_full(native_lib):

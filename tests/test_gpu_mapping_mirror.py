@@ -276,6 +276,40 @@ def test_captured_iterations_match_eager_which_matches_the_mirror(native_lib):
     _check_windows_agree(graph, eager, 4, iters)
 
 
+def test_recaptured_iterations_match_eager_and_forget_the_dropped_captures(native_lib):
+    """``max_replays_per_capture = 3`` over 12 iterations: eager, capture, 3 replays -- three times over.  The result is held
+    against the all-eager run at the bars of ``_check_windows_agree``; the status words of the two captures that were dropped on
+    the way are gone from the ledger, the live plan's handle holds one word per forward its graph captured (single rank: one
+    graph, one forward per window keyframe), and ``_drop_plan()`` leaves none."""
+    from test_gpu_window import _check_windows_agree
+    from monogs_amd import rasterizer as R
+    iters = 12
+    frames, intr, gmap, mapper, bg = _setup(2, 2)
+    mapper.map_surgery = False
+    before = [p.detach().cpu().clone() for p in gmap.params()]
+    mapper.optimize_map(frames, iters=iters)
+    eager = _window_result(gmap, mapper, frames, before)
+    assert mapper.stats["replays"] == 0 and mapper.stats["eager_iters"] == iters
+    mapper._drop_plan()
+    R.check_overflow()
+    R.clear_graph_flags()                                # (whatever earlier tests of this process left behind)
+
+    frames, intr, gmap, mapper, bg = _setup(2, 2, use_graph=True)
+    mapper.map_surgery = False
+    mapper.max_replays_per_capture = 3
+    mapper.optimize_map(frames, iters=iters)
+    assert mapper.stats["captures"] == 3 and mapper.stats["replays"] == 9 and mapper.stats["eager_iters"] == 3, mapper.stats
+    graph = _window_result(gmap, mapper, frames, before)
+    p = mapper._plan
+    assert p.graphs is not None and len(p.graphs) == 1
+    assert len(p.graph_flags) == len(p.vps) == 2
+    assert R._ledger.captured_words() == p.graph_flags.words       # nothing of the two dropped captures
+    assert not R.check_overflow()
+    mapper._drop_plan()
+    assert R._ledger.captured_words() == []
+    _check_windows_agree(graph, eager, 2, iters)
+
+
 # ---- (g) the densify iteration -----------------------------------------------------------------------------------------
 def test_densify_iteration_picks_the_reference_gaussians(native_lib):
     from monogs_amd.gaussian_optim import expon_lr
