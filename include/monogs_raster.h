@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define MGS_ABI_VERSION 16
+#define MGS_ABI_VERSION 17
 #define MGS_TILE 16 /* tile edge in pixels; ranges are per 16x16 tile */
 
 /* GaussianRasterizationSettings, minus `prefiltered` / `debug` which are call flags
@@ -295,6 +295,38 @@ int mgs_debug_blend_stats(const mgs_camera* cam, int32_t P, uint64_t num_rendere
 #define MGS_BLEND_MASK_STATS_WORDS 4
 int mgs_debug_blend_mask_stats(const mgs_camera* cam, int32_t P, uint64_t num_rendered, const void* geometry,
                                const void* binning, const void* image, uint64_t* stats_dev, void* stream);
+
+/* ---- K-channel feature rendering (ABI v17) ---------------------------------------------------------------
+ * Blends K arbitrary per-Gaussian channels (object probabilities, semantic logits, ...) through the lists and the per-pixel
+ * decisions a finished forward left in its scratch, with the weights alpha T that forward's colours were blended with:
+ *
+ *     out[k, p] = sum_i features[g_i, k] alpha_i T_i  (+ final_T[p] bg[k] when bg is non-NULL)
+ *
+ * over the contributors i of pixel p -- list positions 1 .. n_contrib[p] with power <= 0 and alpha >= 1/255; the forward decided
+ * where each pixel stops, nothing is re-decided here.  mgs_features_backward is the gradient to the features,
+ *
+ *     dL_dfeatures[g, k] = sum_p alpha T dL_dout[k, p],
+ *
+ * and the only one: bg, geometry, opacity and pose take none (the feature image is a read-out of a map the colour and depth
+ * losses shape).  dL_dfeatures is cleared by the call; rows of Gaussians in no list stay exactly 0.
+ *
+ * LAYOUT: features and dL_dfeatures are [P, K] row-major, out and dL_dout [K, H, W], bg [K] (or NULL: no background term),
+ * labels [H, W] int32 (or NULL).  K is 1 .. MGS_MAX_FEATURE_CHANNELS (segmentation ids are 8-bit in mgs_frame_prepare); K outside
+ * that, or P > MGS_MAX_GAUSSIANS, returns 1.  labels[p] = the lowest index k that maximises the accumulated value WITHOUT the
+ * background term, or -1 where 1.0f - final_T[p] < min_opacity (the float32 opacity the forward wrote).  P == 0: out = bg (or
+ * 0), labels = -1, nothing else is read.
+ * LIFETIME: `geometry`, `binning`, `image` are the scratch of a finished mgs_forward_render / _capacity for the same cam, P
+ * and num_rendered (the capacity, in capacity mode: what mgs_backward takes); they are only READ, so the calls may come
+ * before or after mgs_backward, any number of times, while the scratch is alive and unmodified.  Both functions keep no state
+ * and never synchronise the host. */
+#define MGS_MAX_FEATURE_CHANNELS 256
+int mgs_features_forward(const mgs_camera* cam, int32_t P, int32_t K, uint64_t num_rendered, const void* geometry,
+                         const void* binning, const void* image, const float* features /* [P,K] */,
+                         const float* bg /* [K] or NULL */, float* out /* [K,H,W] */, int32_t* labels /* [H,W] or NULL */,
+                         float min_opacity, void* stream);
+int mgs_features_backward(const mgs_camera* cam, int32_t P, int32_t K, uint64_t num_rendered, const void* geometry,
+                          const void* binning, const void* image, const float* dL_dout /* [K,H,W] */,
+                          float* dL_dfeatures /* [P,K], cleared here */, void* stream);
 
 /* visible[P] (1 byte each) = view-space z > 0.2 (upstream markVisible; unused by MonoGS). */
 int mgs_mark_visible(int32_t P, const float* means3D, const float* viewmatrix, const float* projmatrix,

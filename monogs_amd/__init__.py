@@ -1,3 +1,11 @@
 """monogs_amd -- MI355X-native differentiable Gaussian rasteriser with camera-pose Jacobians,
 a drop-in for MonoGS's ``diff_gaussian_rasterization`` and ``simple_knn``."""
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    # render_features / FeatureRasterizer (monogs_amd.feature_render) on first use: importing the package stays free of torch
+    if name in ("render_features", "FeatureRasterizer"):
+        from . import feature_render
+        return getattr(feature_render, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

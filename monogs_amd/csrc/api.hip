@@ -375,6 +375,41 @@ int mgs_backward(const mgs_camera* cam, int32_t P, uint64_t R, const float* mean
     return 0;
 }
 
+static int check_features(const mgs_camera* cam, int32_t P, int32_t K) {
+    if (check_cam(cam)) return 1;
+    if (P < 0) { set_error("P must be >= 0"); return 1; }
+    if (check_map_size(P)) return 1;
+    if (K < 1 || K > MGS_MAX_FEATURE_CHANNELS) { set_error("K must be 1..MGS_MAX_FEATURE_CHANNELS (256)"); return 1; }
+    return 0;
+}
+
+int mgs_features_forward(const mgs_camera* cam, int32_t P, int32_t K, uint64_t num_rendered, const void* geometry,
+                         const void* binning, const void* image, const float* features, const float* bg, float* out,
+                         int32_t* labels, float min_opacity, void* stream) {
+    if (check_features(cam, P, K)) return 1;
+    if (!out) { set_error("out must be non-NULL"); return 1; }
+    if (P > 0 && (!geometry || !image || !features)) { set_error("geometry, image, features must be non-NULL"); return 1; }
+    if (P > 0 && num_rendered > 0 && !binning) { set_error("binning scratch is NULL"); return 1; }
+    const int W = cam->image_width, H = cam->image_height;
+    GeometryState g = GeometryState::carve(const_cast<void*>(geometry), P);
+    ImageState img = ImageState::carve(const_cast<void*>(image), W, H);
+    BinningState b = BinningState::carve(const_cast<void*>(binning), num_rendered, W, H);
+    return launch_features_forward(*cam, P, K, g, b, img, features, bg, out, labels, min_opacity, (hipStream_t)stream);
+}
+
+int mgs_features_backward(const mgs_camera* cam, int32_t P, int32_t K, uint64_t num_rendered, const void* geometry,
+                          const void* binning, const void* image, const float* dL_dout, float* dL_dfeatures, void* stream) {
+    if (check_features(cam, P, K)) return 1;
+    if (P == 0) return 0;
+    if (!geometry || !image || !dL_dout || !dL_dfeatures) { set_error("geometry, image, dL_dout, dL_dfeatures must be non-NULL"); return 1; }
+    if (num_rendered > 0 && !binning) { set_error("binning scratch is NULL"); return 1; }
+    const int W = cam->image_width, H = cam->image_height;
+    GeometryState g = GeometryState::carve(const_cast<void*>(geometry), P);
+    ImageState img = ImageState::carve(const_cast<void*>(image), W, H);
+    BinningState b = BinningState::carve(const_cast<void*>(binning), num_rendered, W, H);
+    return launch_features_backward(*cam, P, K, g, b, img, dL_dout, dL_dfeatures, (hipStream_t)stream);
+}
+
 int mgs_debug_blend_stats(const mgs_camera* cam, int32_t P, uint64_t R, const void* geometry, const void* binning,
                            const void* image, uint64_t* stats_dev, void* stream) {
     if (check_cam(cam)) return 1;

@@ -303,6 +303,12 @@ int launch_blend_backward_stats(const mgs_camera& cam, const GeometryState& g, c
 int launch_blend_mask_stats(const mgs_camera& cam, const GeometryState& g, const BinningState& b,
                             const ImageState& img, unsigned long long* stats, hipStream_t s);
 int launch_valu_ceiling(float* out, int iters, hipStream_t s);
+// K feature channels through the tables of a finished forward (features.hip): read-only on all three scratch states
+int launch_features_forward(const mgs_camera& cam, int P, int K, const GeometryState& g, const BinningState& b,
+                            const ImageState& img, const float* features, const float* bg, float* out, int32_t* labels,
+                            float min_opacity, hipStream_t s);
+int launch_features_backward(const mgs_camera& cam, int P, int K, const GeometryState& g, const BinningState& b,
+                             const ImageState& img, const float* dL_dout, float* dL_dfeatures, hipStream_t s);
 struct GeomBackwardArgs {
     const float *means3D, *shs, *colors_precomp, *opacities, *scales, *rotations, *cov3D_precomp;
     const int32_t* radii;

@@ -56,8 +56,15 @@ class GaussianMap:
     """Isotropic RGB map with the reference's activations."""
 
     def __init__(self, device, capturable=False, fused_adam=True, lrs: Sequence[float] = DEFAULT_LRS,
-                 percent_dense: float = 0.01):
+                 percent_dense: float = 0.01, nr_objects: Optional[int] = None):
         self.device = device
+        # The object layer (gaussian_model.py:47,55,66,108-110): a row of ``nr_objects`` object scores per Gaussian, one-hot
+        # from the segment id of the pixel it was back-projected from (:373-382), carried through every piece of map surgery,
+        # NOT in the optimiser and without grad, as the reference has it.  None: no such layer, nothing below touches it.
+        if nr_objects is not None and not 1 <= int(nr_objects) <= 256:
+            raise ValueError("nr_objects must be 1..256 (segmentation ids are 8-bit)")
+        self.nr_objects = None if nr_objects is None else int(nr_objects)
+        self._obj_prob = None if nr_objects is None else torch.empty(0, self.nr_objects, device=device)
         self.capturable = capturable        # torch.optim.Adam(capturable=True): step counters on the device (hipGraph)
         self.fused_adam = fused_adam        # monogs_amd.gaussian_optim.GaussianAdam (one launch, always capturable)
         self.lrs = [float(x) for x in lrs]
@@ -78,6 +85,12 @@ class GaussianMap:
     get_scaling = property(lambda s: torch.exp(s._scaling))
     get_rotation = property(lambda s: torch.nn.functional.normalize(s._rotation))
 
+    @property
+    def get_obj_prob(self):
+        if self._obj_prob is None:
+            raise AttributeError("this map has no object layer: build it with GaussianMap(..., nr_objects=K)")
+        return torch.softmax(self._obj_prob, dim=1)
+
     def __len__(self):
         return int(self._xyz.shape[0])
 
@@ -94,9 +107,13 @@ class GaussianMap:
     # ---- growth: densification_postfix (gaussian_model.py:745-776) ---------------------------------------------
     @torch.no_grad()
     def densification_postfix(self, new_xyz, new_rgb, new_opacity, new_scaling, new_rotation, new_kf_idxs=None,
-                              new_nr_obs=None):
+                              new_nr_obs=None, new_obj_prob=None):
         new = [new_xyz, new_rgb, new_opacity, new_scaling, new_rotation]
         n_new = int(new_xyz.shape[0])
+        if self._obj_prob is not None:       # (checked before anything grows: the rows and the map stay the same length)
+            if new_obj_prob is None or tuple(new_obj_prob.shape) != (n_new, self.nr_objects):
+                raise ValueError(f"a map with an object layer grows by new_obj_prob [{n_new}, {self.nr_objects}]")
+            self._obj_prob = torch.cat((self._obj_prob, new_obj_prob.detach().to(self._obj_prob)), 0)
         if self.optimizer is None:
             self._set_params([torch.cat([o.detach(), n.detach()], 0).requires_grad_(True)
                               for o, n in zip(self.params(), new)])
@@ -145,6 +162,12 @@ class GaussianMap:
         self.max_radii_2d = self.max_radii_2d[keep]
         self.kf_idx = self.kf_idx[keep]
         self.nr_obs = self.nr_obs[keep]
+        if self._obj_prob is not None:
+            self._obj_prob = self._obj_prob[keep]
+
+    def _obj_rows(self, sel, N: int = 1):
+        """The object rows of the selected Gaussians, repeated as clone (N = 1) / split (``.repeat(N, 1)``) repeat them."""
+        return None if self._obj_prob is None else self._obj_prob[sel].repeat(N, 1)
 
     # ---- densify (gaussian_model.py:778-886) -------------------------------------------------------------------
     @torch.no_grad()
@@ -152,7 +175,8 @@ class GaussianMap:
         sel = torch.norm(grads, dim=-1) >= grad_threshold
         sel &= self.get_scaling.max(dim=1).values <= self.percent_dense * scene_extent
         self.densification_postfix(self._xyz[sel], self._rgb[sel], self._opacity[sel], self._scaling[sel],
-                                   self._rotation[sel], new_kf_idxs=self.kf_idx[sel], new_nr_obs=self.nr_obs[sel])
+                                   self._rotation[sel], new_kf_idxs=self.kf_idx[sel], new_nr_obs=self.nr_obs[sel],
+                                   new_obj_prob=self._obj_rows(sel))
 
     @torch.no_grad()
     def densify_and_split(self, grads, grad_threshold, scene_extent, N=2, generator: Optional[torch.Generator] = None):
@@ -168,7 +192,7 @@ class GaussianMap:
         new_scaling = torch.log(self.get_scaling[sel].repeat(N, 1) / (0.8 * N))
         self.densification_postfix(new_xyz, self._rgb[sel].repeat(N, 1), self._opacity[sel].repeat(N, 1), new_scaling,
                                    self._rotation[sel].repeat(N, 1), new_kf_idxs=self.kf_idx[sel].repeat(N),
-                                   new_nr_obs=self.nr_obs[sel].repeat(N))
+                                   new_nr_obs=self.nr_obs[sel].repeat(N), new_obj_prob=self._obj_rows(sel, N))
         prune = torch.cat((sel, torch.zeros(N * int(sel.sum()), device=self.device, dtype=torch.bool)))
         self.prune_points(prune)
 
@@ -225,27 +249,52 @@ class GaussianMap:
 
     # ---- new Gaussians from a keyframe (extend_from_pcd_seq, gaussian_model.py:321-396) --------------------------
     def extend_from_frame(self, vp, intr, downsample: int, point_size=0.05, init=False, render_opacity=None,
-                          render_depth=None, kf_id: Optional[int] = None):
+                          render_depth=None, kf_id: Optional[int] = None, random_indices: Optional[torch.Tensor] = None):
         """Back-project a keyframe's depth into new Gaussians; scale from distCUDA2
         (gaussian_model.py:121-319 via ``monogs_amd.keyframe``).  ``point_size=None``: the reference's rule,
-        scale^2 = dist2 x min(0.05, 0.01 x median depth) (gaussian_model.py:173-178); a number: scale^2 = dist2 x point_size."""
+        scale^2 = dist2 x min(0.05, 0.01 x median depth) (gaussian_model.py:173-178); a number: scale^2 = dist2 x point_size.
+        ``random_indices``: the subset of the candidate pixels, as ``create_viewpoint_pcd`` takes it (default: drawn on the device).
+        A map with an object layer gives every new Gaussian the one-hot row of its pixel's ``vp.segmentation`` id."""
         from .keyframe import create_viewpoint_pcd
         g = torch.Generator(device=self.device).manual_seed(1000 + vp.frame_idx)
         ps = dict(point_size=0.01, point_size_max=0.05) if point_size is None else dict(point_size=1e9, point_size_max=point_size)
-        pw, rgb, scales, rots, opac, _ = create_viewpoint_pcd(
+        pw, rgb, scales, rots, opac, ids = create_viewpoint_pcd(
             vp, intr, render_depth=None if init else (render_depth if render_depth is not None else vp.depth),
             render_opacity=None if init else render_opacity, init=init,
-            generator=g, downsample_factor=downsample, **ps)
+            generator=g, downsample_factor=downsample, random_indices=random_indices, **ps)
         n_new = pw.shape[0]
         if n_new < 4:
             return 0
         kf = torch.full((n_new,), int(vp.frame_idx if kf_id is None else kf_id), dtype=torch.int32, device=self.device)
+        obj = None
+        if self._obj_prob is not None:
+            # one-hot at the segment id of the pixel each point came from (gaussian_model.py:373-382); a frame without
+            # segmentation gives id 0, the viewer packet's fallback (viewer/viewer_packet.py:52-54)
+            ids = torch.zeros(n_new, dtype=torch.long, device=self.device) if ids is None else ids.long()
+            if int(ids.max()) >= self.nr_objects or int(ids.min()) < 0:
+                raise ValueError(f"segmentation id {int(ids.max())} outside the map's {self.nr_objects} objects")
+            obj = torch.nn.functional.one_hot(ids, self.nr_objects).to(torch.float32)
         if self.fused_adam or self.optimizer is None:
             # (extend_from_pcd_seq goes through densification_postfix as well: statistics restart from zero)
-            self.densification_postfix(pw, rgb, opac, scales, rots, new_kf_idxs=kf)
+            self.densification_postfix(pw, rgb, opac, scales, rots, new_kf_idxs=kf, new_obj_prob=obj)
         else:
             self._torch_extend([pw, rgb, opac, scales, rots])
             self._init_stats(len(self))
             self.kf_idx = torch.cat((self.kf_idx, kf))
             self.nr_obs = torch.cat((self.nr_obs, torch.zeros_like(kf)))
+            if obj is not None:
+                self._obj_prob = torch.cat((self._obj_prob, obj), 0)
         return n_new
+
+
+def object_labels(gmap: GaussianMap) -> torch.Tensor:
+    """int64[P]: the most probable object of every Gaussian -- the viewer packet's ``obj_idx`` (viewer/viewer_packet.py:52-54)."""
+    return torch.argmax(gmap.get_obj_prob, dim=1)
+
+
+def object_colors(gmap: GaussianMap, palette: torch.Tensor) -> torch.Tensor:
+    """[P,3]: ``palette[K,3]`` looked up with ``object_labels`` -- the colour override of the viewer's segmentation shader
+    (viewer/slam_viewer.py:698-700)."""
+    if palette.dim() != 2 or palette.shape[0] != gmap.nr_objects or palette.shape[1] != 3:
+        raise ValueError(f"palette must be [{gmap.nr_objects}, 3]")
+    return palette.to(gmap.device)[object_labels(gmap)]

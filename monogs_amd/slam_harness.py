@@ -66,8 +66,10 @@ def scharr_grad_mask(rgb: torch.Tensor, edge_threshold: float = 1.1, eps: float 
 
 
 class Viewpoint:
-    def __init__(self, idx, rgb, depth, device, gt_R=None, gt_T=None, mask=None, grad_mask=None):
+    def __init__(self, idx, rgb, depth, device, gt_R=None, gt_T=None, mask=None, grad_mask=None, segmentation=None):
         self.frame_idx, self.device = idx, device
+        if segmentation is not None:        # [H,W] integer object ids: what the back-projection labels its points with
+            self.segmentation = segmentation
         self.R = torch.eye(3, device=device)
         self.T = torch.zeros(3, device=device)
         self.R_gt, self.T_gt = gt_R, gt_T
@@ -280,9 +282,13 @@ def _room_texture(p, axis, sid):
     return (base * lum[:, None] + tint).clamp(0.02, 0.98)
 
 
+ROOM_SURFACES = 6 + 3 * len(_ROOM_BOXES)       # surface ids raycast_room can return: six walls, three face axes per box
+
+
 @torch.no_grad()
-def raycast_room(R, t, k, device):
-    """(rgb [3,H,W], depth [H,W]) of the room seen by the world->camera pose (R, t).  Pixel (x, y) looks along
+def raycast_room(R, t, k, device, with_ids=False):
+    """(rgb [3,H,W], depth [H,W]) of the room seen by the world->camera pose (R, t); ``with_ids``: also the id [H,W] (int32,
+    below ``ROOM_SURFACES``) of the surface every ray hit.  Pixel (x, y) looks along
     ((x + 0.5 - cx) / fx, (y + 0.5 - cy) / fy, 1): the rasteriser's pixel convention (``px = fx X/Z + cx - 0.5``) and the
     back-projection's (/root/reference/gaussian_splatting/scene/gaussian_model.py:232-236)."""
     H, W = k["H"], k["W"]
@@ -308,12 +314,16 @@ def raycast_room(R, t, k, device):
         sid = torch.where(hit, 6 + bi * 3 + ax, sid)
     p = o + best[:, None] * d
     rgb = _room_texture(p, axis, sid)
+    if with_ids:
+        return rgb.t().reshape(3, H, W).contiguous(), best.reshape(H, W).contiguous(), sid.to(torch.int32).reshape(H, W).contiguous()
     return rgb.t().reshape(3, H, W).contiguous(), best.reshape(H, W).contiguous()
 
 
-def make_room_sequence(n_frames: int, intrinsics="fr3_office", device="cuda:0", step_scale: float = 1.0):
+def make_room_sequence(n_frames: int, intrinsics="fr3_office", device="cuda:0", step_scale: float = 1.0,
+                       with_segmentation: bool = False):
     """``n_frames`` RGB-D frames of the room along a smooth hand-held-like path (about 1 cm and 0.3 degrees per frame at
-    ``step_scale`` 1: the inter-frame motion of a 30 Hz TUM sequence), ground-truth poses attached."""
+    ``step_scale`` 1: the inter-frame motion of a 30 Hz TUM sequence), ground-truth poses attached.  ``with_segmentation``:
+    every frame also carries ``segmentation``, the id of the surface each pixel's ray hit (``raycast_room``)."""
     k = dict(cam.INTRINSICS[intrinsics]) if isinstance(intrinsics, str) else dict(intrinsics)
     intr = Intrinsics(k, device)
     frames: List[Viewpoint] = []
@@ -324,8 +334,9 @@ def make_room_sequence(n_frames: int, intrinsics="fr3_office", device="cuda:0", 
         Rwc = cam.so3_exp(torch.tensor([0.0, yaw, 0.0])) @ cam.so3_exp(torch.tensor([pitch, 0.0, 0.0]))   # camera -> world
         Rcw = Rwc.t().contiguous()
         tcw = -(Rcw @ c)
-        rgb, depth = raycast_room(Rcw, tcw, k, device)
-        frames.append(Viewpoint(i, rgb, depth, device, gt_R=Rcw.to(device), gt_T=tcw.to(device)))
+        rgb, depth, *seg = raycast_room(Rcw, tcw, k, device, with_ids=with_segmentation)
+        frames.append(Viewpoint(i, rgb, depth, device, gt_R=Rcw.to(device), gt_T=tcw.to(device),
+                                segmentation=seg[0] if seg else None))
     return frames, intr
 
 
@@ -475,7 +486,7 @@ def run_slam(n_frames=12, intrinsics="fr3_office", tracking_itr_num=100, mapping
              track_lookahead=1, map_surgery=False, reference_lrs=False, prune_after_mapping=None,
              scene="cloud", reference_densify=False, eager_probe=0, exclusive_device=False,
              kf_selection="interval", check_viewpoints_overlap=False, kf_trace=None, refine_iters=0, eval_render=False,
-             sequence=None):
+             sequence=None, nr_objects=None):
     """Returns a dict with tracking / mapping FPS, iterations and the trajectory error.
 
     Mapping runs through ``monogs_amd.mapping.WindowMapper`` -- the SAME ``optimize_map`` / ``initialize_map`` the sharded
@@ -508,7 +519,11 @@ def run_slam(n_frames=12, intrinsics="fr3_office", tracking_itr_num=100, mapping
     iterations of ``Mapper.refinement`` over all keyframes through ``monogs_amd.refinement.Refiner`` (captured when
     ``graph_mapping``); adds ``refinement`` (the driver's dict + ``it_per_s``).  Both default to off: nothing changes.
     ``sequence``: a ``(frames, intr)`` pair, e.g. from ``monogs_amd.dataset.dataset_frames``, that replaces the synthetic
-    generator; ``n_frames`` is then its length and ``scene`` / ``intrinsics`` / ``n_gaussians`` are ignored."""
+    generator; ``n_frames`` is then its length and ``scene`` / ``intrinsics`` / ``n_gaussians`` are ignored.
+    ``nr_objects``: the map carries that many object scores per Gaussian (``GaussianMap(nr_objects=...)``), one-hot from the
+    frames' ``segmentation`` (``make_room_sequence(with_segmentation=True)`` is what ``scene="room"`` then generates); the result
+    also holds the map, the frames and the intrinsics (``map``, ``frame_list``, ``intr``) for a caller that renders from it.
+    None (default): no object layer, nothing changes."""
     if kf_selection not in ("interval", "overlap"):
         raise ValueError('kf_selection must be "interval" or "overlap"')
     from .gaussian_map import REFERENCE_LRS, REFERENCE_LR_SCHEDULE
@@ -519,7 +534,7 @@ def run_slam(n_frames=12, intrinsics="fr3_office", tracking_itr_num=100, mapping
         frames, intr = sequence
         n_frames = len(frames)
     elif scene == "room":
-        frames, intr = make_room_sequence(n_frames, intrinsics, device=device)
+        frames, intr = make_room_sequence(n_frames, intrinsics, device=device, with_segmentation=nr_objects is not None)
     else:
         frames, intr = make_sequence(n_frames, intrinsics, n_gaussians, device=device)
     if reference_densify:
@@ -527,7 +542,7 @@ def run_slam(n_frames=12, intrinsics="fr3_office", tracking_itr_num=100, mapping
     else:
         extend_kw = lambda init: dict(downsample=init_downsample if init else kf_downsample, point_size=point_size)  # noqa: E731
     bg = torch.zeros(3, device=device)
-    gmap = GaussianMap(device, **(dict(lrs=REFERENCE_LRS) if reference_lrs else {}))
+    gmap = GaussianMap(device, nr_objects=nr_objects, **(dict(lrs=REFERENCE_LRS) if reference_lrs else {}))
     if reference_lrs:
         gmap.lr_schedule = dict(REFERENCE_LR_SCHEDULE)
     gmap.surgery_log = []
@@ -725,6 +740,8 @@ def run_slam(n_frames=12, intrinsics="fr3_office", tracking_itr_num=100, mapping
         gc.collect()
         torch.cuda.empty_cache()
         out["eager_tracking"] = eager_tracking_probe(frames, intr, gmap, bg, int(eager_probe))
+    if nr_objects is not None:
+        out.update(map=gmap, frame_list=frames, intr=intr)
     out.update(frames=n_frames, gaussians=int(gmap.get_xyz.shape[0]), width=intr.width, height=intr.height,
                tracking_fps=stats["tracked"] / max(stats["track_s"], 1e-9),
                tracking_iters_per_s=stats["track_iters"] / max(stats["track_s"], 1e-9),
