@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define MGS_ABI_VERSION 17
+#define MGS_ABI_VERSION 18
 #define MGS_TILE 16 /* tile edge in pixels; ranges are per 16x16 tile */
 
 /* GaussianRasterizationSettings, minus `prefiltered` / `debug` which are call flags
@@ -654,6 +654,82 @@ size_t mgs_grad_mask_scratch_bytes(int32_t width, int32_t height);
 int mgs_grad_mask(int32_t width, int32_t height, const float* rgb /* [3,H,W] */, float edge_threshold, float eps,
                   void* scratch, uint8_t* grad_mask_out /* [H,W] */, float* intensity_out /* [H,W] or NULL */, void* stream);
 int mgs_frame_prepare(const MgsFramePrepare* params, void* stream);
+
+/* ---- Stereo depth: semi-global matching of a rectified grey pair (ABI v18) --------------------------------------
+ * What StereoDataset.__getitem__ (/root/reference/utils/dataset.py:595-629) does per frame -- rectify both grey images, run
+ * StereoSGBM (64 disparities, block 20, uniqueness 40), turn the disparity into metric depth with a fixed baseline x fx -- as
+ * twelve stream-ordered launches: no host synchronisation, no state between calls, nothing assumed about the contents of
+ * scratch or outputs on entry, no atomics, every loop bounded by a launch parameter, no workgroup waits for another;
+ * capturable in a hipGraph as a linear chain of kernel nodes.
+ *
+ * cv2 is not available to this project: the steps below are written from OpenCV's documented behaviour (mode MODE_SGBM,
+ * minDisparity 0, no speckle filter) and ARE the specification; parity with cv2.StereoSGBM / cv2.remap is UNPINNED.  All
+ * arithmetic up to disp16 is integer; the kernels are bit-exact against an integer restatement (tests/stereo_mirror.py).
+ *
+ *   L, R: uint8 [H][W].  D = num_disparities in {16, 32, 48, 64}.  Valid columns x in [D, W); W1 = W - D >= 1; H >= 1.
+ *   Defaulting: block_size <= 0 -> 5; s = block_size / 2, window (2s+1)^2; p1 <= 0 -> 2; p2 <= 0 -> 5, then p2 = max(p2, p1+1);
+ *            uniqueness_ratio < 0 -> 10; disp12_max_diff <= 0 -> 1; ftzero = max(pre_filter_cap, 15) | 1.
+ *   0 rectify (all four maps given; otherwise the images are taken as they are): the 8-bit INTER_LINEAR remap of
+ *            mgs_frame_prepare -- 1/32-pixel coordinates, weights summing to 2^15, constant-zero border, no map value reads
+ *            outside the source -- on the single grey channel, with per-image float maps [H][W].
+ *            rgb_out[c][y][x] = float32(double(g) / 255.0), g the rectified LEFT grey value, c = 0, 1, 2 (dataset.py:614-620).
+ *   1 pre-filter, per image: g = (I[y-1][x+1] - I[y-1][x-1]) + 2 (I[y][x+1] - I[y][x-1]) + (I[y+1][x+1] - I[y+1][x-1]), rows
+ *            clamped to the image; P[y][x] = clip(g, -ftzero, ftzero) + ftzero; P[y][0] = P[y][W-1] = ftzero.
+ *   2 pixel cost (Birchfield-Tomasi), for J in {P, I}, x in [D, W), d in [0, D), xr = x - d: u = Jl[x], ul = (u + Jl[x-1]) / 2,
+ *            ur = (u + Jl[x+1]) / 2 (integer, x +- 1 clamped to the row), u0 = min(ul, ur, u), u1 = max(ul, ur, u); v, v0, v1
+ *            the same of Jr at xr; c0 = max(0, u - v1, v0 - u), c1 = max(0, v - u1, u0 - v), cost_J = min(c0, c1).
+ *            pc = cost_P + cost_I <= 2 ftzero + 255.
+ *   3 window: C(y,x,d) = sum over dy, dx in [-s, s] of pc(clamp(y+dy, 0, H-1), clamp(x+dx, D, W-1), d)
+ *            <= (2s+1)^2 (2 ftzero + 255): 125 685 at the reference's settings, which does NOT fit 16 bits (OpenCV's short
+ *            would wrap; this does not: row sums are uint16, C is uint32).
+ *   4 paths, five directions r (from the left, up-left, above, up-right, the right), q = p - r, m = min_k L_r(q,k):
+ *            L_r(p,d) = C(p,d) + min(L_r(q,d), L_r(q,d-1) + P1, L_r(q,d+1) + P1, m + P2) - m, L_r(q,-1) = L_r(q,D) = +inf;
+ *            a predecessor outside [D,W) x [0,H) has L_r(q,.) = 0 (a path starts with L = C).  S = sum_r L_r <= 5 (C + P2).
+ *   5 winner, per row, x from W-1 down to D: best = the lowest d minimising S(y,x,.), minS that minimum; the pixel is invalid
+ *            if some d has S(d) (100 - uniqueness_ratio) < minS 100 and |best - d| > 1.  Passing pixels update the right-view
+ *            table at x2 = x - best: if cost2[x2] > minS then cost2[x2] = minS, disp2[x2] = best (initially +inf, -1: among
+ *            equal costs the largest x wins).  If 0 < best < D-1: den = max(S(best-1) + S(best+1) - 2 S(best), 1),
+ *            d16 = 16 best + ((S(best-1) - S(best+1)) 16 + den) / (2 den), truncating toward zero; otherwise d16 = 16 best.
+ *            Invalid pixels and every column x < D get d16 = -16.
+ *   6 left-right check, after the whole row's step 5, for a valid d16: a = d16 >> 4, b = (d16 + 15) >> 4; the pixel becomes
+ *            -16 if both disp2[x-a] >= 0 and |disp2[x-a] - a| > disp12_max_diff, and the same of b; an index outside
+ *            [0, W) counts as disp2 < 0.
+ *   7 disp16_out (int16 [H][W]) = the 3x3 median of that image, replicate border, -16 taking part as a number.
+ *   8 depth_out (float [H][W]): disp = double(disp16) / 16.0; 0 -> 1e10; depth = bf / disp in double; < 0 -> 0; float32
+ *            (dataset.py:608-613; the reference's bf is MGS_EUROC_BF).
+ *
+ * Bounds: block_size <= 63 (2s+1 <= 63, so a row sum <= 63 x 509 fits uint16), pre_filter_cap <= 127 (P is 8-bit), p1, p2 <=
+ * 2^20, uniqueness_ratio <= 100; then C <= 2 020 221, S < 2^24, and S x 100 and (S << 6 | d) fit 32 bits.
+ * (W - D) x H x D must stay below 2^31.
+ * Launches: prepare, pre-filter, row sums, column sums, five paths, winner, table, finish = 12.
+ * scratch: mgs_stereo_scratch_bytes(width, height, num_disparities) bytes (pure, monotone in each argument; 256 for sizes
+ * the entry point refuses), 16-byte aligned: 178 944 256 bytes at 752 x 480 x 64 (two uint32 volumes of 84.5 MB).
+ * Optional outputs: left_rect_out / right_rect_out (uint8 [H][W], the images after step 0); sum_out (int32 [H][W-D][D], the S
+ * volume, for tests; NULL in the product).
+ * Refused with 1 and a message before anything is launched: NULL params or a NULL required pointer (left_u8, right_u8,
+ * rgb_out, disp16_out, depth_out, scratch), some but not all of the four maps, num_disparities not one of 16, 32, 48, 64,
+ * width <= num_disparities, height < 1, a parameter beyond the bounds above, a bf that is not finite, a misaligned scratch. */
+#define MGS_EUROC_BF 47.90639384423901
+typedef struct MgsStereo {
+    int32_t width, height, num_disparities;
+    int32_t block_size, p1, p2, uniqueness_ratio, disp12_max_diff, pre_filter_cap;
+    double bf;                    /* baseline x fx */
+    const uint8_t* left_u8;       /* [H][W] */
+    const uint8_t* right_u8;      /* [H][W] */
+    const float* map_lx;          /* [H][W] or NULL: all four maps or none */
+    const float* map_ly;
+    const float* map_rx;
+    const float* map_ry;
+    float* rgb_out;               /* [3][H][W] */
+    int16_t* disp16_out;          /* [H][W] */
+    float* depth_out;             /* [H][W] */
+    uint8_t* left_rect_out;       /* [H][W] or NULL */
+    uint8_t* right_rect_out;      /* [H][W] or NULL */
+    int32_t* sum_out;             /* [H][W-D][D] or NULL */
+    void* scratch;                /* mgs_stereo_scratch_bytes(...) bytes, 16-byte aligned */
+} MgsStereo;
+size_t mgs_stereo_scratch_bytes(int32_t width, int32_t height, int32_t num_disparities);
+int mgs_stereo_depth(const MgsStereo* params, void* stream);
 
 #ifdef __cplusplus
 }

@@ -8,4 +8,8 @@ def __getattr__(name):
     if name in ("render_features", "FeatureRasterizer"):
         from . import feature_render
         return getattr(feature_render, name)
+    # the stereo front end (monogs_amd.stereo) likewise
+    if name in ("StereoMatcher", "StereoIngest", "EuRoCParser", "StereoDataset", "load_stereo_dataset", "rectify_map"):
+        from . import stereo
+        return getattr(stereo, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

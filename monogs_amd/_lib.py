@@ -11,7 +11,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MGS_LIB_PATH") or os.path.join(_HERE, "lib", "libmonogs_raster.so")   # (override: kernel experiments)
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 c_float_p = C.c_void_p   # device pointers travel as integers (tensor.data_ptr())
 
@@ -48,6 +48,13 @@ class MgsFramePrepare(C.Structure):
                 ("masked_ids", C.c_uint32 * 8), ("rgb_out", C.c_void_p), ("depth_out", C.c_void_p), ("mask_out", C.c_void_p),
                 ("grad_mask_out", C.c_void_p), ("intensity_out", C.c_void_p), ("edge_threshold", C.c_float), ("eps", C.c_float),
                 ("scratch", C.c_void_p)]
+
+
+class MgsStereo(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("width", "height", "num_disparities", "block_size", "p1", "p2", "uniqueness_ratio",
+                                         "disp12_max_diff", "pre_filter_cap")] + [("bf", C.c_double)] + [
+        (n, C.c_void_p) for n in ("left_u8", "right_u8", "map_lx", "map_ly", "map_rx", "map_ry", "rgb_out", "disp16_out",
+                                  "depth_out", "left_rect_out", "right_rect_out", "sum_out", "scratch")]
 
 
 # symbol -> (restype, argtypes); exactly the declarations of include/monogs_raster.h
@@ -122,6 +129,8 @@ SIGNATURES = {
     "mgs_grad_mask_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "mgs_grad_mask": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_float, C.c_float] + [C.c_void_p] * 4),
     "mgs_frame_prepare": (C.c_int, [C.POINTER(MgsFramePrepare), C.c_void_p]),
+    "mgs_stereo_scratch_bytes": (C.c_size_t, [C.c_int32] * 3),
+    "mgs_stereo_depth": (C.c_int, [C.POINTER(MgsStereo), C.c_void_p]),
 }
 
 _lib = None

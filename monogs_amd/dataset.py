@@ -6,7 +6,8 @@ parses the lists and decodes the files with PIL, everything after the decode is 
 device.  trimesh is replaced by the quaternion formula it was used for, cv2 by ``frame_ingest.undistort_map`` and the remap
 inside ``mgs_frame_prepare`` (parity with cv2 unpinned: it is not available to this project).
 
-What stays out: the Kubric (TIFF depth) and DAVIS (no depth) parsers, EuRoC stereo (SGBM block matching), RealSense, and
+EuRoC stereo lives in ``monogs_amd.stereo`` (``load_stereo_dataset``: the reader and semi-global matching in HIP); ``load_dataset``
+here keeps refusing ``type: euroc``.  What stays out: the Kubric (TIFF depth) and DAVIS (no depth) parsers, RealSense, and
 monocular operation of the harness -- ``dataset_frames`` refuses a dataset without depth.
 """
 from __future__ import annotations

@@ -4,7 +4,8 @@ stand-in; the TUM / Replica sequences are not available offline).  Prints one JS
   python tools/slam_bench.py --config tum      # 640x480, tracking 100 / mapping 150 / window 8 / kf 5
   python tools/slam_bench.py --config replica  # 1200x680, tracking 100 / mapping 150 / window 10 / kf 4
   python tools/slam_bench.py --config tum --dataset CONFIG.yaml --frames 200 [--stride 2]
-      # a TUM / Replica sequence on disk (monogs_amd.dataset): size and intrinsics from the YAML, iteration counts from --config
+      # a TUM / Replica sequence on disk (monogs_amd.dataset), or an EuRoC stereo one (Dataset.sensor_type: stereo,
+      # monogs_amd.stereo): size and intrinsics from the YAML, iteration counts from --config
 """
 import argparse
 import json
@@ -54,7 +55,7 @@ if __name__ == "__main__":
     ap.add_argument("--eval", action="store_true",
                     help="PSNR / SSIM on every fifth non-keyframe before and after the refinement, and the ATE statistics")
     ap.add_argument("--dataset", default=None, metavar="CONFIG.yaml",
-                    help="run on the TUM / Replica sequence this reference-style YAML names (Dataset.type, dataset_path, "
+                    help="run on the TUM / Replica / EuRoC sequence this reference-style YAML names (Dataset.type, dataset_path, "
                          "Calibration) instead of a synthetic one: --frames frames from the first, every --stride-th")
     ap.add_argument("--stride", type=int, default=1, help="with --dataset: take every N-th frame")
     a = ap.parse_args()
@@ -70,8 +71,11 @@ if __name__ == "__main__":
             cfg[k] = v
     sequence = None
     if a.dataset:
-        from monogs_amd.dataset import dataset_frames, load_dataset
-        sequence = dataset_frames(load_dataset(a.dataset, device="cuda:0"), a.frames, device="cuda:0", stride=a.stride)
+        from monogs_amd.dataset import dataset_frames, load_config, load_dataset
+        config = load_config(a.dataset)
+        if config["Dataset"].get("sensor_type") == "stereo":     # EuRoC: depth from semi-global matching (monogs_amd.stereo)
+            from monogs_amd.stereo import load_stereo_dataset as load_dataset
+        sequence = dataset_frames(load_dataset(config, device="cuda:0"), a.frames, device="cuda:0", stride=a.stride)
         cfg.pop("intrinsics")                           # (the YAML's calibration is the camera)
     out = run_slam(sequence=sequence, n_frames=a.frames, init_itr_num=init_iters, n_gaussians=a.gaussians, graph_tracking=a.graph,
                    graph_mapping=a.graph and not a.eager_mapping, track_lookahead=a.lookahead, map_surgery=a.surgery,
