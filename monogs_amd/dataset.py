@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from .frame_ingest import FrameIngest
+from .frames import Intrinsics, Viewpoint
 
 MAX_DT = 0.08          # s: a colour frame needs a depth frame and a pose this close (dataset.py:148)
 FRAME_RATE = 32.0      # Hz: kept colour frames are more than 1 / 32 s apart (dataset.py:138,186-191)
@@ -199,10 +200,9 @@ def load_dataset(config, device="cuda:0", preload: bool = False) -> MonocularDat
 
 
 def dataset_frames(dataset: MonocularDataset, n_frames: int, device="cuda:0", start: int = 0, stride: int = 1):
-    """``(frames, intr)`` as ``slam_harness.make_room_sequence`` returns them: ``Viewpoint`` objects over the frames ``start,
+    """``(frames, intr)`` as ``sequences.make_room_sequence`` returns them: ``frames.Viewpoint`` objects over the frames ``start,
     start + stride, ...`` of the dataset, the ground-truth ``R`` / ``T`` from the world-to-camera pose and the ingest's ``mask``
     / ``grad_mask`` in place of recomputed ones."""
-    from .slam_harness import Intrinsics, Viewpoint
     if not dataset.with_depth:
         raise ValueError("dataset_frames needs depth (depth files and Calibration.use_depth): the harness is RGB-D")
     idx = list(range(int(start), len(dataset), int(stride)))[:int(n_frames)]

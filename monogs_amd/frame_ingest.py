@@ -101,7 +101,7 @@ def grad_mask_scratch(width: int, height: int, device) -> torch.Tensor:
 def grad_mask(rgb: torch.Tensor, edge_threshold: float = EDGE_THRESHOLD, eps: float = GRAD_EPS,
               scratch: Optional[torch.Tensor] = None, return_intensity: bool = False):
     """``compute_grad_mask`` of a ``[3,H,W]`` float32 device image through ``mgs_grad_mask``: a drop-in for
-    ``slam_harness.scharr_grad_mask`` (bool ``[H,W]``), eight launches, no host synchronisation.  With ``return_intensity`` the
+    ``frames.scharr_grad_mask`` (bool ``[H,W]``), eight launches, no host synchronisation.  With ``return_intensity`` the
     pair ``(grad_mask, intensity)``."""
     _require_device(rgb, "grad_mask")
     if rgb.dim() != 3 or rgb.shape[0] != 3 or rgb.dtype != torch.float32:

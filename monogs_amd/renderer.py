@@ -6,7 +6,7 @@ duck-typed: ``viewpoint_camera`` needs ``world_view_transform``, ``camera_center
 ``cam_rot_delta``, ``cam_trans_delta``; ``cam_intrinsics`` needs ``FoVx``, ``FoVy``, ``height``,
 ``width``, ``projection_matrix`` -- the reference's own CameraExtrinsics / CameraIntrinsics
 (/root/reference/utils/camera_utils.py:8-79,82-221) satisfy this, as do the light-weight
-stand-ins in ``monogs_amd.slam_harness``.
+stand-ins in ``monogs_amd.frames``.
 """
 from __future__ import annotations
 

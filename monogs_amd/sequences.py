@@ -1,0 +1,136 @@
+"""Synthetic RGB-D sequences with ground-truth poses, for the measurements whose datasets (BASELINE configs 3-4) are not
+available offline: an opaque box room ray-cast analytically (``make_room_sequence``: what bench.py runs, survives the
+reference's pruning) and, historically, a seeded cloud of Gaussians rendered by the rasteriser itself (``make_sequence``).
+A sequence on disk comes from ``monogs_amd.dataset.dataset_frames`` in the same ``(frames, intr)`` form."""
+from __future__ import annotations
+
+import math
+from typing import List
+
+import torch
+
+from . import camera as cam
+from .frames import Intrinsics, Viewpoint
+from .gaussian_map import GaussianMap
+from .mapping import render_map
+from .synthetic import make_scene
+
+
+def make_sequence(n_frames: int, intrinsics="fr3_office", n_gaussians=60000, seed=11, device="cuda:0"):
+    """Ground-truth map + a smooth camera path; frames rendered by the rasteriser itself."""
+    sc = make_scene(n_gaussians, intrinsics, seed=seed, near_fraction=0.0, mean_radius_px=9.0, device=device)
+    intr = Intrinsics(sc.intr, device)
+    gt = GaussianMap(device)
+    gt._xyz, gt._rgb = sc.means3D, sc.colors
+    gt._opacity = torch.logit(sc.opacities.clamp(0.05, 0.95) * 0 + 0.9)     # mostly opaque surface-like splats
+    gt._scaling, gt._rotation = torch.log(sc.scales), sc.rotations
+    bg = torch.zeros(3, device=device)
+    T0 = torch.eye(4, device=device)
+    T0[:3, :3], T0[:3, 3] = sc.R, sc.t
+    frames: List[Viewpoint] = []
+    with torch.no_grad():
+        for i in range(n_frames):
+            d = cam.se3_exp(torch.tensor([0.004 * i, -0.002 * i, 0.001 * i, 0.0, 0.0015 * i, 0.0005 * i], device=device))
+            Tm = d @ T0
+            vp = Viewpoint(i, torch.zeros(3, intr.height, intr.width, device=device),
+                           torch.ones(intr.height, intr.width, device=device), device)
+            vp.update_RT(Tm[:3, :3], Tm[:3, 3])
+            pkg = render_map(vp, intr, gt, bg)
+            depth = torch.where(pkg["opacity"][0] > 0.5, pkg["depth"][0] / pkg["opacity"][0].clamp_min(1e-6),
+                                torch.zeros_like(pkg["depth"][0]))
+            frames.append(Viewpoint(i, pkg["render"].clamp(0, 1), depth, device, gt_R=Tm[:3, :3], gt_T=Tm[:3, 3]))
+    return frames, intr
+
+
+# ---- an OPAQUE-surface stand-in: a box room with furniture, ray-cast analytically -----------------------------------------
+# The cloud of `make_sequence` is semi-transparent by construction (its "depth" is a blend over several layers), so a map
+# fitted to it never gets past the reference's 0.7 opacity pruning threshold.  A real sequence shows opaque surfaces: this
+# one is a 6 x 3 x 6 m room with four boxes standing in it, every pixel's colour and z-depth computed in closed form
+# (ray / axis-aligned-box intersection, a procedural texture of the hit point), seen from a hand-held-like camera path.
+_ROOM_HALF = (3.0, 1.5, 3.0)
+_ROOM_BOXES = (   # (lo, hi) in world metres; y points down in the first camera, the floor is y = +1.5
+    ((-2.4, 0.55, 1.1), (-0.9, 1.5, 2.3)),      # a desk
+    ((0.9, -0.3, 1.8), (1.9, 1.5, 2.8)),        # a cabinet
+    ((-0.5, 0.9, 0.9), (0.4, 1.5, 1.6)),        # a crate in front
+    ((2.2, 0.2, -0.5), (3.0, 1.5, 0.9)),        # a shelf on the right wall
+)
+
+
+def _room_texture(p, axis, sid):
+    """Colour of the surface point ``p`` [N,3] whose normal is along ``axis`` [N]; ``sid`` [N] picks the base colour."""
+    dev = p.device
+    ia = torch.where(axis == 0, 1, 0)
+    ib = torch.where(axis == 2, 1, 2)
+    a = torch.gather(p, 1, ia[:, None])[:, 0]
+    b = torch.gather(p, 1, ib[:, None])[:, 0]
+    base = torch.tensor([[0.78, 0.72, 0.62], [0.55, 0.66, 0.80], [0.70, 0.80, 0.62], [0.82, 0.60, 0.58], [0.60, 0.60, 0.72],
+                         [0.85, 0.80, 0.55], [0.50, 0.72, 0.70], [0.75, 0.55, 0.75], [0.62, 0.78, 0.85], [0.80, 0.68, 0.50]],
+                        device=dev)[sid % 10]
+    two_pi = 2.0 * math.pi
+    ph = sid.to(torch.float32) * 1.7
+    slow = 0.5 + 0.5 * torch.sin(two_pi * 0.45 * a + ph) * torch.sin(two_pi * 0.38 * b + 0.6 * ph)
+    # a soft checker (edges 3 cm wide) and a fine weave: image gradients everywhere, as a textured office has
+    chk = torch.tanh(torch.sin(two_pi * a / 0.8) * torch.sin(two_pi * b / 0.8) * 12.0)
+    fine = torch.sin(two_pi * a / 0.11 + ph) * torch.sin(two_pi * b / 0.13)
+    lum = 0.62 + 0.16 * slow + 0.14 * chk + 0.06 * fine
+    tint = torch.stack([torch.sin(two_pi * 0.21 * a + ph), torch.sin(two_pi * 0.17 * b + 2.0 + ph),
+                        torch.sin(two_pi * 0.13 * (a + b) + 4.0)], 1) * 0.08
+    return (base * lum[:, None] + tint).clamp(0.02, 0.98)
+
+
+ROOM_SURFACES = 6 + 3 * len(_ROOM_BOXES)       # surface ids raycast_room can return: six walls, three face axes per box
+
+
+@torch.no_grad()
+def raycast_room(R, t, k, device, with_ids=False):
+    """(rgb [3,H,W], depth [H,W]) of the room seen by the world->camera pose (R, t); ``with_ids``: also the id [H,W] (int32,
+    below ``ROOM_SURFACES``) of the surface every ray hit.  Pixel (x, y) looks along
+    ((x + 0.5 - cx) / fx, (y + 0.5 - cy) / fy, 1): the rasteriser's pixel convention (``px = fx X/Z + cx - 0.5``) and the
+    back-projection's (/root/reference/gaussian_splatting/scene/gaussian_model.py:232-236)."""
+    H, W = k["H"], k["W"]
+    ys, xs = torch.meshgrid(torch.arange(H, device=device, dtype=torch.float32),
+                            torch.arange(W, device=device, dtype=torch.float32), indexing="ij")
+    dc = torch.stack([(xs + 0.5 - k["cx"]) / k["fx"], (ys + 0.5 - k["cy"]) / k["fy"], torch.ones_like(xs)], -1).reshape(-1, 3)
+    R, t = R.to(device), t.to(device)
+    o = -(R.t() @ t)
+    d = dc @ R                                            # R^T d, row form
+    d = torch.where(d.abs() < 1e-9, torch.full_like(d, 1e-9), d)
+    half = torch.tensor(_ROOM_HALF, device=device)
+    t_wall = (torch.where(d > 0, half, -half) - o) / d    # the room from inside: the nearest exit plane
+    best, axis = t_wall.min(dim=1)
+    sid = axis * 2 + (torch.gather(d, 1, axis[:, None])[:, 0] > 0).long()
+    for bi, (lo, hi) in enumerate(_ROOM_BOXES):
+        lo, hi = torch.tensor(lo, device=device), torch.tensor(hi, device=device)
+        t1, t2 = (lo - o) / d, (hi - o) / d
+        tn, ax = torch.minimum(t1, t2).max(dim=1)
+        tf = torch.maximum(t1, t2).min(dim=1).values
+        hit = (tn < tf) & (tn > 1e-3) & (tn < best)
+        best = torch.where(hit, tn, best)
+        axis = torch.where(hit, ax, axis)
+        sid = torch.where(hit, 6 + bi * 3 + ax, sid)
+    p = o + best[:, None] * d
+    rgb = _room_texture(p, axis, sid)
+    if with_ids:
+        return rgb.t().reshape(3, H, W).contiguous(), best.reshape(H, W).contiguous(), sid.to(torch.int32).reshape(H, W).contiguous()
+    return rgb.t().reshape(3, H, W).contiguous(), best.reshape(H, W).contiguous()
+
+
+def make_room_sequence(n_frames: int, intrinsics="fr3_office", device="cuda:0", step_scale: float = 1.0,
+                       with_segmentation: bool = False):
+    """``n_frames`` RGB-D frames of the room along a smooth hand-held-like path (about 1 cm and 0.3 degrees per frame at
+    ``step_scale`` 1: the inter-frame motion of a 30 Hz TUM sequence), ground-truth poses attached.  ``with_segmentation``:
+    every frame also carries ``segmentation``, the id of the surface each pixel's ray hit (``raycast_room``)."""
+    k = dict(cam.INTRINSICS[intrinsics]) if isinstance(intrinsics, str) else dict(intrinsics)
+    intr = Intrinsics(k, device)
+    frames: List[Viewpoint] = []
+    for i in range(n_frames):
+        s = step_scale * i
+        c = torch.tensor([0.35 * math.sin(0.022 * s) - 0.2, 0.05 * math.sin(0.05 * s) + 0.1, -1.6 + 0.25 * (1 - math.cos(0.02 * s))])
+        yaw, pitch = 0.0055 * s - 0.1, 0.05 + 0.03 * math.sin(0.04 * s)
+        Rwc = cam.so3_exp(torch.tensor([0.0, yaw, 0.0])) @ cam.so3_exp(torch.tensor([pitch, 0.0, 0.0]))   # camera -> world
+        Rcw = Rwc.t().contiguous()
+        tcw = -(Rcw @ c)
+        rgb, depth, *seg = raycast_room(Rcw, tcw, k, device, with_ids=with_segmentation)
+        frames.append(Viewpoint(i, rgb, depth, device, gt_R=Rcw.to(device), gt_T=tcw.to(device),
+                                segmentation=seg[0] if seg else None))
+    return frames, intr

@@ -827,7 +827,8 @@ def test_tracking_graph_close_leaves_other_owners_words_alone(native_lib):
     from monogs_amd.gaussian_map import GaussianMap
     from monogs_amd.rasterizer import GaussianRasterizer
     from monogs_amd.renderer import raster_settings
-    from monogs_amd.slam_harness import TrackingGraph, make_sequence
+    from monogs_amd.sequences import make_sequence
+    from monogs_amd.tracking import TrackingGraph
     frames, intr = make_sequence(1, "fr3_office", n_gaussians=20000, device=DEV)
     vp = frames[0]
     vp.update_RT(vp.R_gt.clone(), vp.T_gt.clone())

@@ -312,7 +312,8 @@ def _quaternion(R):
 def test_tum_directory_round_trip_and_a_short_slam_run(native_lib, tmp_path):
     from PIL import Image
     from monogs_amd.dataset import dataset_frames, load_dataset
-    from monogs_amd.slam_harness import make_room_sequence, run_slam
+    from monogs_amd.sequences import make_room_sequence
+    from monogs_amd.slam_harness import run_slam
     k = dict(fx=535.4 / 8, fy=539.2 / 8, cx=320.1 / 8, cy=247.6 / 8, W=80, H=60)
     src, _ = make_room_sequence(12, k, device=DEV)
     os.makedirs(tmp_path / "rgb"), os.makedirs(tmp_path / "depth")

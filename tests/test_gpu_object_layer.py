@@ -158,12 +158,14 @@ def test_object_map_end_to_end(native_lib):
     last keyframe must beat the always-guess-the-majority answer, computed here from the ground truth.
     Measured on the MI355X: accuracy 0.96 on every pixel of the frame against a majority share of 0.49 (11 surfaces in view)."""
     from monogs_amd import render_features
-    from monogs_amd.slam_harness import ROOM_SURFACES, _render, make_room_sequence, run_slam
+    from monogs_amd.mapping import render_map
+    from monogs_amd.sequences import ROOM_SURFACES, make_room_sequence
+    from monogs_amd.slam_harness import run_slam
     r = run_slam(nr_objects=ROOM_SURFACES, **ROOM)
     gmap, frames, intr = r["map"], r["frame_list"], r["intr"]
     assert gmap._obj_prob.shape == (len(gmap), ROOM_SURFACES) and len(gmap) == r["gaussians"]
     vp = frames[10]                                        # the last keyframe (every second frame is one)
-    pkg = _render(vp, intr, gmap, torch.zeros(3, device=DEV))
+    pkg = render_map(vp, intr, gmap, torch.zeros(3, device=DEV))
     feat, labels = render_features(pkg["render"], gmap.get_obj_prob, want_labels=True)
     assert feat.shape == (ROOM_SURFACES, 120, 160)
     gt = vp.segmentation.long()

@@ -44,7 +44,9 @@ def test_graph_tracking_equals_eager_tracking(native_lib):
     from monogs_amd.mapping import WindowMapper
     from monogs_amd.pose_optim import PoseAdam
     from monogs_amd.renderer import render
-    from monogs_amd.slam_harness import TrackingGraph, Viewpoint, make_sequence
+    from monogs_amd.frames import Viewpoint
+    from monogs_amd.sequences import make_sequence
+    from monogs_amd.tracking import TrackingGraph
     dev = "cuda:0"
     frames, intr = make_sequence(3, "fr3_office", n_gaussians=30000, device=dev)
     bg = torch.zeros(3, device=dev)

@@ -35,7 +35,7 @@ def room_workload(dev):
     from monogs_amd.gaussian_map import GaussianMap
     from monogs_amd.mapping import WindowMapper
     from monogs_amd.renderer import render
-    from monogs_amd.slam_harness import make_room_sequence
+    from monogs_amd.sequences import make_room_sequence
     frames, intr = make_room_sequence(1, "fr3_office", device=dev)
     vp = frames[0]
     vp.update_RT(vp.R_gt.clone(), vp.T_gt.clone())

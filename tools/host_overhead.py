@@ -9,7 +9,7 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
-from monogs_amd.slam_harness import Intrinsics, Viewpoint
+from monogs_amd.frames import Intrinsics, Viewpoint
 from monogs_amd.renderer import render
 from monogs_amd.synthetic import make_scene
 from monogs_amd import fused_losses

@@ -2,7 +2,7 @@
 """Device time per frame of the frame ingest (monogs_amd.frame_ingest.FrameIngest.prepare_device: mgs_frame_prepare, nine
 launches) at the TUM and Replica sizes, with and without the undistortion maps, beside the torch composition that does the
 same work for the undistorted case on the same device inputs: ``/ 255``, permute, depth ``/ depth_scale``, a mask of ones and
-``slam_harness.scharr_grad_mask`` (pad, three convolutions, elementwise operations, ``torch.median``).
+``frames.scharr_grad_mask`` (pad, three convolutions, elementwise operations, ``torch.median``).
 
 Every call is timed on its own with a pair of device events, after --warmup calls of each variant; the variants alternate call
 by call inside one process and the figure is the median of --calls calls (min and max beside it).  The uploads are not in the
@@ -95,7 +95,7 @@ def main():
     if args.calls < 50:
         sys.exit("--calls must be at least 50")
     from monogs_amd.frame_ingest import FrameIngest
-    from monogs_amd.slam_harness import scharr_grad_mask
+    from monogs_amd.frames import scharr_grad_mask
     dev = "cuda:0"
     results = []
     for size in args.sizes.split(","):
