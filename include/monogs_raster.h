@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define MGS_ABI_VERSION 18
+#define MGS_ABI_VERSION 19
 #define MGS_TILE 16 /* tile edge in pixels; ranges are per 16x16 tile */
 
 /* GaussianRasterizationSettings, minus `prefiltered` / `debug` which are call flags
@@ -349,9 +349,16 @@ int mgs_dist2_knn(int32_t P, const float* points /* [P,3] */, float* out /* [P] 
  * d_exposure[2] = (dL/da, dL/db; may be NULL), all scaled by the device scalar grad_out (NULL = 1).
  * The opacity image gets no gradient (the rasteriser ignores dL/dopacity).
  * d_exposure is STORED (scale x the unscaled sums the forward kept in its per-workgroup partials: no atomics, no clear,
- * bitwise reproducible); it may be the two floats at scratch + MGS_LOSS_SCRATCH_DAB. */
+ * bitwise reproducible); it may be the two floats at scratch + MGS_LOSS_SCRATCH_DAB.
+ * MGS_LOSS_RGB_ONLY (ABI v19; monocular frames, a [RECALL] of upstream MonoGS' get_loss_tracking_rgb / get_loss_mapping_rgb):
+ * the depth term is dropped and with it its images -- depth, gt_depth and d_depth may be NULL and are never read; a non-NULL
+ * d_depth is zero-filled (a memset node).  Tracking: L = 0.5 mean(opacity) mean_{3HW}(m |rgb - gt|), m = mask grad_mask
+ * (opacity > 0.99).  Mapping: L = mean_{mask, 3 ch} |rgb - gt|; lambda_rgb is ignored (coefficient 1).  The colour sums are
+ * formed exactly as without the bit: the results equal, bit for bit, the tracking mode on gt_depth = 0 and the mapping mode
+ * on lambda_rgb = 1 with an all-positive gt_depth.  MGS_LOSS_INVERT_DEPTH has nothing to act on then and is ignored. */
 #define MGS_LOSS_TRACKING 1
 #define MGS_LOSS_INVERT_DEPTH 2
+#define MGS_LOSS_RGB_ONLY 4
 #define MGS_LOSS_SCRATCH_DAB 10
 #define MGS_LOSS_SCRATCH_LOSS 12
 size_t mgs_loss_scratch_bytes(void);
@@ -570,6 +577,38 @@ int mgs_covisibility(int32_t P, const int32_t* cur_n_touched, const uint64_t* cu
                      uint32_t* counts /* [K][4] */, void* stream);
 int mgs_keyframe_decide(const MgsKeyframeParams* params, const uint32_t* counts, const float* median,
                         const float* const* poses, uint32_t* out /* [8] */, void* stream);
+
+/* ---- Depth hypothesis of a keyframe without measured depth (ABI v19) ------------------------------------------------
+ * Monocular operation: the image the back-projection reads in place of a sensor's depth, from the keyframe's frozen render.
+ * A [RECALL] of public upstream MonoGS' add_new_keyframe, anchored on what the reference keeps of it
+ * (get_median_depth(..., return_std=True), /root/reference/utils/slam_utils.py:149-157; rgb_boundary_threshold in every config):
+ * parity unpinned.  One stream-ordered call, no host read-back, no state between calls, capturable in a hipGraph.
+ *   valid   = render_depth > 0 && render_opacity > opacity_min && valid_rgb      (a NULL image passes its test everywhere)
+ *   median  = lower median of render_depth[valid] (mgs_masked_median);  std = its UNBIASED standard deviation (torch.std),
+ *             two passes -- mean, then squared deviations -- over per-workgroup double-precision partials added in a fixed
+ *             order: no float atomics, bitwise reproducible;  count = |valid|
+ *   outlier = render_depth > median + std || render_depth < median - std || !valid      (both sums rounded to float32)
+ *   depth_out = (outlier ? median : render_depth) + noise * (outlier ? sigma_out : sigma_in) * std
+ *   init rule -- render_depth == NULL, or count < 2 (std undefined): depth_out = init_mean + init_sigma * noise
+ *   depth_out = 0 exactly where valid_rgb is 0, under either rule.
+ * noise: [H,W] standard normals the caller draws (no generator in the kernel).  stats_out[4] (device floats) = { median, std,
+ * count, used_init_rule (0 / 1) }; under the init rule the first two hold init_mean and init_sigma.  render_opacity is ignored
+ * without render_depth.  scratch: mgs_pseudo_depth_scratch_bytes(W x H) bytes, 256-byte aligned (may be NULL without
+ * render_depth); nothing is assumed about its contents.  Nine launches with a render, one without; the elementwise kernels
+ * read 4-pixel vectors when W x H % 4 == 0 and the images are 16-byte (valid_rgb: 4-byte) aligned, else pixel by pixel.
+ * W x H < 2^32.  Argument errors return 1 with a message before anything is launched. */
+typedef struct MgsPseudoDepthParams {
+    float init_mean;       /* 2.0 */
+    float init_sigma;      /* 0.3 */
+    float opacity_min;     /* 0.95 */
+    float sigma_in;        /* 0.2 */
+    float sigma_out;       /* 0.5 */
+} MgsPseudoDepthParams;
+size_t mgs_pseudo_depth_scratch_bytes(uint64_t n);
+int mgs_pseudo_depth(int32_t width, int32_t height, const float* render_depth /* [H,W] or NULL: init rule */,
+                     const float* render_opacity /* [H,W] or NULL */, const uint8_t* valid_rgb /* [H,W] or NULL */,
+                     const float* noise /* [H,W] */, const MgsPseudoDepthParams* params, void* scratch,
+                     float* depth_out /* [H,W] */, float* stats_out /* [4] */, void* stream);
 
 /* ---- Image metrics of a rendered frame (ABI v15) -------------------------------------------------------------
  * What eval_rendering (/root/reference/utils/eval_utils.py:169-183) computes per evaluated frame, in ONE pass over the render

@@ -11,7 +11,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MGS_LIB_PATH") or os.path.join(_HERE, "lib", "libmonogs_raster.so")   # (override: kernel experiments)
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 c_float_p = C.c_void_p   # device pointers travel as integers (tensor.data_ptr())
 
@@ -55,6 +55,10 @@ class MgsStereo(C.Structure):
                                          "disp12_max_diff", "pre_filter_cap")] + [("bf", C.c_double)] + [
         (n, C.c_void_p) for n in ("left_u8", "right_u8", "map_lx", "map_ly", "map_rx", "map_ry", "rgb_out", "disp16_out",
                                   "depth_out", "left_rect_out", "right_rect_out", "sum_out", "scratch")]
+
+
+class MgsPseudoDepthParams(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ("init_mean", "init_sigma", "opacity_min", "sigma_in", "sigma_out")]
 
 
 # symbol -> (restype, argtypes); exactly the declarations of include/monogs_raster.h
@@ -120,6 +124,8 @@ SIGNATURES = {
     "mgs_dist2_knn": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mgs_median_scratch_bytes": (C.c_size_t, [C.c_uint64]),
     "mgs_masked_median": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_float] + [C.c_void_p] * 4),
+    "mgs_pseudo_depth_scratch_bytes": (C.c_size_t, [C.c_uint64]),
+    "mgs_pseudo_depth": (C.c_int, [C.c_int32, C.c_int32] + [C.c_void_p] * 4 + [C.POINTER(MgsPseudoDepthParams)] + [C.c_void_p] * 4),
     "mgs_covisibility": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
                                    C.c_void_p, C.c_void_p, C.c_void_p]),
     "mgs_keyframe_decide": (C.c_int, [C.POINTER(MgsKeyframeParams), C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p,

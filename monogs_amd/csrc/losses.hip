@@ -11,11 +11,16 @@
 //   tracking:  L = 0.5 * mean(opacity) * mean_{all 3HW} (m |rgb - gt|) + mean_{gt_depth > 0, opacity > 0.99} |depth - gt_depth|
 //              with m = mask * grad_mask * (opacity > 0.99); the depth term is 0 when its mask is empty
 //   rgb = exp(a) * render + b   (exposure; identity when `init`)
+//   RGB-only (MGS_LOSS_RGB_ONLY, monocular frames): the same sums without the depth term and without its two images --
+//              tracking: the formula above minus its last term; mapping: L = mean_{mask, 3 ch} |rgb - gt| (coefficient 1,
+//              upstream MonoGS' get_loss_mapping_rgb).  The colour sums are formed by the very code of the RGB-D modes, so
+//              the values equal, bit for bit, the tracking mode on gt_depth = 0 and the mapping mode on lambda = 1.
 //   invert_depth (slam_utils.py:83-88, :138-141): the depth term compares 1 / (depth + eps) with 1 / (gt_depth + eps),
 //   eps = 1e-6 in the tracking loss and 0 in the mapping loss, as the reference writes them
 //
 // Forward: one reduction kernel (<= 256 workgroups write partial sums) + a one-wave finalize kernel that adds
-// them in a fixed order (no atomics, no memset, bitwise reproducible); backward: one elementwise kernel.  HBM-bound: ~44 B/pixel read forward, ~60 B/pixel backward.
+// them in a fixed order (no atomics, no memset, bitwise reproducible); backward: one elementwise kernel.  HBM-bound: ~44 B/pixel read
+// forward, ~60 B/pixel backward; RGB-only: 8 B/pixel fewer read by either kernel (no depth pair), 4 fewer written by the backward.
 #include "common.h"
 
 namespace mgs {
@@ -34,7 +39,7 @@ enum : int { LP_L1_RGB = 6, LP_L1_D = 7, LP_SCALE_RGB = 8, LP_SCALE_D = 9, LP_DA
 struct LossArgs {
     const float *render, *depth, *opacity, *gt_rgb, *gt_depth, *exp_a, *exp_b;
     const uint8_t *mask, *grad_mask;
-    int W, H, tracking, init, invert_depth;
+    int W, H, tracking, init, invert_depth, rgb_only;
     float lambda_rgb;
 };
 
@@ -73,7 +78,8 @@ __device__ __forceinline__ void fwd_pixel(const LossArgs& a, float ea, float eb,
 
 // VEC4: every image is read four pixels at a time (16-byte loads; needs H*W % 4 == 0 and 16-byte-aligned images): a
 // thread then has all its loads in flight at once instead of ~11 dependent-latency scalar loads per pixel.
-template <bool VEC4>
+// RGB: MGS_LOSS_RGB_ONLY -- depth and gt_depth are never read (they may be NULL); every pixel's depth term is masked out.
+template <bool VEC4, bool RGB>
 __global__ void __launch_bounds__(LS_THREADS) loss_forward_kernel(LossArgs a, float* __restrict__ part) {
     const size_t HW = (size_t)a.W * a.H;
     const float ea = a.init ? 1.f : expf(a.exp_a[0]), eb = a.init ? 0.f : a.exp_b[0];      // (torch.exp: the accurate one)
@@ -84,7 +90,8 @@ __global__ void __launch_bounds__(LS_THREADS) loss_forward_kernel(LossArgs a, fl
         const float4 *R0 = (const float4*)a.render, *R1 = (const float4*)(a.render + HW), *R2 = (const float4*)(a.render + 2 * HW);
         const float4 *G0 = (const float4*)a.gt_rgb, *G1 = (const float4*)(a.gt_rgb + HW), *G2 = (const float4*)(a.gt_rgb + 2 * HW);
         for (size_t q = (size_t)blockIdx.x * LS_THREADS + threadIdx.x; q < NQ; q += stride) {
-            const float4 gd = ((const float4*)a.gt_depth)[q], d = ((const float4*)a.depth)[q];
+            const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+            const float4 gd = RGB ? zero4 : ((const float4*)a.gt_depth)[q], d = RGB ? zero4 : ((const float4*)a.depth)[q];
             const float4 r0 = R0[q], r1 = R1[q], r2 = R2[q], g0 = G0[q], g1 = G1[q], g2 = G2[q];
             const uchar4 mk = a.mask ? ((const uchar4*)a.mask)[q] : make_uchar4(1, 1, 1, 1);
             const uchar4 gm = a.tracking ? ((const uchar4*)a.grad_mask)[q] : make_uchar4(1, 1, 1, 1);
@@ -96,9 +103,9 @@ __global__ void __launch_bounds__(LS_THREADS) loss_forward_kernel(LossArgs a, fl
         }
     } else {
         for (size_t p = (size_t)blockIdx.x * LS_THREADS + threadIdx.x; p < HW; p += stride)
-            fwd_pixel(a, ea, eb, a.gt_depth[p], a.mask ? a.mask[p] != 0 : true, a.tracking ? a.grad_mask[p] != 0 : true,
+            fwd_pixel(a, ea, eb, RGB ? 0.f : a.gt_depth[p], a.mask ? a.mask[p] != 0 : true, a.tracking ? a.grad_mask[p] != 0 : true,
                       a.tracking ? a.opacity[p] : 0.f, a.render[p], a.render[HW + p], a.render[2 * HW + p], a.gt_rgb[p],
-                      a.gt_rgb[HW + p], a.gt_rgb[2 * HW + p], a.depth[p], acc);
+                      a.gt_rgb[HW + p], a.gt_rgb[2 * HW + p], RGB ? 0.f : a.depth[p], acc);
     }
     // the seven sums of the workgroup with ONE pair of barriers (wave sums by shuffles, the four waves' sums through LDS, added
     // in the order ((w0 + w1) + (w2 + w3)) by seven threads)
@@ -134,6 +141,12 @@ __device__ __forceinline__ LossScalars loss_scalars(const LossArgs& a, const flo
         r.scale_rgb = 0.5f * mean_op / (3.f * (float)HW);
         r.scale_d = C_d > 0.f ? 1.f / C_d : 0.f;
         r.loss = 0.5f * r.l1_rgb + r.l1_d;
+    } else if (a.rgb_only) {                            // (lambda_rgb is 1 here: the scale below is the mapping mode's at lambda = 1)
+        r.l1_rgb = S_rgb / C_rgb;
+        r.l1_d = 0.f;
+        r.scale_rgb = a.lambda_rgb / C_rgb;
+        r.scale_d = 0.f;
+        r.loss = r.l1_rgb;
     } else {
         r.l1_rgb = S_rgb / C_rgb;                       // NaN when the mask is empty, like torch's mean of nothing
         r.l1_d = S_d / C_d;
@@ -177,7 +190,8 @@ __global__ void loss_finalize_kernel(LossArgs a, int nblocks, float* __restrict_
 
 // fwd_blocks > 0: "fused" mode -- no finalize kernel ran: every workgroup adds the forward's partial sums up itself (its
 // first wave, fixed order, <= 8 KB out of L2) and workgroup 0 also stores the loss value for whoever wants to log it.
-template <bool VEC4>
+// RGB: MGS_LOSS_RGB_ONLY -- neither depth image is read and d_depth (which may be NULL) is not written.
+template <bool VEC4, bool RGB>
 __global__ void __launch_bounds__(LS_THREADS) loss_backward_kernel(LossArgs a, float* __restrict__ part, int fwd_blocks,
                                                                    const float* __restrict__ grad_out,
                                                                    float* __restrict__ d_render,
@@ -221,11 +235,12 @@ __global__ void __launch_bounds__(LS_THREADS) loss_backward_kernel(LossArgs a, f
             m_rgb = m_rgb && gmask && opaque;
             m_d = m_d && opaque;
         }
-        o0 = o1 = o2 = 0.f;
+        o0 = o1 = o2 = od = 0.f;
         if (m_rgb) {
             const float s0 = sgn(residual(ea, x0, eb, t0)), s1 = sgn(residual(ea, x1, eb, t1)), s2 = sgn(residual(ea, x2, eb, t2));
             o0 = k_rgb * ea * s0; o1 = k_rgb * ea * s1; o2 = k_rgb * ea * s2;
         }
+        if (RGB) return;
         if (a.invert_depth) {                       // d/dd |1/(d + eps) - 1/(gd + eps)| = -sgn(.) / (d + eps)^2
             const float eps = a.tracking ? 1e-6f : 0.f, inv = 1.f / (d + eps);
             od = m_d ? -k_d * sgn(inv - 1.f / (gd + eps)) * (inv * inv) : 0.f;
@@ -239,7 +254,8 @@ __global__ void __launch_bounds__(LS_THREADS) loss_backward_kernel(LossArgs a, f
         const float4 *G0 = (const float4*)a.gt_rgb, *G1 = (const float4*)(a.gt_rgb + HW), *G2 = (const float4*)(a.gt_rgb + 2 * HW);
         float4 *O0 = (float4*)d_render, *O1 = (float4*)(d_render + HW), *O2 = (float4*)(d_render + 2 * HW);
         for (size_t q = (size_t)blockIdx.x * LS_THREADS + threadIdx.x; q < NQ; q += stride) {
-            const float4 gd = ((const float4*)a.gt_depth)[q], d = ((const float4*)a.depth)[q];
+            const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+            const float4 gd = RGB ? zero4 : ((const float4*)a.gt_depth)[q], d = RGB ? zero4 : ((const float4*)a.depth)[q];
             const float4 r0 = R0[q], r1 = R1[q], r2 = R2[q], t0 = G0[q], t1 = G1[q], t2 = G2[q];
             const uchar4 mk = a.mask ? ((const uchar4*)a.mask)[q] : make_uchar4(1, 1, 1, 1);
             const uchar4 gm = a.tracking ? ((const uchar4*)a.grad_mask)[q] : make_uchar4(1, 1, 1, 1);
@@ -250,16 +266,16 @@ __global__ void __launch_bounds__(LS_THREADS) loss_backward_kernel(LossArgs a, f
             pixel(gd.z, mk.z != 0, gm.z != 0, op.z, r0.z, r1.z, r2.z, t0.z, t1.z, t2.z, d.z, o0.z, o1.z, o2.z, od.z);
             pixel(gd.w, mk.w != 0, gm.w != 0, op.w, r0.w, r1.w, r2.w, t0.w, t1.w, t2.w, d.w, o0.w, o1.w, o2.w, od.w);
             O0[q] = o0; O1[q] = o1; O2[q] = o2;
-            ((float4*)d_depth)[q] = od;
+            if (!RGB) ((float4*)d_depth)[q] = od;
         }
     } else {
         for (size_t p = (size_t)blockIdx.x * LS_THREADS + threadIdx.x; p < HW; p += stride) {
             float o0, o1, o2, od;
-            pixel(a.gt_depth[p], a.mask ? a.mask[p] != 0 : true, a.tracking ? a.grad_mask[p] != 0 : true,
+            pixel(RGB ? 0.f : a.gt_depth[p], a.mask ? a.mask[p] != 0 : true, a.tracking ? a.grad_mask[p] != 0 : true,
                   a.tracking ? a.opacity[p] : 0.f, a.render[p], a.render[HW + p], a.render[2 * HW + p], a.gt_rgb[p],
-                  a.gt_rgb[HW + p], a.gt_rgb[2 * HW + p], a.depth[p], o0, o1, o2, od);
+                  a.gt_rgb[HW + p], a.gt_rgb[2 * HW + p], RGB ? 0.f : a.depth[p], o0, o1, o2, od);
             d_render[p] = o0; d_render[HW + p] = o1; d_render[2 * HW + p] = o2;
-            d_depth[p] = od;
+            if (!RGB) d_depth[p] = od;
         }
     }
 }
@@ -281,10 +297,28 @@ static int loss_fwd_grid(int W, int H) {
     return g > LS_MAX_BLOCKS ? LS_MAX_BLOCKS : g;
 }
 
+// the four instantiations of either kernel: (4-pixel vectors or scalar) x (RGB-D or RGB-only)
+static void launch_fwd(const LossArgs& a, bool vec4, int nb, float* partials, hipStream_t s) {
+    auto k = vec4 ? (a.rgb_only ? loss_forward_kernel<true, true> : loss_forward_kernel<true, false>)
+                  : (a.rgb_only ? loss_forward_kernel<false, true> : loss_forward_kernel<false, false>);
+    hipLaunchKernelGGL(k, dim3(nb), dim3(LS_THREADS), 0, s, a, partials);
+}
+static void launch_bwd(const LossArgs& a, bool vec4, float* partials, int fwd_blocks, const float* grad_out, float* d_render,
+                       float* d_depth, float* d_ab, hipStream_t s) {
+    auto k = vec4 ? (a.rgb_only ? loss_backward_kernel<true, true> : loss_backward_kernel<true, false>)
+                  : (a.rgb_only ? loss_backward_kernel<false, true> : loss_backward_kernel<false, false>);
+    hipLaunchKernelGGL(k, dim3(loss_grid(a.W, a.H)), dim3(LS_THREADS), 0, s, a, partials, fwd_blocks, grad_out, d_render, d_depth,
+                       d_ab);
+}
+// RGB-only: the kernel leaves d_depth alone; a caller that passes one gets zeros (a memset node of its own)
+static int clear_rgb_only_depth(const LossArgs& a, float* d_depth, hipStream_t s) {
+    if (a.rgb_only && d_depth) MGS_HIP(hipMemsetAsync(d_depth, 0, (size_t)a.W * a.H * sizeof(float), s));
+    return 0;
+}
+
 int launch_loss_forward(const LossArgs& a, float* partials, float* loss_out, hipStream_t s) {
     const int nb = loss_fwd_grid(a.W, a.H);
-    if (loss_vec4(a, nullptr, nullptr)) hipLaunchKernelGGL(loss_forward_kernel<true>, dim3(nb), dim3(LS_THREADS), 0, s, a, partials);
-    else hipLaunchKernelGGL(loss_forward_kernel<false>, dim3(nb), dim3(LS_THREADS), 0, s, a, partials);
+    launch_fwd(a, loss_vec4(a, nullptr, nullptr), nb, partials, s);
     hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(WAVE), 0, s, a, nb, partials, loss_out);
     MGS_HIP(hipGetLastError());
     return 0;
@@ -293,12 +327,8 @@ int launch_loss_forward(const LossArgs& a, float* partials, float* loss_out, hip
 int launch_loss_backward(const LossArgs& a, float* partials, const float* grad_out, float* d_render,
                          float* d_depth, float* d_ab, hipStream_t s) {
     // (d_ab is STORED by one thread of the kernel: no clear)
-    if (loss_vec4(a, d_render, d_depth))
-        hipLaunchKernelGGL(loss_backward_kernel<true>, dim3(loss_grid(a.W, a.H)), dim3(LS_THREADS), 0, s, a, partials, 0, grad_out,
-                           d_render, d_depth, d_ab);
-    else
-        hipLaunchKernelGGL(loss_backward_kernel<false>, dim3(loss_grid(a.W, a.H)), dim3(LS_THREADS), 0, s, a, partials, 0, grad_out,
-                           d_render, d_depth, d_ab);
+    if (clear_rgb_only_depth(a, d_depth, s)) return 2;
+    launch_bwd(a, loss_vec4(a, d_render, d_depth), partials, 0, grad_out, d_render, d_depth, d_ab, s);
     MGS_HIP(hipGetLastError());
     return 0;
 }
@@ -307,15 +337,10 @@ int launch_loss_backward(const LossArgs& a, float* partials, const float* grad_o
 int launch_loss_grads(const LossArgs& a, float* partials, float* d_render, float* d_depth, hipStream_t s) {
     const int nb = loss_fwd_grid(a.W, a.H);
     float* d_ab = a.init ? nullptr : partials + LP_DAB;
-    if (loss_vec4(a, d_render, d_depth)) {
-        hipLaunchKernelGGL(loss_forward_kernel<true>, dim3(nb), dim3(LS_THREADS), 0, s, a, partials);
-        hipLaunchKernelGGL(loss_backward_kernel<true>, dim3(loss_grid(a.W, a.H)), dim3(LS_THREADS), 0, s, a, partials, nb, nullptr,
-                           d_render, d_depth, d_ab);
-    } else {
-        hipLaunchKernelGGL(loss_forward_kernel<false>, dim3(nb), dim3(LS_THREADS), 0, s, a, partials);
-        hipLaunchKernelGGL(loss_backward_kernel<false>, dim3(loss_grid(a.W, a.H)), dim3(LS_THREADS), 0, s, a, partials, nb, nullptr,
-                           d_render, d_depth, d_ab);
-    }
+    const bool vec4 = loss_vec4(a, d_render, d_depth);
+    if (clear_rgb_only_depth(a, d_depth, s)) return 2;
+    launch_fwd(a, vec4, nb, partials, s);
+    launch_bwd(a, vec4, partials, nb, nullptr, d_render, d_depth, d_ab, s);
     MGS_HIP(hipGetLastError());
     return 0;
 }
@@ -326,21 +351,24 @@ using namespace mgs;
 
 extern "C" {
 
-// `mode`: MGS_LOSS_TRACKING | MGS_LOSS_INVERT_DEPTH (0 = get_loss_mapping)
+// `mode`: MGS_LOSS_TRACKING | MGS_LOSS_INVERT_DEPTH | MGS_LOSS_RGB_ONLY (0 = get_loss_mapping)
 static int fill_args(LossArgs& a, int32_t W, int32_t H, int32_t mode, int32_t init, float lambda_rgb,
                      const float* render, const float* depth, const float* opacity, const float* gt_rgb,
                      const float* gt_depth, const uint8_t* mask, const uint8_t* grad_mask, const float* exp_a,
                      const float* exp_b) {
     if (W <= 0 || H <= 0) { set_error("image size must be positive"); return 1; }
-    if (mode & ~(MGS_LOSS_TRACKING | MGS_LOSS_INVERT_DEPTH)) { set_error("unknown loss mode bits"); return 1; }
-    const int tracking = (mode & MGS_LOSS_TRACKING) ? 1 : 0;
-    if (!render || !depth || !gt_rgb || !gt_depth) { set_error("render, depth, gt_rgb, gt_depth must be non-NULL"); return 1; }
+    if (mode & ~(MGS_LOSS_TRACKING | MGS_LOSS_INVERT_DEPTH | MGS_LOSS_RGB_ONLY)) { set_error("unknown loss mode bits"); return 1; }
+    const int tracking = (mode & MGS_LOSS_TRACKING) ? 1 : 0, rgb_only = (mode & MGS_LOSS_RGB_ONLY) ? 1 : 0;
+    if (!render || !gt_rgb) { set_error("render and gt_rgb must be non-NULL"); return 1; }
+    if (!rgb_only && (!depth || !gt_depth)) { set_error("render, depth, gt_rgb, gt_depth must be non-NULL"); return 1; }
+    if (rgb_only) { depth = gt_depth = nullptr; lambda_rgb = 1.f; }       // never read; the colour term's coefficient is 1
     if (tracking && (!opacity || !grad_mask)) { set_error("tracking loss needs opacity and grad_mask"); return 1; }
     if (!init && (!exp_a || !exp_b)) { set_error("exposure_a / exposure_b must be non-NULL unless init"); return 1; }
     a.render = render; a.depth = depth; a.opacity = opacity; a.gt_rgb = gt_rgb; a.gt_depth = gt_depth;
     a.exp_a = exp_a; a.exp_b = exp_b; a.mask = mask; a.grad_mask = grad_mask;
     a.W = W; a.H = H; a.tracking = tracking; a.init = init; a.lambda_rgb = lambda_rgb;
     a.invert_depth = (mode & MGS_LOSS_INVERT_DEPTH) ? 1 : 0;
+    a.rgb_only = rgb_only;
     return 0;
 }
 
@@ -365,7 +393,7 @@ int mgs_loss_backward(int32_t W, int32_t H, int32_t mode, int32_t init, float la
     LossArgs a;
     if (fill_args(a, W, H, mode, init, lambda_rgb, render, depth, opacity, gt_rgb, gt_depth, mask, grad_mask,
                   exposure_a, exposure_b)) return 1;
-    if (!scratch || !d_render || !d_depth) { set_error("scratch, d_render, d_depth must be non-NULL"); return 1; }
+    if (!scratch || !d_render || (!d_depth && !a.rgb_only)) { set_error("scratch, d_render, d_depth must be non-NULL"); return 1; }
     return launch_loss_backward(a, const_cast<float*>(scratch), grad_out, d_render, d_depth, d_exposure, (hipStream_t)stream);
 }
 
@@ -376,7 +404,7 @@ int mgs_loss_grads(int32_t W, int32_t H, int32_t mode, int32_t init, float lambd
     LossArgs a;
     if (fill_args(a, W, H, mode, init, lambda_rgb, render, depth, opacity, gt_rgb, gt_depth, mask, grad_mask,
                   exposure_a, exposure_b)) return 1;
-    if (!scratch || !d_render || !d_depth) { set_error("scratch, d_render, d_depth must be non-NULL"); return 1; }
+    if (!scratch || !d_render || (!d_depth && !a.rgb_only)) { set_error("scratch, d_render, d_depth must be non-NULL"); return 1; }
     return launch_loss_grads(a, scratch, d_render, d_depth, (hipStream_t)stream);
 }
 

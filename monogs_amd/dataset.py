@@ -7,8 +7,10 @@ device.  trimesh is replaced by the quaternion formula it was used for, cv2 by `
 inside ``mgs_frame_prepare`` (parity with cv2 unpinned: it is not available to this project).
 
 EuRoC stereo lives in ``monogs_amd.stereo`` (``load_stereo_dataset``: the reader and semi-global matching in HIP); ``load_dataset``
-here keeps refusing ``type: euroc``.  What stays out: the Kubric (TIFF depth) and DAVIS (no depth) parsers, RealSense, and
-monocular operation of the harness -- ``dataset_frames`` refuses a dataset without depth.
+here keeps refusing ``type: euroc``.  Monocular operation (``configs/mono/*``, ``Dataset.sensor_type: monocular``):
+``dataset_frames(..., monocular=True)`` builds depthless frames from any dataset -- depth files, if present, are not read -- which
+``run_slam(sensor="monocular")`` tracks and maps with the RGB-only losses and ``monocular.pseudo_depth``; without the argument a
+dataset that brings no depth is still refused.  What stays out: the Kubric (TIFF depth) and DAVIS (no depth) parsers and RealSense.
 """
 from __future__ import annotations
 
@@ -165,7 +167,7 @@ class MonocularDataset:
         if color.ndim != 3 or color.shape[2] < 3:
             raise ValueError(f"{self.color_paths[idx]}: not a colour image")
         color = color[..., :3]                               # (the alpha channel is dropped)
-        depth = np.array(Image.open(self.depth_paths[idx])) if self.with_depth else None
+        depth = np.array(Image.open(self.depth_paths[idx])) if self.with_depth and not getattr(self, "skip_depth", False) else None
         for a, p in ((color, self.color_paths[idx]), (depth, self.depth_paths[idx] if depth is not None else None)):
             if a is not None and a.shape[:2] != (self.height, self.width):
                 raise ValueError(f"{p}: {a.shape[1]} x {a.shape[0]} pixels, the calibration says {self.width} x {self.height}")
@@ -199,20 +201,40 @@ def load_dataset(config, device="cuda:0", preload: bool = False) -> MonocularDat
     return MonocularDataset(PARSERS[kind](config["Dataset"]["dataset_path"]), config, device=device, preload=preload)
 
 
-def dataset_frames(dataset: MonocularDataset, n_frames: int, device="cuda:0", start: int = 0, stride: int = 1):
+def config_is_monocular(config) -> bool:
+    """``Dataset.sensor_type == "monocular"`` (the reference's configs/mono/* and configs/live/realsense.yaml)."""
+    return (load_config(config).get("Dataset") or {}).get("sensor_type") == "monocular"
+
+
+def dataset_frames(dataset: MonocularDataset, n_frames: int, device="cuda:0", start: int = 0, stride: int = 1,
+                   monocular: bool = False, config=None, rgb_boundary_threshold: Optional[float] = None):
     """``(frames, intr)`` as ``sequences.make_room_sequence`` returns them: ``frames.Viewpoint`` objects over the frames ``start,
     start + stride, ...`` of the dataset, the ground-truth ``R`` / ``T`` from the world-to-camera pose and the ingest's ``mask``
-    / ``grad_mask`` in place of recomputed ones."""
-    if not dataset.with_depth:
+    / ``grad_mask`` in place of recomputed ones.  ``monocular=True``: frames without depth (``Viewpoint(sensor="monocular")``, one
+    shared all-zero depth image) from any dataset; depth files are not decoded.  ``config`` (a path or dict), where at hand:
+    ``Dataset.sensor_type: monocular`` switches the mode on as well and ``Training.rgb_boundary_threshold`` (default 0.01) is the
+    threshold of the frames' ``valid_rgb`` mask, unless the argument of that name gives one."""
+    cfg = load_config(config) if config is not None else {}
+    monocular = bool(monocular) or (config is not None and config_is_monocular(cfg))
+    if rgb_boundary_threshold is None:
+        rgb_boundary_threshold = float((cfg.get("Training") or {}).get("rgb_boundary_threshold", 0.01))
+    if not monocular and not dataset.with_depth:
         raise ValueError("dataset_frames needs depth (depth files and Calibration.use_depth): the harness is RGB-D")
     idx = list(range(int(start), len(dataset), int(stride)))[:int(n_frames)]
     if len(idx) < int(n_frames):
         raise ValueError(f"the dataset holds {len(idx)} frames from {start} in steps of {stride}, {n_frames} were asked for")
     intr = Intrinsics(dict(fx=dataset.fx, fy=dataset.fy, cx=dataset.cx, cy=dataset.cy, W=dataset.width, H=dataset.height), device)
     frames = []
-    for n, i in enumerate(idx):
-        d = dataset[i]
-        pose = d["pose"].to(torch.float32)
-        frames.append(Viewpoint(n, d["rgb"], d["depth"], device, gt_R=pose[:3, :3].contiguous(), gt_T=pose[:3, 3].contiguous(),
-                                mask=d["mask"], grad_mask=d["grad_mask"]))
+    zero = torch.zeros(dataset.height, dataset.width, dtype=torch.float32, device=device) if monocular else None
+    was = getattr(dataset, "skip_depth", False)
+    dataset.skip_depth = bool(monocular)                 # (the decode leaves the depth files alone)
+    try:
+        for n, i in enumerate(idx):
+            d = dataset[i]
+            pose = d["pose"].to(torch.float32)
+            kw = dict(sensor="monocular", rgb_boundary_threshold=rgb_boundary_threshold) if monocular else {}
+            frames.append(Viewpoint(n, d["rgb"], zero if monocular else d["depth"], device, gt_R=pose[:3, :3].contiguous(),
+                                    gt_T=pose[:3, 3].contiguous(), mask=d["mask"], grad_mask=d["grad_mask"], **kw))
+    finally:
+        dataset.skip_depth = was
     return frames, intr

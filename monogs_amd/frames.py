@@ -38,8 +38,18 @@ def scharr_grad_mask(rgb: torch.Tensor, edge_threshold: float = 1.1, eps: float 
 
 
 class Viewpoint:
-    def __init__(self, idx, rgb, depth, device, gt_R=None, gt_T=None, mask=None, grad_mask=None, segmentation=None):
-        self.frame_idx, self.device = idx, device
+    """``sensor="monocular"``: a frame without measured depth.  Its ``depth`` is an all-zero image -- the datasets' own "no
+    measurement here" value, which keeps ``ones_like(depth)`` consumers working; pass one to share a single storage among the
+    frames of a sequence, or None -- and its ``mask`` is and-ed with ``monocular.valid_rgb(rgb, rgb_boundary_threshold)``.  The
+    tracker and the mapper pick the RGB-only losses for it (``fused_losses``)."""
+
+    def __init__(self, idx, rgb, depth, device, gt_R=None, gt_T=None, mask=None, grad_mask=None, segmentation=None,
+                 sensor="depth", rgb_boundary_threshold=0.01):
+        if sensor not in ("depth", "monocular"):
+            raise ValueError('sensor must be "depth" or "monocular"')
+        self.frame_idx, self.device, self.sensor = idx, device, sensor
+        if sensor == "monocular" and depth is None:
+            depth = torch.zeros(rgb.shape[-2:], dtype=torch.float32, device=rgb.device)
         if segmentation is not None:        # [H,W] integer object ids: what the back-projection labels its points with
             self.segmentation = segmentation
         self.R = torch.eye(3, device=device)
@@ -48,6 +58,8 @@ class Viewpoint:
         self.rgb, self.depth = rgb, depth
         # (a dataset frame brings both from monogs_amd.frame_ingest; the synthetic generators bring neither)
         self.mask = torch.ones_like(depth, dtype=torch.bool) if mask is None else mask
+        if sensor == "monocular":
+            self.mask = self.mask.bool() & (rgb.sum(dim=0) > rgb_boundary_threshold)      # (monocular.valid_rgb)
         self.grad_mask = scharr_grad_mask(rgb) if grad_mask is None else grad_mask
         z = lambda n, v=0.0: torch.nn.Parameter(torch.full((n,), v, device=device))  # noqa: E731
         self.cam_rot_delta, self.cam_trans_delta = z(3), z(3)

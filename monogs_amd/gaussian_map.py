@@ -249,17 +249,21 @@ class GaussianMap:
 
     # ---- new Gaussians from a keyframe (extend_from_pcd_seq, gaussian_model.py:321-396) --------------------------
     def extend_from_frame(self, vp, intr, downsample: int, point_size=0.05, init=False, render_opacity=None,
-                          render_depth=None, kf_id: Optional[int] = None, random_indices: Optional[torch.Tensor] = None):
+                          render_depth=None, kf_id: Optional[int] = None, random_indices: Optional[torch.Tensor] = None,
+                          depth: Optional[torch.Tensor] = None):
         """Back-project a keyframe's depth into new Gaussians; scale from distCUDA2
         (gaussian_model.py:121-319 via ``monogs_amd.keyframe``).  ``point_size=None``: the reference's rule,
         scale^2 = dist2 x min(0.05, 0.01 x median depth) (gaussian_model.py:173-178); a number: scale^2 = dist2 x point_size.
         ``random_indices``: the subset of the candidate pixels, as ``create_viewpoint_pcd`` takes it (default: drawn on the device).
-        A map with an object layer gives every new Gaussian the one-hot row of its pixel's ``vp.segmentation`` id."""
+        A map with an object layer gives every new Gaussian the one-hot row of its pixel's ``vp.segmentation`` id.
+        ``depth``: the image to back-project instead of ``vp.depth`` (a monocular keyframe's ``monocular.pseudo_depth``); without it a
+        monocular viewpoint adds nothing (its depth is zero everywhere)."""
         from .keyframe import create_viewpoint_pcd
         g = torch.Generator(device=self.device).manual_seed(1000 + vp.frame_idx)
         ps = dict(point_size=0.01, point_size_max=0.05) if point_size is None else dict(point_size=1e9, point_size_max=point_size)
         pw, rgb, scales, rots, opac, ids = create_viewpoint_pcd(
-            vp, intr, render_depth=None if init else (render_depth if render_depth is not None else vp.depth),
+            vp, intr, depth=depth,
+            render_depth=None if init else (render_depth if render_depth is not None else (vp.depth if depth is None else depth)),
             render_opacity=None if init else render_opacity, init=init,
             generator=g, downsample_factor=downsample, random_indices=random_indices, **ps)
         n_new = pw.shape[0]

@@ -18,6 +18,9 @@ sizes the result.  The random stream therefore differs from the reference's; pas
 reference's ``torch.randperm(num_points)[:k]`` would be) to reproduce a given subset exactly -- the parity test does.
 The reference cannot be imported here (open3d is absent), so this file is checked against a plain PyTorch
 restatement of the lines cited above: parity unpinned.
+
+``depth=``: the image to back-project in place of ``viewpoint.depth`` -- a monocular keyframe's depth hypothesis
+(``monocular.pseudo_depth``).  The mask, the point-size median and the unprojection all read it; ``viewpoint.depth`` is untouched.
 """
 from __future__ import annotations
 
@@ -50,7 +53,7 @@ def create_viewpoint_pcd(viewpoint, cam_intrinsics, render_depth=None, render_op
                          isotropic=True, random_indices: Optional[torch.Tensor] = None,
                          generator: Optional[torch.Generator] = None, downsample_factor: Optional[int] = None,
                          point_size: float = 0.01, point_size_max: float = 0.05,
-                         knn_against: Optional[torch.Tensor] = None):
+                         knn_against: Optional[torch.Tensor] = None, depth: Optional[torch.Tensor] = None):
     """``downsample_factor`` / ``point_size`` / ``point_size_max`` default to the values hard-coded in the reference
     (32 or 64, 0.01, 0.05: gaussian_model.py:166-178).
 
@@ -61,7 +64,7 @@ def create_viewpoint_pcd(viewpoint, cam_intrinsics, render_depth=None, render_op
     that lands next to mapped geometry gets a scale that fits it instead of the spacing of the sparse new sample."""
     lib = _lib.load()
     rgb = viewpoint.rgb.to(torch.float32).contiguous()
-    depth = viewpoint.depth.to(torch.float32).contiguous()
+    depth = (viewpoint.depth if depth is None else depth.detach().reshape(viewpoint.rgb.shape[-2:])).to(torch.float32).contiguous()
     dev = depth.device
     H, W = depth.shape
     seg = getattr(viewpoint, "segmentation", None)

@@ -41,6 +41,7 @@ import torch.distributed as dist
 from . import _lib, camera as cam, fused_losses, rasterizer as _rast, window as W
 from .gaussian_map import GaussianMap
 from .gaussian_optim import activate, fan_out, window_stats
+from .monocular import window_is_monocular
 from .pose_optim import PoseAdam
 from .rasterizer import GaussianRasterizer, _device_guard, _stream
 from .renderer import raster_settings, render
@@ -63,6 +64,9 @@ class _Plan:
     def __init__(self, mapper: "WindowMapper", viewpoints: Sequence, init: bool):
         gmap, dev = mapper.gmap, mapper.gmap.device
         self.P, self.n, self.init = len(gmap), len(viewpoints), bool(init)
+        # monocular keyframes are optimised by the RGB-only loss (a window that mixes sensors is a ValueError); the plan is keyed by
+        # the viewpoints, so the loss flavour cannot change under a captured graph
+        self.rgb_only = window_is_monocular(viewpoints)
         self.mine = mapper.owned(self.n)
         self.vps = [viewpoints[k] for k in self.mine]
         self.key = (self.P, tuple(id(v) for v in viewpoints), self.init, int(mapper.intr.height), int(mapper.intr.width),
@@ -238,10 +242,12 @@ class WindowMapper:
         h = p.holders[j]
         h.grad = None
         color, radii, depth, n_touched = self._rasterize(vp, xyz_k, rot_k, sc_k, opac_k, feat_k, h)
-        lg = fused_losses.loss_grads(color, depth, None, vp, tracking=False, init=p.init)
+        lg = fused_losses.loss_grads(color, depth, None, vp, tracking=False, init=p.init, rgb_only=p.rgb_only)
         p.lgs.append(lg)
         p.radii.append(radii)
         p.n_touched.append(n_touched)
+        if p.rgb_only:                 # (no gradient for the depth image: the rasteriser's backward takes it as zero)
+            return [color], [lg.d_render]
         return [color, depth], [lg.d_render, lg.d_depth]
 
     @staticmethod

@@ -19,6 +19,7 @@ from .frames import Viewpoint, position_error
 from .gaussian_map import GaussianMap
 from .map_arena import MapArena
 from .mapping import WindowMapper, render_map
+from .monocular import is_monocular, monocular_frames, pseudo_depth, valid_rgb
 from .sequences import make_room_sequence, make_sequence      # make_sequence: re-exported, bench.py imports it (and run_slam) from here
 from .tracking import TrackingGraph, track_eager
 
@@ -54,8 +55,12 @@ def _setup(c):
     ``dataset.dataset_frames``) instead of a synthetic ``scene``: "room" = ray-cast opaque surfaces (survive the reference's pruning,
     carry ``segmentation`` for a map with ``nr_objects`` scores per Gaussian), "cloud" = ``make_sequence`` (historical).
     ``reference_lrs`` / ``map_surgery``: the reference's learning rates / densify, prune and opacity-reset schedule.
-    ``kf_selection="overlap"``: a ``KeyframeWindow``, ``check_viewpoints_overlap`` being the tracker's flag (False in the fork)."""
+    ``kf_selection="overlap"``: a ``KeyframeWindow``, ``check_viewpoints_overlap`` being the tracker's flag (False in the fork).
+    ``sensor="monocular"``: the frames carry no depth (a synthetic or RGB-D sequence is stripped of it, a monocular ``sequence`` is
+    taken as it is); the tracker and the mapper then run the RGB-only losses and ``_map_keyframe`` back-projects depth hypotheses."""
     from .gaussian_map import REFERENCE_LRS, REFERENCE_LR_SCHEDULE
+    if c.sensor not in ("depth", "monocular"):
+        raise ValueError('sensor must be "depth" or "monocular"')
     if c.kf_selection not in ("interval", "overlap"):
         raise ValueError('kf_selection must be "interval" or "overlap"')
     if c.prune_after_mapping is None:
@@ -66,6 +71,11 @@ def _setup(c):
         frames, intr = make_room_sequence(c.n_frames, c.intrinsics, device=c.device, with_segmentation=c.nr_objects is not None)
     else:
         frames, intr = make_sequence(c.n_frames, c.intrinsics, c.n_gaussians, device=c.device)
+    if c.sensor == "monocular":
+        if not all(is_monocular(f) for f in frames):
+            frames = monocular_frames(frames)
+    elif any(is_monocular(f) for f in frames):
+        raise ValueError('the sequence holds monocular frames: run it with sensor="monocular"')
     # ``reference_densify``: new Gaussians as the fork hard-codes them (1/32 of the pixels at initialisation, 1/64 per keyframe, the
     # reference's point-size rule) instead of ``init_downsample`` / ``kf_downsample`` / ``point_size``
     if c.reference_densify:
@@ -87,6 +97,7 @@ def _setup(c):
     return SimpleNamespace(
         c=c, frames=frames, intr=intr, bg=bg, gmap=gmap, mapper=mapper, kfw=kfw, window=[], tgraph=None,
         kf_list=[],                                     # every keyframe of the run (the reference's viewpoints_dict / kf_indices)
+        pseudo_depth_stats=[],                          # monocular: (frame, median, std, count, used_init_rule) per keyframe
         per_frame=[], map_loss=[], window_sizes=[],     # (frame, tracking iterations); (first, last) mapping loss per call
         size_trace=[],                                  # (frame, Gaussians in the map after that keyframe's mapping)
         stats=dict(kf_extend_s=0.0, track_capture_s=0.0, track_s=0.0, track_iters=0, tracked=0, map_s=0.0, map_iters=0,
@@ -178,17 +189,32 @@ def _select_keyframe(s, i, vp):
     return pkg, t0
 
 
+def _depth_hypothesis(s, i, vp, pkg):
+    """``dict(depth=...)`` for ``extend_from_frame`` of a monocular keyframe (empty for a depth sensor); the statistics stay on the
+    device until ``_report``."""
+    if s.c.sensor != "monocular":
+        return {}
+    g = torch.Generator(device=vp.rgb.device).manual_seed(2000 + int(i))
+    pd, stats = pseudo_depth(None if pkg is None else pkg["depth"], None if pkg is None else pkg["opacity"], valid_rgb(vp.rgb),
+                             generator=g)
+    s.pseudo_depth_stats.append((i, stats))
+    return dict(depth=pd)
+
+
 def _map_keyframe(s, i, vp, pkg=None, t0=None):
     """As ``Mapper.run`` does per keyframe: extend the map, apply the window policy (overlap: the window as ``KeyframeWindow`` left
     it, most recent first as the reference hands it over), ``_map_window``.  CLOSES the ``map_s`` bracket ``_select_keyframe``
-    opened at ``t0``.  Frame 0 comes without ``pkg`` and ``t0``: it initialises the map inside a bracket of its own."""
+    opened at ``t0``.  Frame 0 comes without ``pkg`` and ``t0``: it initialises the map inside a bracket of its own.
+    A monocular keyframe is extended from ``monocular.pseudo_depth``: frame 0 from the init rule, a later one from its frozen render
+    ``pkg``; the noise generator is seeded from the frame index."""
     init, kfw = pkg is None, s.kfw
     with _timed(s.stats, "map_s", t0):
         if init:
-            s.gmap.extend_from_frame(vp, s.intr, init=True, **s.c.extend_kw(True))
+            s.gmap.extend_from_frame(vp, s.intr, init=True, **_depth_hypothesis(s, i, vp, None), **s.c.extend_kw(True))
         else:
             with _timed(s.stats, "kf_extend_s"):
-                s.gmap.extend_from_frame(vp, s.intr, render_opacity=pkg["opacity"], render_depth=pkg["depth"], **s.c.extend_kw(False))
+                s.gmap.extend_from_frame(vp, s.intr, render_opacity=pkg["opacity"], render_depth=pkg["depth"],
+                                         **_depth_hypothesis(s, i, vp, pkg), **s.c.extend_kw(False))
         if kfw is None or init:
             _slide_window(s.window, vp, s.c.window_size)
         else:
@@ -264,6 +290,11 @@ def _report(s, extra):
         gaussians_after_keyframe=[n for _, n in s.size_trace], log=sl[:6] + sl[-4:] if len(sl) > 10 else sl)
     if c.nr_objects is not None:
         out.update(map=gmap, frame_list=frames, intr=s.intr)
+    if c.sensor == "monocular":          # (a depth run keeps exactly the keys it always had)
+        from .evaluation import eval_ate
+        out.update(sensor="monocular", ate_sim3=eval_ate(frames, align=True, correct_scale=True),
+                   pseudo_depth_stats=[dict(frame=i, median=m, std=sd, count=int(n), used_init_rule=bool(r))
+                                       for i, (m, sd, n, r) in ((i, st.tolist()) for i, st in s.pseudo_depth_stats)])
     out.update(frames=len(frames), gaussians=int(gmap.get_xyz.shape[0]), width=s.intr.width, height=s.intr.height,
                tracking_fps=stats["tracked"] / max(stats["track_s"], 1e-9),
                tracking_iters_per_s=stats["track_iters"] / max(stats["track_s"], 1e-9),
@@ -295,10 +326,11 @@ def run_slam(n_frames=12, intrinsics="fr3_office", tracking_itr_num=100, mapping
              track_lookahead=1, map_surgery=False, reference_lrs=False, prune_after_mapping=None,
              scene="cloud", reference_densify=False, eager_probe=0, exclusive_device=False,
              kf_selection="interval", check_viewpoints_overlap=False, kf_trace=None, refine_iters=0, eval_render=False,
-             sequence=None, nr_objects=None):
+             sequence=None, nr_objects=None, sensor="depth"):
     """Tracks and maps a sequence in one process; returns tracking / mapping rates, iterations and the trajectory error (``_report``).
     Every argument is described where it acts: ``_setup``, ``_track_frame``, ``_select_keyframe``, ``_map_keyframe``, ``_map_window``,
-    ``_finish`` (what follows the last frame).  ``log``: a callable that gets a line per frame."""
+    ``_finish`` (what follows the last frame).  ``log``: a callable that gets a line per frame.  ``sensor="monocular"`` adds the result
+    keys ``sensor``, ``ate_sim3`` (Sim(3)-aligned ATE over all frames) and ``pseudo_depth_stats``; ``run_slam_two_process`` stays RGB-D."""
     s = _setup(SimpleNamespace(**locals()))              # (every argument, by name: must stay the first statement)
     for i, vp in enumerate(s.frames):
         if i == 0:

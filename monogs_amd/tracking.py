@@ -1,7 +1,8 @@
 """The tracker (/root/reference/utils/slam_tracker.py:83-193): pose-only Adam (rot 0.003, trans 0.001, exposure 0.01 --
 /root/reference/configs/mono/tum/base_config.yaml:46-48), at most ``max_iters`` iterations of render -> get_loss_tracking ->
 backward -> step -> update_pose, left early when the retraction step is < 1e-4.  ``track_eager`` launches every iteration from
-Python; ``TrackingGraph`` captures one iteration per map version in a hipGraph and replays it."""
+Python; ``TrackingGraph`` captures one iteration per map version in a hipGraph and replays it.  A monocular viewpoint
+(``Viewpoint(sensor="monocular")``) is tracked with ``get_loss_tracking_rgb``, eagerly and under capture."""
 from __future__ import annotations
 
 import torch
@@ -18,11 +19,12 @@ from .renderer import raster_settings
 def track_eager(vp, intr, gmap, bg, max_iters: int) -> int:
     """Tracks ``vp`` (starting from the pose it holds) against ``gmap``; returns the iterations run."""
     opt = PoseAdam(vp, 0.003, 0.001, 0.01)
+    loss_fn = fused_losses.get_loss_tracking_rgb if getattr(vp, "sensor", "depth") == "monocular" else fused_losses.get_loss_tracking
     n_it = 0
     for it in range(max_iters):
         pkg = render_map(vp, intr, gmap, bg)
         opt.zero_grad()
-        loss = fused_losses.get_loss_tracking(pkg["render"], pkg["depth"], pkg["opacity"], vp)
+        loss = loss_fn(pkg["render"], pkg["depth"], pkg["opacity"], vp)
         loss.backward()
         n_it += 1
         with torch.no_grad():
@@ -50,7 +52,9 @@ class TrackingGraph:
             self.map = (gmap.get_xyz.detach(), gmap.get_rotation.detach(), gmap.get_scaling.detach(),   # [P,1]: isotropic
                         gmap.get_opacity.detach(), gmap.get_features.detach())
         self.n_gaussians = int(self.map[0].shape[0])
-        self.svp = Viewpoint(-1, torch.zeros_like(proto.rgb), torch.ones_like(proto.depth), dev)
+        self.monocular = getattr(proto, "sensor", "depth") == "monocular"      # the captured loss is this sensor's
+        self.svp = Viewpoint(-1, torch.zeros_like(proto.rgb), torch.zeros_like(proto.depth) if self.monocular
+                             else torch.ones_like(proto.depth), dev, sensor="monocular" if self.monocular else "depth")
         self.opt = PoseAdam(self.svp, 0.003, 0.001, 0.01, sticky=True)
         self.intr, self.bg = intr, bg
         self.flags = [torch.zeros(1, pin_memory=True) for _ in range(2)]
@@ -94,13 +98,15 @@ class TrackingGraph:
         self.opt.zero_grad()
         # loss value + upstream gradients in two launches, then the rasteriser's backward directly: no autograd node for
         # the scalar (its finalize kernel and the ones-fill of loss.backward() were two of the 25 launches of a replay)
-        lg = fused_losses.loss_grads(color, depth, opacity, self.svp, tracking=True)
+        lg = fused_losses.loss_grads(color, depth, opacity, self.svp, tracking=True, rgb_only=self.monocular)
         lg.backward(color, depth, self.svp)
         self.opt.step_and_retract(sync=False, host_flag=host_flag, camera=(self.intr.projection_matrix,) + self.cam3)
 
     @torch.no_grad()
     def _load(self, vp: Viewpoint):
         s = self.svp
+        if (getattr(vp, "sensor", "depth") == "monocular") != self.monocular:
+            raise ValueError(f"this tracking graph was captured for a {s.sensor} viewpoint")
         s.rgb.copy_(vp.rgb); s.depth.copy_(vp.depth); s.mask.copy_(vp.mask); s.grad_mask.copy_(vp.grad_mask)
         s.R.copy_(vp.R); s.T.copy_(vp.T)
         s.exposure_a.data.copy_(vp.exposure_a.data); s.exposure_b.data.copy_(vp.exposure_b.data)

@@ -6,6 +6,9 @@ stand-in; the TUM / Replica sequences are not available offline).  Prints one JS
   python tools/slam_bench.py --config tum --dataset CONFIG.yaml --frames 200 [--stride 2]
       # a TUM / Replica sequence on disk (monogs_amd.dataset), or an EuRoC stereo one (Dataset.sensor_type: stereo,
       # monogs_amd.stereo): size and intrinsics from the YAML, iteration counts from --config
+  python tools/slam_bench.py --config tum --room --graph --sensor monocular
+      # no depth: RGB-only losses, keyframes back-projected from depth hypotheses (monogs_amd.monocular); with --dataset the depth
+      # files are not read (a YAML with Dataset.sensor_type: monocular selects this by itself).  Prints both ATEs to stderr.
 """
 import argparse
 import json
@@ -58,6 +61,8 @@ if __name__ == "__main__":
                     help="run on the TUM / Replica / EuRoC sequence this reference-style YAML names (Dataset.type, dataset_path, "
                          "Calibration) instead of a synthetic one: --frames frames from the first, every --stride-th")
     ap.add_argument("--stride", type=int, default=1, help="with --dataset: take every N-th frame")
+    ap.add_argument("--sensor", default=None, choices=["depth", "monocular"],
+                    help="monocular: run without depth (default: what the --dataset YAML's Dataset.sensor_type says, else depth)")
     a = ap.parse_args()
     from monogs_amd.slam_harness import run_slam
     cfg = dict(CONFIGS[a.config])
@@ -69,21 +74,27 @@ if __name__ == "__main__":
                  ("kf_interval", a.kf_interval)):
         if v is not None:
             cfg[k] = v
-    sequence = None
+    sequence, sensor = None, a.sensor or "depth"
     if a.dataset:
         from monogs_amd.dataset import dataset_frames, load_config, load_dataset
         config = load_config(a.dataset)
         if config["Dataset"].get("sensor_type") == "stereo":     # EuRoC: depth from semi-global matching (monogs_amd.stereo)
             from monogs_amd.stereo import load_stereo_dataset as load_dataset
-        sequence = dataset_frames(load_dataset(config, device="cuda:0"), a.frames, device="cuda:0", stride=a.stride)
+        if a.sensor is None and config["Dataset"].get("sensor_type") == "monocular":
+            sensor = "monocular"
+        mono = dict(monocular=True, config=config) if sensor == "monocular" else {}
+        sequence = dataset_frames(load_dataset(config, device="cuda:0"), a.frames, device="cuda:0", stride=a.stride, **mono)
         cfg.pop("intrinsics")                           # (the YAML's calibration is the camera)
     out = run_slam(sequence=sequence, n_frames=a.frames, init_itr_num=init_iters, n_gaussians=a.gaussians, graph_tracking=a.graph,
                    graph_mapping=a.graph and not a.eager_mapping, track_lookahead=a.lookahead, map_surgery=a.surgery,
                    reference_lrs=a.reference_lrs, scene="room" if a.room else "cloud", reference_densify=a.reference_densify,
                    eager_probe=a.eager_probe, kf_selection=a.kf_selection, check_viewpoints_overlap=a.check_overlap,
-                   refine_iters=a.refine, eval_render=a.eval, log=lambda s: print("[slam]", s, file=sys.stderr, flush=True), **cfg)
+                   refine_iters=a.refine, eval_render=a.eval, sensor=sensor, log=lambda s: print("[slam]", s, file=sys.stderr, flush=True), **cfg)
     what = f"{a.dataset}, every {a.stride}. frame" if a.dataset else f"synthetic {a.config}-like sequence"
     out["workload"] = f"{what}, {a.frames} frames" + (" (fork's hard-coded run configuration)" if a.fork else "")
+    if sensor == "monocular":
+        print(f"[slam] monocular: ATE rmse {out['ate_rmse_m']:.4f} m raw, {out['ate_sim3']['rmse']:.4f} m after Sim(3) alignment "
+              f"({out['ate_sim3']['n']} frames)", file=sys.stderr, flush=True)
     for k in ("poses", "camera_centers", "camera_centers_gt"):      # tensors: not JSON
         out.pop(k, None)
     print(json.dumps(out))
