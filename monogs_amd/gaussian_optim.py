@@ -13,7 +13,7 @@ from typing import Sequence
 import torch
 
 from . import _lib
-from .rasterizer import _stream, _device_guard
+from .rasterizer import _stream, _device_guard, _ptr
 
 
 class GaussianAdam:
@@ -135,10 +135,9 @@ def add_densification_stats(viewspace_grad: torch.Tensor, radii: torch.Tensor, x
     lib = _lib.load()
     P = radii.shape[0]
     g = viewspace_grad.contiguous()
-    p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
     with _device_guard(radii.device):
-        _lib.check(lib.mgs_densify_stats(P, g.data_ptr(), radii.contiguous().data_ptr(), p(xyz_gradient_accum), p(denom),
-                                         p(max_radii_2d), _stream()), "mgs_densify_stats")
+        _lib.check(lib.mgs_densify_stats(P, g.data_ptr(), radii.contiguous().data_ptr(), _ptr(xyz_gradient_accum), _ptr(denom),
+                                         _ptr(max_radii_2d), _stream()), "mgs_densify_stats")
 
 
 def window_stats(grads2d, radii, n_touched, grad_norm, visible, max_radii, accumulate: bool, bits=None):
@@ -164,39 +163,49 @@ def window_stats(grads2d, radii, n_touched, grad_norm, visible, max_radii, accum
                                         None if bits is None else bits.data_ptr(), _stream()), "mgs_window_stats")
 
 
+def activate_into(rot_raw, scale_raw, opacity_raw, rot, scales3, opac):
+    """``mgs_activate_forward``: (normalize(rot_raw), exp(scale_raw) expanded to [P,3], sigmoid(opacity_raw)) written into the
+    caller's ``rot`` [P,4], ``scales3`` [P,3], ``opac`` [P,1] in one launch.  Contiguous float32 device tensors, no autograd."""
+    lib = _lib.load()
+    with _device_guard(rot_raw.device):
+        _lib.check(lib.mgs_activate_forward(rot_raw.shape[0], scale_raw.shape[1], rot_raw.data_ptr(), scale_raw.data_ptr(),
+                                            opacity_raw.data_ptr(), rot.data_ptr(), scales3.data_ptr(), opac.data_ptr(),
+                                            _stream()), "mgs_activate_forward")
+
+
+def activate_backward_into(rot_raw, scales3, opac, g_rot, g_scales3, g_opac, sd, d_rot, d_scale, d_opac):
+    """``mgs_activate_backward``: gradients of the raw rotation [P,4], scale [P,sd], opacity [P,1] into the caller's ``d_*`` in one
+    launch, from the gradients ``g_*`` of the activated tensors (read in place when contiguous).  Any ``g_*`` / ``d_*`` may be None."""
+    lib = _lib.load()
+    keep = [None if g is None else g.contiguous() for g in (g_rot, g_scales3, g_opac)]
+    with _device_guard(rot_raw.device):
+        _lib.check(lib.mgs_activate_backward(rot_raw.shape[0], sd, rot_raw.data_ptr(), scales3.data_ptr(), opac.data_ptr(),
+                                             _ptr(keep[0]), _ptr(keep[1]), _ptr(keep[2]), _ptr(d_rot), _ptr(d_scale),
+                                             _ptr(d_opac), _stream()), "mgs_activate_backward")
+
+
 class _Activate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, rot_raw, scale_raw, opacity_raw):
-        lib = _lib.load()
         rot_raw, scale_raw, opacity_raw = rot_raw.detach().contiguous(), scale_raw.detach().contiguous(), opacity_raw.detach().contiguous()
-        P, sd = rot_raw.shape[0], scale_raw.shape[1]
-        dev = rot_raw.device
+        P, dev = rot_raw.shape[0], rot_raw.device
         rot = torch.empty(P, 4, device=dev)
         scales3 = torch.empty(P, 3, device=dev)
         opac = torch.empty(P, 1, device=dev)
-        with _device_guard(dev):
-            _lib.check(lib.mgs_activate_forward(P, sd, rot_raw.data_ptr(), scale_raw.data_ptr(), opacity_raw.data_ptr(),
-                                                rot.data_ptr(), scales3.data_ptr(), opac.data_ptr(), _stream()),
-                       "mgs_activate_forward")
+        activate_into(rot_raw, scale_raw, opacity_raw, rot, scales3, opac)
         ctx.save_for_backward(rot_raw, scales3, opac)
-        ctx.sd = sd
+        ctx.sd = scale_raw.shape[1]
         return rot, scales3, opac
 
     @staticmethod
     def backward(ctx, g_rot, g_scales3, g_opac):
-        lib = _lib.load()
         rot_raw, scales3, opac = ctx.saved_tensors
         P, dev = rot_raw.shape[0], rot_raw.device
         need = ctx.needs_input_grad
         d_rot = torch.empty(P, 4, device=dev) if need[0] else None
         d_scale = torch.empty(P, ctx.sd, device=dev) if need[1] else None
         d_opac = torch.empty(P, 1, device=dev) if need[2] else None
-        p = lambda t: None if t is None else t.contiguous().data_ptr()  # noqa: E731
-        keep = [t.contiguous() if t is not None else None for t in (g_rot, g_scales3, g_opac)]
-        with _device_guard(dev):
-            _lib.check(lib.mgs_activate_backward(P, ctx.sd, rot_raw.data_ptr(), scales3.data_ptr(), opac.data_ptr(),
-                                                 p(keep[0]), p(keep[1]), p(keep[2]), p(d_rot), p(d_scale), p(d_opac),
-                                                 _stream()), "mgs_activate_backward")
+        activate_backward_into(rot_raw, scales3, opac, g_rot, g_scales3, g_opac, ctx.sd, d_rot, d_scale, d_opac)
         return d_rot, d_scale, d_opac
 
 

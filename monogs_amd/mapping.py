@@ -21,6 +21,9 @@ loop; it has two halves with the collectives between them:
           learning rates in device memory, the xyz schedule + iteration count stepped on the device, the owned keyframes'
           pose steps in one launch.
 
+The activations, the five leaves that cut the autograd graph behind them, the rasteriser call and everything from the activations'
+backward to the schedule are ``monogs_amd.map_step.MapStep``, shared with the refiner (monogs_amd/refinement.py).
+
 Nothing in either half synchronises the host, allocates outside the caching allocator or launches a memset / memcpy node, so
 both are captured once per (map size, window) and replayed; map surgery (densify / prune / opacity reset) stays eager
 between replays, on exactly the iterations the reference does it.  Sharding (`monogs_amd.window`):
@@ -40,42 +43,30 @@ import torch.distributed as dist
 
 from . import _lib, camera as cam, fused_losses, rasterizer as _rast, window as W
 from .gaussian_map import GaussianMap
-from .gaussian_optim import activate, fan_out, window_stats
+from .gaussian_optim import fan_out, window_stats
+from .map_step import MapStep, rasterize, render_map      # noqa: F401  (render_map: re-exported, tests and tools import it from here)
 from .monocular import window_is_monocular
 from .pose_optim import PoseAdam
-from .rasterizer import GaussianRasterizer, _device_guard, _stream
-from .renderer import raster_settings, render
+from .rasterizer import _device_guard, _stream
 
 BUCKET_COLS = 16          # floats per Gaussian in the exchange bucket (see the module docstring)
 _GRAD_COLS = 14
 
 
-def render_map(vp, intr, gmap: GaussianMap, bg):
-    """``render()`` with the map's activations (normalize / exp / sigmoid, forward and backward) in one launch each."""
-    if gmap.fused_adam and gmap._rotation.requires_grad:
-        rot, scales3, opac = activate(gmap._rotation, gmap._scaling, gmap._opacity)
-        return render(vp, intr, gmap.get_xyz, rot, scales3, opac, gmap.get_features, bg)
-    return render(vp, intr, gmap.get_xyz, gmap.get_rotation, gmap.get_scaling, gmap.get_opacity, gmap.get_features, bg)
-
-
 class _Plan:
     """Static state of the window iteration for one (map size, window, loss flavour): everything a captured half points at."""
 
-    def __init__(self, mapper: "WindowMapper", viewpoints: Sequence, init: bool):
+    def __init__(self, mapper: "WindowMapper", viewpoints: Sequence, init: bool, key):
         gmap, dev = mapper.gmap, mapper.gmap.device
-        self.P, self.n, self.init = len(gmap), len(viewpoints), bool(init)
+        self.P, self.n, self.init, self.key = len(gmap), len(viewpoints), bool(init), key
         # monocular keyframes are optimised by the RGB-only loss (a window that mixes sensors is a ValueError); the plan is keyed by
         # the viewpoints, so the loss flavour cannot change under a captured graph
         self.rgb_only = window_is_monocular(viewpoints)
         self.mine = mapper.owned(self.n)
         self.vps = [viewpoints[k] for k in self.mine]
-        self.key = (self.P, tuple(id(v) for v in viewpoints), self.init, int(mapper.intr.height), int(mapper.intr.width),
-                    tuple(id(p) for p in gmap.params()))
         P, f32 = self.P, dict(dtype=torch.float32, device=dev)
-        self.sd = int(gmap._scaling.shape[1])
+        self.step = MapStep(gmap)       # the activated tensors, their raw gradients and the schedule's iteration count
         self.bucket = torch.zeros(P * BUCKET_COLS, **f32)
-        self.rot, self.scales3, self.opac = torch.empty(P, 4, **f32), torch.empty(P, 3, **f32), torch.empty(P, 1, **f32)
-        self.d_rot, self.d_scale, self.d_opac = torch.empty(P, 4, **f32), torch.empty(P, self.sd, **f32), torch.empty(P, 1, **f32)
         # the screen-space gradient holders of render() (zeros whose .grad receives dL/dmean2D), one per owned keyframe,
         # allocated once: the rasteriser never reads their values
         self.holders = [torch.zeros(P, 3, requires_grad=True, **f32) for _ in self.mine]
@@ -92,7 +83,6 @@ class _Plan:
         self.n_touched: List = []
         self.graphs = None              # (front, back) or (whole,) once captured
         self.graph_flags = None         # owner of the status words of every forward those graphs captured
-        self.iter_dev = torch.zeros(1, dtype=torch.int32, device=dev)
         # pipelined exchange (WindowMapper.exchange = "per_keyframe"): one gradient bucket per owned keyframe, reduced on
         # its own while the next keyframe renders; `slot_graphs`: one captured (render, loss, backward) per owned keyframe
         # (decided from rank-INDEPENDENT quantities: every rank issues exactly `rows` slot collectives of the same size, a rank
@@ -111,6 +101,13 @@ class _Plan:
     def grad_view(self, col0: int, cols: int):
         P = self.P
         return self.bucket[P * col0:P * (col0 + cols)].view(P, cols)
+
+    def packed_row(self, k: int):
+        """Packed visibility bits of window keyframe k, a view: row ``k // world`` of what rank ``k % world`` put behind its MAX radii."""
+        if self.gout is None:
+            return self.bits[k]
+        world = self.gout.shape[0]
+        return self.gout[k % world, (self.P + 1) // 2:].view(self.rows, self.words)[k // world]
 
 
 class WindowMapper:
@@ -213,7 +210,7 @@ class WindowMapper:
                tuple(id(q) for q in self.gmap.params()))
         if p is None or p.key != key:
             self._drop_plan()
-            p = self._plan = _Plan(self, viewpoints, init)
+            p = self._plan = _Plan(self, viewpoints, init, key)
         return p
 
     def _drop_plan(self):
@@ -222,26 +219,13 @@ class WindowMapper:
         self._plan = None
 
     # ---- the two halves of an iteration -----------------------------------------------------------------------------
-    def _activations(self, p: _Plan):
-        gmap, lib, P = self.gmap, _lib.load(), p.P
-        with _device_guard(gmap._xyz.device):
-            _lib.check(lib.mgs_activate_forward(P, p.sd, gmap._rotation.data_ptr(), gmap._scaling.data_ptr(),
-                                                gmap._opacity.data_ptr(), p.rot.data_ptr(), p.scales3.data_ptr(),
-                                                p.opac.data_ptr(), _stream()), "mgs_activate_forward")
-
-    def _cut(self, p: _Plan):
-        """The five tensors the renders differentiate with respect to: leaves that CUT the graph at the activations (their
-        backward is one explicit launch in `_back`, after the collectives)."""
-        gmap = self.gmap
-        return [t.detach().requires_grad_(True) for t in (gmap._xyz, gmap._rgb, p.opac, p.scales3, p.rot)]
-
     def _render_slot(self, p: _Plan, j: int, fan):
         """Forward of owned keyframe j: the full render + the fused loss value and gradients.  Returns what its backward needs."""
         vp = p.vps[j]
-        xyz_k, feat_k, opac_k, sc_k, rot_k = fan
         h = p.holders[j]
         h.grad = None
-        color, radii, depth, n_touched = self._rasterize(vp, xyz_k, rot_k, sc_k, opac_k, feat_k, h)
+        cam3 = cam.cached_camera_tensors(vp, vp.R, vp.T, self.intr.projection_matrix)
+        color, radii, depth, n_touched = rasterize(self.intr, self.bg, cam3, fan, h, vp.cam_rot_delta, vp.cam_trans_delta)
         lg = fused_losses.loss_grads(color, depth, None, vp, tracking=False, init=p.init, rgb_only=p.rgb_only)
         p.lgs.append(lg)
         p.radii.append(radii)
@@ -268,8 +252,8 @@ class WindowMapper:
     def _front(self, p: _Plan, accumulate_stats: bool, parallel: bool):
         """Renders + losses + ONE backward of the owned keyframes into the bucket, then the statistics launch."""
         P = p.P
-        self._activations(p)
-        cut = self._cut(p)
+        p.step.activate()
+        cut = p.step.leaves()
         p.lgs, p.radii, p.n_touched = [], [], []
         if not p.mine:
             p.bucket[:P * _GRAD_COLS].zero_()
@@ -298,7 +282,7 @@ class WindowMapper:
     # ---- pipelined exchange: one bucket per owned keyframe, its all-reduce behind the next keyframe's render ------------
     def _slot(self, p: _Plan, j: int):
         """Render + loss + backward of owned keyframe j alone; its map gradients land in ``p.slot_flat[j]`` (bucket layout)."""
-        fan = fan_out(1, *self._cut(p), out=p.slot_flat[j])[0]
+        fan = fan_out(1, *p.step.leaves(), out=p.slot_flat[j])[0]
         o, g = self._render_slot(p, j, fan)
         torch.autograd.backward(o, g)
         self._take_exposure_grads(p.vps[j], p.lgs[-1])
@@ -309,7 +293,7 @@ class WindowMapper:
         buckets added up in keyframe order and the statistics launch.  The two statistics columns and the all-gather follow in
         `_exchange`.  Captured plans replay one graph per keyframe (`p.slot_graphs`) and one for the tail."""
         if p.slot_graphs is None:
-            self._activations(p)
+            p.step.activate()
             p.lgs, p.radii, p.n_touched = [], [], []
             produce = lambda j: self._slot(p, j)                    # noqa: E731
         else:
@@ -325,14 +309,6 @@ class WindowMapper:
         from .gaussian_optim import sum_buffers
         sum_buffers(p.slot_flat, out=p.bucket[:p.P * _GRAD_COLS])          # fixed order: keyframe 0, 1, ... of this rank
         self._stats(p, accumulate_stats=False)
-
-    def _rasterize(self, vp, xyz, rot, scales3, opac, feat, holder):
-        """The rasteriser call of ``render()`` (/root/reference/gaussian_splatting/gaussian_renderer/__init__.py:52-156)."""
-        rs = raster_settings(self.intr, self.bg, *cam.cached_camera_tensors(vp, vp.R, vp.T, self.intr.projection_matrix))
-        color, radii, depth, _, n_touched = GaussianRasterizer(rs)(
-            means3D=xyz, means2D=holder, opacities=opac, colors_precomp=feat, scales=scales3, rotations=rot,
-            theta=vp.cam_rot_delta, rho=vp.cam_trans_delta)
-        return color, radii, depth, n_touched
 
     def _exchange(self, p: _Plan, grads: bool = True, reduced: bool = False):
         """The collectives of one iteration: SUM of the bucket, one all-gather of MAX radii + visibility bits.
@@ -354,33 +330,24 @@ class WindowMapper:
             self.exposed_comm_s += time.perf_counter() - t0
 
     def _back(self, p: _Plan, viewpoints, pose_steps: bool, lr_update: bool, surgery=None):
-        """Statistics into the map, backward of the activations, (eager only: map surgery,) Adam, schedule, pose steps."""
-        gmap, lib, P = self.gmap, _lib.load(), p.P
-        with _device_guard(gmap._xyz.device):
-            if self.sharded:
-                maxr = torch.amax(p.gout[:, :(P + 1) // 2].view(torch.float32)[:, :P], dim=0)
-                _lib.check(lib.mgs_window_apply(P, p.grad_view(14, 1).data_ptr(), p.grad_view(15, 1).data_ptr(),
-                                                maxr.data_ptr(), gmap.xyz_gradient_accum.data_ptr(), gmap.denom.data_ptr(),
-                                                gmap.max_radii_2d.data_ptr(), _stream()), "mgs_window_apply")
-            _lib.check(lib.mgs_activate_backward(P, p.sd, gmap._rotation.data_ptr(), p.scales3.data_ptr(), p.opac.data_ptr(),
-                                                 p.grad_view(10, 4).data_ptr(), p.grad_view(7, 3).data_ptr(),
-                                                 p.grad_view(6, 1).data_ptr(), p.d_rot.data_ptr(), p.d_scale.data_ptr(),
-                                                 p.d_opac.data_ptr(), _stream()), "mgs_activate_backward")
-        # the leaves' gradients, exactly where autograd would have put them -- BEFORE any surgery: densify_and_prune replaces
-        # every tensor (new leaves, no gradient: no step, as torch.optim.Adam), an opacity reset replaces the opacities only
-        for q, g in zip(gmap.params(), (p.grad_view(0, 3), p.grad_view(3, 3), p.d_opac, p.d_scale, p.d_rot)):
-            q.grad = g
-        gaussian_split = bool(surgery(p)) if surgery is not None else False
-        if self.keep_reduced_grads:
-            self.last_grads = [None if q.grad is None else q.grad.clone() for q in gmap.params()]
-        gmap.optimizer.step()                     # (after surgery every .grad is None: no step, as torch.optim.Adam)
-        if lr_update and gmap.lr_schedule is not None:
-            s = gmap.lr_schedule
+        """Statistics into the map, then the map step -- with (eager only) the map surgery before its Adam -- and the pose steps."""
+        gmap, P = self.gmap, p.P
+        if self.sharded:
             with _device_guard(gmap._xyz.device):
-                _lib.check(lib.mgs_lr_schedule_step(p.iter_dev.data_ptr(), gmap.optimizer.device_lrs().data_ptr(),
-                                                    float(s["lr_init"]), float(s["lr_final"]), int(s.get("lr_delay_steps", 0)),
-                                                    float(s.get("lr_delay_mult", 1.0)), int(s["max_steps"]), _stream()),
-                           "mgs_lr_schedule_step")
+                maxr = torch.amax(p.gout[:, :(P + 1) // 2].view(torch.float32)[:, :P], dim=0)
+                _lib.check(_lib.load().mgs_window_apply(
+                    P, p.grad_view(14, 1).data_ptr(), p.grad_view(15, 1).data_ptr(), maxr.data_ptr(),
+                    gmap.xyz_gradient_accum.data_ptr(), gmap.denom.data_ptr(), gmap.max_radii_2d.data_ptr(), _stream()),
+                    "mgs_window_apply")
+
+        def before_step():
+            gaussian_split = bool(surgery(p)) if surgery is not None else False
+            if self.keep_reduced_grads:
+                self.last_grads = [None if q.grad is None else q.grad.clone() for q in gmap.params()]
+            return gaussian_split
+        # the gradient columns of the bucket, read in place, in the order of the leaves: xyz, rgb, opacity, scales, rotation
+        grads = [p.grad_view(c, n) for c, n in ((0, 3), (3, 3), (6, 1), (7, 3), (10, 4))]
+        gaussian_split = p.step.apply(grads, before_step, schedule=lr_update)
         if pose_steps:
             moved = [self._pose_optimizer(vp) for vp in p.vps if vp.frame_idx != 0]      # the first frame is the gauge
             PoseAdam.step_batch(moved)                                                   # one launch
@@ -407,7 +374,7 @@ class WindowMapper:
             # activations | one graph per owned keyframe | slot sum + statistics; the collectives run between them
             p.lgs, p.radii, p.n_touched = [], [], []
             graphs = []
-            for body in [lambda: self._activations(p)] + [(lambda j=j: self._slot(p, j)) for j in range(len(p.mine))] + \
+            for body in [p.step.activate] + [(lambda j=j: self._slot(p, j)) for j in range(len(p.mine))] + \
                     [lambda: self._sum_slots(p)]:
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, pool=self._pool):
@@ -453,11 +420,6 @@ class WindowMapper:
         self.stats["replays"] += n
 
     # ---- the loop shared by optimize_map and initialize_map -----------------------------------------------------------
-    def _sync_schedule(self, p: _Plan):
-        """Device copies of the mapper's iteration count and of the learning rates (what the captured schedule steps)."""
-        p.iter_dev.fill_(self.nr_iters)
-        self.gmap.optimizer.device_lrs()
-
     def _run(self, viewpoints, kf_ids, iters: int, init: bool, pose_steps: bool, lr_update: bool, surgery_at) -> bool:
         gmap = self.gmap
         gaussian_split = False
@@ -465,7 +427,7 @@ class WindowMapper:
         on_gpu = torch.device(gmap.device).type == "cuda"
         while done < iters:
             p = self._get_plan(viewpoints, init)
-            self._sync_schedule(p)
+            p.step.set_iteration(self.nr_iters)
             # iterations until (and including) the next one that does map surgery
             ahead = 0
             while done + ahead < iters and surgery_at(self.nr_iters + ahead + 1, done + ahead) is None:
@@ -505,10 +467,10 @@ class WindowMapper:
                             # (the capture left ITS gradient tensors in the pose / exposure parameters' .grad, holding the last
                             #  replay's values: the eager backward would add to them)
                             self._zero_grads(p, viewpoints)
-                            self._sync_schedule(p)
+                            p.step.set_iteration(self.nr_iters)
                             self._iterate_eager(p, viewpoints, pose_steps, lr_update, None, parallel=False)
                             n_left -= 1
-                            self._sync_schedule(p)
+                            p.step.set_iteration(self.nr_iters)
                 else:
                     for _ in range(n_left):
                         self._iterate_eager(p, viewpoints, pose_steps, lr_update, None, parallel=False)
@@ -548,12 +510,7 @@ class WindowMapper:
         p = self._plan
         if p is None:
             return
-        out = {}
-        for k in range(p.n):
-            src = p.bits if not self.sharded else p.gout[k % self.world, (p.P + 1) // 2:].view(p.rows, p.words)
-            words = src[k // self.world]
-            out[kf_ids[k]] = W.unpack_bits(words.view(torch.uint8), p.P)
-        self.occ_aware_visibility = out
+        self.occ_aware_visibility = {kf_ids[k]: W.unpack_bits(p.packed_row(k).view(torch.uint8), p.P) for k in range(p.n)}
 
     def packed_visibility(self) -> Optional[Dict[int, torch.Tensor]]:
         """Read-only: the rows of ``occ_aware_visibility`` as the statistics launch of the LAST iteration packed them
@@ -564,11 +521,7 @@ class WindowMapper:
         kf_ids = list(self.occ_aware_visibility)
         if p is None or len(kf_ids) != p.n or p.P != len(self.gmap):
             return None
-        out = {}
-        for k, kf in enumerate(kf_ids):
-            src = p.bits if not self.sharded else p.gout[k % self.world, (p.P + 1) // 2:].view(p.rows, p.words)
-            out[kf] = src[k // self.world]
-        return out
+        return {kf: p.packed_row(k) for k, kf in enumerate(kf_ids)}
 
     # ---- one call = Mapper.optimize_map(cur_kf_list, prune, iters) ------------------------------------------------------
     def optimize_map(self, viewpoints: Sequence, kf_ids: Optional[Sequence[int]] = None, prune: bool = False,

@@ -7,10 +7,10 @@ visible Gaussians (:542-545; ``xyz_gradient_accum`` and ``denom`` are NOT touche
 ``update_learning_rate(iteration)`` with the REFINEMENT's own count 1..iters (:548: the xyz schedule restarts from ``lr_init``).
 Poses and exposures take no step.
 
-A sibling of ``WindowMapper`` (monogs_amd/mapping.py), not a mode of it: the same way of cutting the autograd graph at the
-activations (``mgs_activate_forward`` / ``_backward`` as explicit launches around leaves), ``fused_losses.refinement_loss_grads``,
-``GaussianAdam.step`` with the learning rates on the device and ``mgs_lr_schedule_step``.  The keyframe order is drawn on the
-host BEFORE the loop (``self.sequence``): reproducible, and the same when a chunk has to be run again.
+A sibling of ``WindowMapper`` (monogs_amd/mapping.py), not a mode of it.  The two share ``monogs_amd.map_step.MapStep``: the
+activations, the leaves that cut the autograd graph behind them, the rasteriser call, and everything from the activations'
+backward through ``GaussianAdam.step`` to the schedule on the device; the loss is ``fused_losses.refinement_loss_grads``.  The
+keyframe order is drawn on the host BEFORE the loop (``self.sequence``): reproducible, and the same when a chunk has to be run again.
 
 ``use_graph=True``: ONE captured iteration serves every keyframe, the way ``TrackingGraph`` serves every frame -- a static slot
 holds the image and the camera tensors, the chosen keyframe is copied into it before each replay.  The capture is made on one
@@ -30,8 +30,29 @@ import torch
 
 from . import _lib, camera as cam, fused_losses, rasterizer as _rast
 from .gaussian_map import GaussianMap
-from .rasterizer import GaussianRasterizer, _device_guard, _stream
-from .renderer import raster_settings
+from .map_step import MapStep, rasterize
+from .rasterizer import _device_guard, _stream
+
+
+class _Buffers:
+    """Static state of the iteration for one map size: everything a captured iteration points at."""
+
+    def __init__(self, gmap: GaussianMap, intr):
+        dev = gmap.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        H, W = int(intr.height), int(intr.width)
+        self.step = MapStep(gmap)       # the activated tensors, their raw gradients and the refinement's own iteration count
+        self.P = P = self.step.P
+        self.holder = torch.zeros(P, 3, requires_grad=True, **f32)      # render()'s screen-space gradient holder
+        self.zero_depth = torch.zeros(1, H, W, **f32)                   # dL/ddepth: the loss has no depth term
+        # zero pose deltas of the iteration's own: no viewpoint is touched
+        self.theta, self.rho = torch.nn.Parameter(torch.zeros(3, **f32)), torch.nn.Parameter(torch.zeros(3, **f32))
+        self.acc = torch.zeros(2, 3, **f32)                             # sums of (loss, L1, SSIM): first / last window
+        self.sticky = torch.zeros(1, dtype=torch.int32, device=dev)     # status bits of every replay since the chunk began
+        # the static viewpoint slot of the captured iteration
+        self.rgb, self.R, self.T = torch.zeros(3, H, W, **f32), torch.eye(3, **f32), torch.zeros(3, **f32)
+        self.cam3 = (torch.empty(4, 4, **f32), torch.empty(4, 4, **f32), torch.empty(3, **f32))
+        self.rg = None                  # the loss record of the last iteration
 
 
 class Refiner:
@@ -65,88 +86,37 @@ class Refiner:
         rng = random.Random(seed)
         return [rng.randint(0, n_keyframes - 1) for _ in range(iters)]
 
-    # ---- static state of the iteration ----------------------------------------------------------------------------------
-    def _buffers(self):
-        gmap, P = self.gmap, len(self.gmap)
-        b = self._buf
-        if b is not None and b["P"] == P:
-            return b
-        self._drop_graph()
-        dev = gmap.device
-        f32 = dict(dtype=torch.float32, device=dev)
-        H, W = int(self.intr.height), int(self.intr.width)
-        z = lambda n: torch.nn.Parameter(torch.zeros(n, **f32))  # noqa: E731
-        b = self._buf = dict(
-            P=P, sd=int(gmap._scaling.shape[1]),
-            rot=torch.empty(P, 4, **f32), scales3=torch.empty(P, 3, **f32), opac=torch.empty(P, 1, **f32),
-            d_rot=torch.empty(P, 4, **f32), d_scale=torch.empty(P, int(gmap._scaling.shape[1]), **f32), d_opac=torch.empty(P, 1, **f32),
-            holder=torch.zeros(P, 3, requires_grad=True, **f32),            # render()'s screen-space gradient holder
-            zero_depth=torch.zeros(1, H, W, **f32),                         # dL/ddepth: the loss has no depth term
-            theta=z(3), rho=z(3),                                           # zero pose deltas of the iteration's own: no viewpoint is touched
-            iter_dev=torch.zeros(1, dtype=torch.int32, device=dev),         # the refinement's own iteration count
-            acc=torch.zeros(2, 3, **f32),                                   # sums of (loss, L1, SSIM): first / last window
-            sticky=torch.zeros(1, dtype=torch.int32, device=dev),           # status bits of every replay since the chunk began
-            # the static viewpoint slot of the captured iteration
-            rgb=torch.zeros(3, H, W, **f32), R=torch.eye(3, **f32), T=torch.zeros(3, **f32),
-            cam3=(torch.empty(4, 4, **f32), torch.empty(4, 4, **f32), torch.empty(3, **f32)))
-        return b
-
-    def _activations(self, b):
-        gmap, lib = self.gmap, _lib.load()
-        with _device_guard(gmap._xyz.device):
-            _lib.check(lib.mgs_activate_forward(b["P"], b["sd"], gmap._rotation.data_ptr(), gmap._scaling.data_ptr(),
-                                                gmap._opacity.data_ptr(), b["rot"].data_ptr(), b["scales3"].data_ptr(),
-                                                b["opac"].data_ptr(), _stream()), "mgs_activate_forward")
-
-    def _rasterize(self, cam3, xyz, rot, scales3, opac, feat, holder, theta, rho):
-        """The rasteriser call of ``render()`` (/root/reference/gaussian_splatting/gaussian_renderer/__init__.py:52-156)."""
-        color, radii, depth, _, _ = GaussianRasterizer(raster_settings(self.intr, self.bg, *cam3))(
-            means3D=xyz, means2D=holder, opacities=opac, colors_precomp=feat, scales=scales3, rotations=rot,
-            theta=theta, rho=rho)
-        return color, radii, depth
-
     # ---- one iteration (eager, or the body of the capture) ---------------------------------------------------------------
     def _iteration(self, b, rgb, cam3):
-        gmap, lib, P = self.gmap, _lib.load(), b["P"]
-        self._activations(b)
-        # leaves that CUT the graph at the activations, as WindowMapper._cut: their backward is one explicit launch below
-        xyz, feat, opac, sc3, rot = [t.detach().requires_grad_(True) for t in (gmap._xyz, gmap._rgb, b["opac"], b["scales3"], b["rot"])]
-        h = b["holder"]
-        h.grad = b["theta"].grad = b["rho"].grad = None
-        color, radii, depth = self._rasterize(cam3, xyz, rot, sc3, opac, feat, h, b["theta"], b["rho"])
+        gmap = self.gmap
+        b.step.activate()
+        leaves = b.step.leaves()
+        h = b.holder
+        h.grad = b.theta.grad = b.rho.grad = None
+        color, radii, depth, _ = rasterize(self.intr, self.bg, cam3, leaves, h, b.theta, b.rho)
         if torch.cuda.is_current_stream_capturing():
             # a forward rewrites its status word: the chunk's check must see an overflow of ANY replay, whichever keyframe it drew
-            self._graph_flags.accumulate(b["sticky"])
+            self._graph_flags.accumulate(b.sticky)
         rg = fused_losses.refinement_loss_grads(color, rgb, self.lambda_ssim)
-        torch.autograd.backward([color, depth], [rg.d_render, b["zero_depth"]])
-        b["rg"], self.last_radii = rg, radii
+        torch.autograd.backward([color, depth], [rg.d_render, b.zero_depth])
+        b.rg, self.last_radii = rg, radii
         with _device_guard(gmap._xyz.device):
             # max_radii_2d[visible] = max(., radii[visible]) alone (slam_mapper.py:542-545): NULL for the other two statistics
-            _lib.check(lib.mgs_densify_stats(P, h.grad.data_ptr(), radii.data_ptr(), None, None, gmap.max_radii_2d.data_ptr(),
-                                             _stream()), "mgs_densify_stats")
-            g_rot, g_sc, g_op = rot.grad.contiguous(), sc3.grad.contiguous(), opac.grad.contiguous()
-            _lib.check(lib.mgs_activate_backward(P, b["sd"], gmap._rotation.data_ptr(), b["scales3"].data_ptr(), b["opac"].data_ptr(),
-                                                 g_rot.data_ptr(), g_sc.data_ptr(), g_op.data_ptr(), b["d_rot"].data_ptr(),
-                                                 b["d_scale"].data_ptr(), b["d_opac"].data_ptr(), _stream()), "mgs_activate_backward")
-        for q, g in zip(gmap.params(), (xyz.grad, feat.grad, b["d_opac"], b["d_scale"], b["d_rot"])):
-            q.grad = g
-        if self.keep_grads:
-            self.last_grads = [q.grad.clone() for q in gmap.params()]
-        gmap.optimizer.step()
-        s = gmap.lr_schedule
-        if s is not None:           # update_learning_rate(iteration), AFTER the step, on the device
-            with _device_guard(gmap._xyz.device):
-                _lib.check(lib.mgs_lr_schedule_step(b["iter_dev"].data_ptr(), gmap.optimizer.device_lrs().data_ptr(),
-                                                    float(s["lr_init"]), float(s["lr_final"]), int(s.get("lr_delay_steps", 0)),
-                                                    float(s.get("lr_delay_mult", 1.0)), int(s["max_steps"]), _stream()),
-                           "mgs_lr_schedule_step")
+            _lib.check(_lib.load().mgs_densify_stats(b.P, h.grad.data_ptr(), radii.data_ptr(), None, None,
+                                                     gmap.max_radii_2d.data_ptr(), _stream()), "mgs_densify_stats")
+
+        def keep_grads():
+            if self.keep_grads:
+                self.last_grads = [q.grad.clone() for q in gmap.params()]
+        # (contiguous views of the rasteriser's one gradient allocation, read in place)
+        b.step.apply([t.grad for t in leaves], keep_grads)
 
     def _account(self, b, i, iters, m):
         """Iteration i's (loss, L1, SSIM) into the running sums of the first / last ``m`` iterations, on the device."""
         if i < m:
-            b["acc"][0] += b["rg"].scratch[:3]
+            b.acc[0] += b.rg.scratch[:3]
         if i >= iters - m:
-            b["acc"][1] += b["rg"].scratch[:3]
+            b.acc[1] += b.rg.scratch[:3]
 
     def _iterate_eager(self, b, vp, i, iters, m):
         cam3 = cam.cached_camera_tensors(vp, vp.R, vp.T, self.intr.projection_matrix)
@@ -158,26 +128,26 @@ class Refiner:
     @torch.no_grad()
     def _measure(self, b, vps) -> int:
         """One exact no-grad forward per keyframe at the current map: the largest instance count."""
-        gmap, key = self.gmap, (b["P"], int(self.intr.width), int(self.intr.height))
+        gmap, key = self.gmap, (b.P, int(self.intr.width), int(self.intr.height))
         with _rast.exact_counts():
-            self._activations(b)
+            b.step.activate()
+            five = (gmap._xyz.detach(), gmap._rgb.detach(), b.step.opac, b.step.scales3, b.step.rot)
             most = 0
             for vp in vps:
                 cam3 = cam.cached_camera_tensors(vp, vp.R, vp.T, self.intr.projection_matrix)
-                self._rasterize(cam3, gmap._xyz.detach(), b["rot"], b["scales3"], b["opac"], gmap._rgb.detach(),
-                                b["holder"].detach(), None, None)
+                rasterize(self.intr, self.bg, cam3, five, b.holder.detach(), None, None)
                 most = max(most, int(_rast.capacity_hint(*key)))
         return most
 
     def _capture(self, b, vps, at_least: int = 0):
         W, H = int(self.intr.width), int(self.intr.height)
         scale = self.first_reserve_scale if self.stats["captures"] == 0 else 1.0
-        _rast.reserve_capacity(b["P"], W, H, max(int(self._measure(b, vps) * scale), int(at_least)))
+        _rast.reserve_capacity(b.P, W, H, max(int(self._measure(b, vps) * scale), int(at_least)))
         self.gmap.optimizer.zero_grad(set_to_none=True)
         g = torch.cuda.CUDAGraph()
         self._graph_flags = _rast.graph_flags()
         with self._graph_flags, torch.cuda.graph(g):   # one stream, no side streams; a memory pool of its own, released with the graph
-            self._iteration(b, b["rgb"], b["cam3"])
+            self._iteration(b, b.rgb, b.cam3)
         self._graph = g
         self.stats["captures"] += 1
 
@@ -186,22 +156,22 @@ class Refiner:
             self._graph_flags.release()
         self._graph = self._graph_flags = None
         if self._buf is not None:
-            self._buf.pop("rg", None)
+            self._buf.rg = None
         self.gmap.optimizer.zero_grad(set_to_none=True)
 
     def _state(self, b):
         """Everything an iteration writes."""
         opt = self.gmap.optimizer
         return [p.data for p in self.gmap.params()] + list(opt.exp_avg) + list(opt.exp_avg_sq) + \
-               [opt.t_dev, opt.device_lrs(), b["iter_dev"], self.gmap.max_radii_2d, b["acc"]]
+               [opt.t_dev, opt.device_lrs(), b.step.iter_dev, self.gmap.max_radii_2d, b.acc]
 
     @torch.no_grad()
     def _replay_chunk(self, b, vps, i0, n, iters, m):
-        b["sticky"].zero_()
+        b.sticky.zero_()
         for i in range(i0, i0 + n):
             vp = vps[self.sequence[i]]
-            b["rgb"].copy_(vp.rgb); b["R"].copy_(vp.R); b["T"].copy_(vp.T)
-            cam.fused_camera_matrices(b["R"], b["T"], self.intr.projection_matrix, out=b["cam3"])
+            b.rgb.copy_(vp.rgb); b.R.copy_(vp.R); b.T.copy_(vp.T)
+            cam.fused_camera_matrices(b.R, b.T, self.intr.projection_matrix, out=b.cam3)
             self._graph.replay()
             self._account(b, i, iters, m)
         self.stats["replays"] += n
@@ -216,10 +186,11 @@ class Refiner:
             raise ValueError("refinement needs at least one keyframe and one iteration")
         self.sequence = self.draw_sequence(len(self._vps), iters, self.seed)
         self._iters, self._done, self._window = iters, 0, min(iters // 4, 1000)
-        b = self._buffers()
-        b["iter_dev"].zero_()
-        b["acc"].zero_()
-        self.gmap.optimizer.device_lrs()
+        if self._buf is None or self._buf.P != len(self.gmap):
+            self._drop_graph()
+            self._buf = _Buffers(self.gmap, self.intr)
+        self._buf.step.set_iteration(0)
+        self._buf.acc.zero_()
 
     def step_eager(self) -> int:
         """The next iteration of the sequence, eagerly (exact-count forward).  Returns the index of the keyframe it used."""
@@ -246,7 +217,7 @@ class Refiner:
             if _rast.check_overflow():
                 # instances were dropped somewhere in the chunk: back to its start, a capture with the capacity that
                 # check_overflow() doubled (or what the keyframes measure now, if that is more), the same chunk again
-                doubled = int(_rast.capacity_hint(b["P"], W, H) or 0)
+                doubled = int(_rast.capacity_hint(b.P, W, H) or 0)
                 with torch.no_grad():
                     for t, s in zip(self._state(b), snap):
                         t.copy_(s)
@@ -263,7 +234,7 @@ class Refiner:
 
     def finish(self) -> Dict:
         m = self._window
-        means = self._buf["acc"].cpu() / max(m, 1)                      # the ONE read-back
+        means = self._buf.acc.cpu() / max(m, 1)                      # the ONE read-back
         self._drop_graph()
         if self.gmap.lr_schedule is not None:
             self.gmap.optimizer.sync_lrs_from_device()

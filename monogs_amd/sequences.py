@@ -12,7 +12,7 @@ import torch
 from . import camera as cam
 from .frames import Intrinsics, Viewpoint
 from .gaussian_map import GaussianMap
-from .mapping import render_map
+from .map_step import render_map
 from .synthetic import make_scene
 
 

@@ -18,7 +18,8 @@ import torch
 from .frames import Viewpoint, position_error
 from .gaussian_map import GaussianMap
 from .map_arena import MapArena
-from .mapping import WindowMapper, render_map
+from .map_step import render_map
+from .mapping import WindowMapper
 from .monocular import is_monocular, monocular_frames, pseudo_depth, valid_rgb
 from .sequences import make_room_sequence, make_sequence      # make_sequence: re-exported, bench.py imports it (and run_slam) from here
 from .tracking import TrackingGraph, track_eager

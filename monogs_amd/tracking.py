@@ -10,7 +10,7 @@ import torch
 from . import camera as cam
 from . import fused_losses
 from .frames import Viewpoint
-from .mapping import render_map
+from .map_step import render_map
 from .pose_optim import PoseAdam
 from .rasterizer import GaussianRasterizer
 from .renderer import raster_settings

@@ -120,7 +120,7 @@ def test_refinement_iteration_matches_the_reference_loop_step_for_step(native_li
         pkg, terms = mirror.forward_backward(k)
         # gradients of xyz / rgb / opacity / scaling: the "torch loss" bar of the mapping mirror test (relative L2 < 1e-3)
         worst["grad"] = max(worst["grad"], _check_gradients(refiner, mirror, (n, "torch loss"), "torch loss"))
-        rg = refiner._buf["rg"]
+        rg = refiner._buf.rg
         for name, got in (("loss", rg.loss), ("l1", rg.l1), ("ssim", rg.ssim)):
             # the value bar of tests/test_gpu_ssim.py (1e-4 absolute) on all three terms
             d = abs(float(got) - float(terms[name]))

@@ -52,6 +52,31 @@ def test_names_live_in_their_modules():
     assert reexported is make_sequence and ROOM_SURFACES == 18
 
 
+def test_the_map_step_has_one_home():
+    """The activations, their backward and the schedule step are each launched from ONE place; the window mapper and the refiner
+    reach them through ``map_step`` and name none of them; what only renders the map does not import the window mapper."""
+    symbols = ("mgs_activate_forward", "mgs_activate_backward", "mgs_lr_schedule_step")
+    calls = {s: [] for s in symbols}
+    for path in sorted(glob.glob(os.path.join(PKG, "*.py"))):
+        with open(path) as f:
+            tree = ast.parse(f.read())
+        for node in ast.walk(tree):
+            if isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr in calls:
+                calls[node.func.attr].append((os.path.basename(path), node.lineno))
+    assert all(len(v) == 1 for v in calls.values()), calls
+    for name in ("mapping.py", "refinement.py"):
+        with open(os.path.join(PKG, name)) as f:
+            text = f.read()
+        assert not [s for s in symbols if s in text], name
+    for name in ("tracking.py", "sequences.py"):
+        with open(os.path.join(PKG, name)) as f:
+            names = list(_imported_names(ast.parse(f.read())))
+        assert not [n for n in names if "mapping" in n.split(".")], name
+    import monogs_amd.map_step
+    import monogs_amd.mapping
+    assert monogs_amd.mapping.render_map is monogs_amd.map_step.render_map
+
+
 def test_the_dataset_readers_do_not_load_the_harness():
     code = ("import sys; import monogs_amd.dataset, monogs_amd.frame_ingest, monogs_amd.renderer; "
             "sys.exit(1 if 'monogs_amd.slam_harness' in sys.modules else 0)")
