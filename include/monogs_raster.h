@@ -170,6 +170,10 @@ int mgs_debug_set_radix_spin_limit(uint32_t limit);
  * "radix_scanned" (0 = one kernel per pass with a gather of the earlier tiles' counts, 1 = counted tiles: two kernels per
  * pass, no waiting between workgroups -- honoured from 64 k pairs), "radix_ballot_rank" (1 = rank with wave ballots instead of
  * returning LDS atomics: the reference the sort tests compare with), "scan_small" (0 = the two-launch scan at every size),
+ * "pre_scan" (per-tile path, mgs_binning_path() == 1: -1 / 1 = default, the per-Gaussian forward kernel scans the tiles touched
+ * by its own workgroup's 256 Gaussians and one launch scans the block sums -- "scan_small" then has no effect there; 0 = the
+ * scan as launches of its own over the rectangles, as on the global path.  Set it between whole forwards, not between
+ * mgs_forward_preprocess and the render call that consumes its geometry scratch; the same tables either way),
  * "dup_slot_major" (0 / 1 = the duplicate kernel's emission balanced by Gaussians / by output slots at every size),
  * "tile_sort_fused" (per-tile path: 1 = default, each blend forward workgroup sorts its own tile's list first; 0 = the
  * per-tile depth sort as a launch of its own between the tile sort and the blend forward; the same lists either way),

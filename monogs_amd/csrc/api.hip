@@ -33,7 +33,7 @@ GeometryState GeometryState::carve(void* base, int P) {
     g.iota_alt = (uint32_t*)take(p, (size_t)P * sizeof(uint32_t));
     g.perm = (uint32_t*)take(p, (size_t)P * sizeof(uint32_t));
     g.point_offsets = (uint32_t*)take(p, (size_t)P * sizeof(uint32_t));
-    g.scan_blocks = (uint32_t*)take(p, ((size_t)scan_nblocks(P) + 64) * sizeof(uint32_t));
+    g.scan_blocks = (uint32_t*)take(p, ((size_t)scan_nblocks(P, SCAN_ITEMS_PRE) + 64) * sizeof(uint32_t));
     g.clamped = (uint8_t*)take(p, (size_t)P * 4);
     g.rect = (uint2*)take(p, (size_t)P * sizeof(uint2));
     g.rect_sorted = (uint2*)take(p, (size_t)P * sizeof(uint2));
@@ -196,18 +196,19 @@ int mgs_forward_preprocess(const mgs_camera* cam, int32_t P, const float* means3
     tm.mark();
     const bool exclusive = (cam->flags & MGS_FLAG_EXCLUSIVE_DEVICE) != 0;
     const bool per_tile = binning_path(P, cam->image_width, cam->image_height) != 0;
+    const int items = scan_items(P, cam->image_width, cam->image_height);      // (the decision launch_preprocess_forward took)
     if (per_tile) {                         // no global depth sort: the scan runs in index order (binning.hip)
         tm.mark();
-        if (int rc = launch_scan(g, P, s, exclusive, g.rect)) return rc;
+        if (int rc = launch_scan(g, P, s, exclusive, g.rect, items)) return rc;
     } else {
         if (int rc = launch_depth_sort(g, P, depth_sort_payload(P, cam->image_width, cam->image_height), s, exclusive)) return rc;
         tm.mark();
-        if (int rc = launch_scan(g, P, s, exclusive, g.rect_sorted)) return rc;
+        if (int rc = launch_scan(g, P, s, exclusive, g.rect_sorted, items)) return rc;
     }
     tm.mark();
     if (num_rendered) {
         uint32_t total = 0, sort_errors[RADIX_ERROR_WORDS] = {0, 0, 0, 0};
-        MGS_HIP(hipMemcpyAsync(&total, g.scan_blocks + scan_nblocks(P), sizeof(uint32_t), hipMemcpyDeviceToHost, s));   // grand total
+        MGS_HIP(hipMemcpyAsync(&total, g.scan_blocks + scan_nblocks(P, items), sizeof(uint32_t), hipMemcpyDeviceToHost, s));   // grand total
         MGS_HIP(hipMemcpyAsync(sort_errors, radix_depth_error_flag(g.sort_temp, (uint64_t)P), sizeof(sort_errors),
                                hipMemcpyDeviceToHost, s));
         // the status word of an EARLIER forward on this stream rides along: its kernels are done by the time this copy runs,
@@ -497,6 +498,7 @@ int mgs_debug_set_option(const char* name, int64_t value) {
     if (name && !strcmp(name, "blend_bwd_split_min")) { g_opt_blend_bwd_split_min = value < 0 ? 4 : (int)value; return 0; }
     if (name && !strcmp(name, "blend_bwd_split_frac")) { g_opt_blend_bwd_split_frac = value < 0 ? 32 : (int)value; return 0; }
     if (name && !strcmp(name, "scan_small")) { g_opt_scan_small = (int)value; return 0; }
+    if (name && !strcmp(name, "pre_scan")) { g_opt_pre_scan = (int)value; return 0; }
     if (name && !strcmp(name, "tile_sort_fused")) { g_opt_tile_sort_fused = value < 0 ? 1 : (int)value; return 0; }
     if (name && !strcmp(name, "knn_grid_min")) { g_opt_knn_grid_min = value > 0x7FFFFFFF ? 0x7FFFFFFF : (int)value; return 0; }
     set_error("mgs_debug_set_option: unknown option");

@@ -19,27 +19,17 @@
 namespace mgs {
 
 // ------------------------------------------------------------------------------------------------
-// inclusive scan of uint32 in two launches: per-block local scan + block sums, exclusive scan of the block sums
-// (+ the grand total).  Global offset of element i = local[i] + block_sums[i / SCAN_ITEMS].  256 threads x 8 items.
+// inclusive scan of uint32 in two steps: per-block local scan + block sums, exclusive scan of the block sums
+// (+ the grand total).  Global offset of element i = local[i] + block_sums[i / items], items = scan_items() of the forward:
+//   SCAN_ITEMS (2048; 256 threads x 8 items): scan_local_kernel, a launch of its own over the rectangles -- the global path,
+//     where the scan runs in depth order, after the depth sort;
+//   SCAN_ITEMS_PRE (256): the per-tile path, where the scan runs in index order: preprocess_forward_kernel has the
+//     rectangles in registers and scans its own workgroup's (preprocess.hip); only scan_blocks_kernel is launched.
+// The consumers (duplicate_kernel) take the granularity as a shift.
 // ------------------------------------------------------------------------------------------------
 constexpr int SCAN_THREADS = 256;
-__device__ __forceinline__ int scan_nblocks_dev(int P) { return (P + SCAN_ITEMS - 1) / SCAN_ITEMS; }
+__device__ __forceinline__ int scan_nblocks_dev(int P, int shift) { return (P + (1 << shift) - 1) >> shift; }
 constexpr int SCAN_PER_THREAD = SCAN_ITEMS / SCAN_THREADS;
-
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, int) { return wave_incl_scan_dpp(v); }
-
-// block-wide exclusive prefix of one value per thread; returns the prefix, writes the total
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t& total, uint32_t* smem /* >=5 */) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const uint32_t incl = wave_incl_scan(v, lane);
-    if (lane == 63) smem[wv] = incl;
-    __syncthreads();
-    uint32_t base = 0;
-    for (int w = 0; w < wv; ++w) base += smem[w];
-    total = smem[0] + smem[1] + smem[2] + smem[3];
-    __syncthreads();
-    return base + incl - v;
-}
 
 // Items of a scan block are dealt out wave by wave, row by row: wave w owns items [w * 512, (w + 1) * 512) of the block, item
 // (i, lane) = i * 64 + lane of them -- every load and every store of a wave is 64 consecutive elements.  (The first version
@@ -90,17 +80,46 @@ __global__ void __launch_bounds__(SCAN_THREADS) scan_local_kernel(const uint2* _
     if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
 }
 
-// single block: exclusive scan of the block sums in place (nblocks <= a few thousand)
-__global__ void __launch_bounds__(SCAN_THREADS) scan_blocks_kernel(uint32_t* block_sums, int nblocks) {
-    __shared__ uint32_t smem[8];
+// single workgroup: exclusive scan of the block sums in place.  1024 threads x 8 items: the 7 813 sums of 256 Gaussians each
+// at C5 are ONE iteration (256 threads x 1 item took 31 dependent ones); larger maps loop.  Items are dealt out as in
+// scan_block_rows: wave w owns items [w * 512, (w + 1) * 512) of the iteration, item (i, lane) = i * 64 + lane of them.
+constexpr int SCANB_THREADS = 1024, SCANB_PER_THREAD = 8, SCANB_WAVES = SCANB_THREADS / WAVE;
+constexpr int SCANB_ITEMS = SCANB_THREADS * SCANB_PER_THREAD;
+__global__ void __launch_bounds__(SCANB_THREADS) scan_blocks_kernel(uint32_t* block_sums, int nblocks) {
+    __shared__ uint32_t smem[SCANB_WAVES];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     uint32_t carry = 0;
-    for (int start = 0; start < nblocks; start += SCAN_THREADS) {
-        const int i = start + threadIdx.x;
-        const uint32_t v = i < nblocks ? block_sums[i] : 0u;
-        uint32_t total;
-        const uint32_t ex = block_excl_scan(v, total, smem);
-        if (i < nblocks) block_sums[i] = carry + ex;
+    for (int start = 0; start < nblocks; start += SCANB_ITEMS) {          // (workgroup-uniform: every thread reaches the barriers)
+        const int cbase = start + wv * (SCANB_PER_THREAD * WAVE);
+        uint32_t v[SCANB_PER_THREAD], incl[SCANB_PER_THREAD];
+#pragma unroll
+        for (int i = 0; i < SCANB_PER_THREAD; ++i) {
+            const int idx = cbase + i * WAVE + lane;
+            v[i] = idx < nblocks ? block_sums[idx] : 0u;
+        }
+        uint32_t run = 0;                                                  // wave-uniform: rows before this one
+#pragma unroll
+        for (int i = 0; i < SCANB_PER_THREAD; ++i) {
+            const uint32_t sc = wave_incl_scan_dpp(v[i]);
+            incl[i] = run + sc;
+            run += (uint32_t)__builtin_amdgcn_readlane((int)sc, 63);
+        }
+        if (lane == 0) smem[wv] = run;
+        __syncthreads();
+        uint32_t wbase = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < SCANB_WAVES; ++w) {
+            const uint32_t t = smem[w];
+            wbase += w < wv ? t : 0u;
+            total += t;
+        }
+#pragma unroll
+        for (int i = 0; i < SCANB_PER_THREAD; ++i) {
+            const int idx = cbase + i * WAVE + lane;
+            if (idx < nblocks) block_sums[idx] = carry + wbase + incl[i] - v[i];
+        }
         carry += total;
+        __syncthreads();                                                   // smem is rewritten by the next iteration
     }
     if (threadIdx.x == 0) block_sums[nblocks] = carry;      // grand total = number of instances R (read back by the exact path)
 }
@@ -157,17 +176,35 @@ __global__ void __launch_bounds__(SCAN_THREADS) scan_small_kernel(const uint2* _
     if (threadIdx.x == 0 && bid == nb - 1) block_sums[nb] = s_prefix + total;
 }
 int g_opt_scan_small = -1;          // mgs_debug_set_option("scan_small", -1 | 0 | 1): 0 = always the two-launch scan
-bool scan_is_small(int P) { return g_opt_scan_small != 0 && scan_nblocks(P) <= SCAN_SMALL_MAX_BLOCKS; }
+int g_opt_pre_scan = -1;            // mgs_debug_set_option("pre_scan", -1 | 0 | 1): 0 = per-tile path scans with launches of its own
+// The ONE host-side place that decides the scan's granularity: preprocess (does it scan?), launch_scan (what is left to
+// launch), launch_duplicate (how the offsets are put together) and the exact path's read-back all ask here.
+int scan_items(int P, int W, int H) {
+    return (g_opt_pre_scan != 0 && binning_path(P, W, H) != 0) ? SCAN_ITEMS_PRE : SCAN_ITEMS;
+}
+// (SCAN_ITEMS granularity only: the single-launch scan writes GLOBAL sums)
+static bool scan_is_small(int P, int items) {
+    return items == SCAN_ITEMS && g_opt_scan_small != 0 && scan_nblocks(P, SCAN_ITEMS) <= SCAN_SMALL_MAX_BLOCKS;
+}
 
 // (There is no third "add the block offset" pass: the only consumer of the offsets, duplicate_kernel, adds
-//  block_sums[i / SCAN_ITEMS] itself -- one launch and a 16-byte-per-Gaussian read-modify-write less.)
+//  block_sums[i / items] itself -- one launch and a 16-byte-per-Gaussian read-modify-write less.)
 
 // (Measured and rejected: a single-workgroup scan for small P -- 1024 threads x a serial run of dependent
 //  gathers each -- took ~300 us at P = 38 k against ~15 us for the three launches below: latency, not launches.)
-int launch_scan(const GeometryState& g, int P, hipStream_t s, bool exclusive, const uint2* rects) {
+//
+// What is launched:  items == SCAN_ITEMS_PRE (per-tile path): preprocess_forward_kernel already wrote the block-local sums
+// of its 256-Gaussian workgroups and their totals -- scan_blocks_kernel alone (the "scan_small" option has no effect).
+// items == SCAN_ITEMS: scan_small_kernel (one launch, P <= 131 072) or scan_local_kernel + scan_blocks_kernel.
+int launch_scan(const GeometryState& g, int P, hipStream_t s, bool exclusive, const uint2* rects, int items) {
     if (P == 0) return 0;
-    const int nb = scan_nblocks(P);
-    if (scan_is_small(P)) {
+    const int nb = scan_nblocks(P, items);
+    if (items == SCAN_ITEMS_PRE) {
+        hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(SCANB_THREADS), 0, s, g.scan_blocks, nb);
+        MGS_HIP(hipGetLastError());
+        return 0;
+    }
+    if (scan_is_small(P, items)) {
         hipLaunchKernelGGL(scan_small_kernel, dim3(nb), dim3(SCAN_THREADS), 0, s, rects, g.point_offsets, g.scan_blocks,
                            g.scan_status, P, nb, const_cast<uint32_t*>(radix_depth_error_flag(g.sort_temp, (uint64_t)P)),
                            exclusive ? 0 : 1);
@@ -176,7 +213,7 @@ int launch_scan(const GeometryState& g, int P, hipStream_t s, bool exclusive, co
     }
     hipLaunchKernelGGL(scan_local_kernel, dim3(nb), dim3(SCAN_THREADS), 0, s, rects, g.point_offsets,
                        g.scan_blocks, P);
-    hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(SCAN_THREADS), 0, s, g.scan_blocks, nb);
+    hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(SCANB_THREADS), 0, s, g.scan_blocks, nb);
     MGS_HIP(hipGetLastError());
     return 0;
 }
@@ -189,15 +226,45 @@ int launch_scan(const GeometryState& g, int P, hipStream_t s, bool exclusive, co
 // key = tile << tshift | depth27 >> lo, value = (depth27 & (2^lo - 1)) << (32 - lo) | index (common.h).  Depths beyond
 // the narrow range are clamped to DEPTH_KEY_NARROW; tile_depth_sort_kernel re-sorts that trailing run by the full key.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void dup_pair(uint32_t gidx, const uint32_t* __restrict__ depth_key, int lo, uint32_t& val,
-                                         uint32_t& kfield) {
+// (`k`: depth_key[gidx], loaded by the caller beside its other inputs; `keyed`: there is a depth key)
+__device__ __forceinline__ void dup_pair(uint32_t gidx, bool keyed, uint32_t k, int lo, uint32_t& val, uint32_t& kfield) {
     val = gidx; kfield = 0u;
-    if (depth_key) {
-        const uint32_t k = depth_key[gidx];
+    if (keyed) {
         const uint32_t d = k == 0xFFFFFFFFu ? DEPTH_KEY_NARROW : min(k - DEPTH_KEY_SUB, DEPTH_KEY_NARROW);
         kfield = d >> lo;
         if (lo) val |= (d & ((1u << lo) - 1u)) << (32 - lo);
     }
+}
+// Slot t of a rectangle w tiles wide -> (row, column) = (t / w, t % w).  t < 65 536 (`small`: the grid has at most 2^16
+// tiles -- always on the per-tile path), so t and w are exact in float32 and one multiply by a reciprocal rounded DOWN gives
+// the quotient or one less: v_rcp_f32 is good to 1 ulp, two ulps are taken off, so r <= 1 / w and t * r <= t / w
+// <= q + 1 - 1 / w; the product's rounding error is below q * 2^-24 < 1 / w, so it stays below q + 1, and from below it loses
+// less than 65 536 * 5 * 2^-24 < 1.  One correction step settles it (tests/test_dup_slot_decode.py runs the formula over every
+// t < 65 536, w <= 4 096 and every reciprocal 1 ulp around the exact one).  A full 32-bit division is ~40 instructions per
+// emitted slot; larger grids keep it.
+__device__ __forceinline__ void dup_divmod(uint32_t t, uint32_t w, bool small, uint32_t& q, uint32_t& rem) {
+    if (small) {
+        const float r = __uint_as_float(__float_as_uint(__builtin_amdgcn_rcpf((float)w)) - 2u);
+        q = (uint32_t)((float)t * r);
+        rem = t - q * w;
+        if (rem >= w) { q += 1u; rem -= w; }
+    } else {
+        q = t / w; rem = t - q * w;
+    }
+}
+// What a lane needs of the Gaussian that owns its slot, as ONE 16-byte LDS entry (a ds_read_b128; six 4-byte gathers
+// before) + the key field: {first slot, tile id of the rectangle's corner, width, value of the pair}
+__device__ __forceinline__ uint4 dup_entry(uint32_t first, int x0, int y0, int w, int gx, uint32_t val) {
+    return make_uint4(first, (uint32_t)(y0 * gx + x0), (uint32_t)max(w, 1), val);
+}
+__device__ __forceinline__ void dup_emit(const uint4 e, uint32_t kf, uint32_t o, int gx, int tshift, bool small,
+                                         uint32_t* __restrict__ keys, uint32_t* __restrict__ vals, uint32_t& key) {
+    uint32_t yy, xx;
+    dup_divmod(o - e.x, e.z, small, yy, xx);
+    const uint32_t tid = e.y + yy * (uint32_t)gx + xx;
+    key = (tid << tshift) | kf;
+    keys[o] = key;
+    vals[o] = e.w;
 }
 __global__ void __launch_bounds__(256) duplicate_kernel(int P, const uint2* __restrict__ rects,
                                                         const uint32_t* __restrict__ perm,
@@ -210,6 +277,8 @@ __global__ void __launch_bounds__(256) duplicate_kernel(int P, const uint2* __re
                                                         int ntiles, uint32_t* __restrict__ zero_ptr, size_t zero_words,
                                                         uint32_t* __restrict__ count, uint32_t* __restrict__ overflow,
                                                         const uint32_t* __restrict__ depth_err, int offsets_global,
+                                                        int scan_sh /* log2 of the scan block: offsets[] are local to it */,
+                                                        int small_grid /* <= 2^16 tiles: dup_divmod */,
                                                         uint32_t* __restrict__ hist /* [4][256] or NULL */, int hist_passes,
                                                         int n_threads /* of this launch */, int slot_major,
                                                         unsigned long long* __restrict__ prepare /* GeometryState::prepare or NULL */) {
@@ -221,13 +290,48 @@ __global__ void __launch_bounds__(256) duplicate_kernel(int P, const uint2* __re
         prepare[0] = 0ull;
     }
     const int lane = threadIdx.x & 63;
-    // scratch of the tile sort that follows (was its own launch)
-    grid_zero(zero_ptr, zero_words, (size_t)n_threads, 256);
+    // Gaussian-major emission: every per-Gaussian input -- rectangle, depth key, the scanned offset of the Gaussian before and
+    // its block's sum -- is requested HERE, before the housekeeping below, so that the wave waits for memory once.  (They
+    // were three DEPENDENT round trips: the depth key, then the rectangle, then, only for a Gaussian that touches a tile,
+    // the offset and the block sum -- most of the life of a wave that then emits ~170 pairs.)  Lanes past P load the
+    // last Gaussian's and ignore them; a culled Gaussian's offset is read for nothing, which is cheaper than the trip.
+    uint2 in_rect = make_uint2(0u, 0u);
+    uint32_t in_gidx = 0, in_dkey = 0, in_off = 0, in_bsum = 0;
+    if (!slot_major && P > 0) {                            // (grid-uniform)
+        const int ci = i < P ? i : P - 1, cp = ci > 0 ? ci - 1 : 0;
+        in_rect = rects[ci];                               // the rectangle preprocess computed (0 x 0: culled)
+        in_off = offsets[cp];
+        if (!offsets_global) in_bsum = block_sums[cp >> scan_sh];
+        if (perm) {                                        // (global path: the key's address depends on perm -- one more trip)
+            in_gidx = perm[ci];
+            if (depth_key) in_dkey = depth_key[in_gidx];
+        } else {
+            in_gidx = (uint32_t)ci;
+            if (depth_key) in_dkey = depth_key[ci];
+        }
+    }
     // a depth sort whose look-back timed out left perm / rect_sorted / offsets partly unwritten: emit nothing (the live
     // count is published as 0, so the tile sort, the ranges and the blend kernels have nothing to do either)
     const bool depth_bad = depth_err && radix_failed(depth_err) != 0u;
+    uint32_t idx = 0, nt = 0, off = 0, kf = 0;
+    int x0 = 0, y0 = 0, x1 = 0;
+    // (an empty asm that "uses" the loaded values: the compiler otherwise sinks each load to its first use again)
+    asm volatile("" ::"v"(in_rect.x), "v"(in_rect.y), "v"(in_gidx), "v"(in_dkey), "v"(in_off), "v"(in_bsum));
+    if (i < P && !slot_major) {                          // everything in depth (or index) order and coalesced: no gather
+        dup_pair(in_gidx, depth_key != nullptr, in_dkey, lo, idx, kf);
+        const uint2 r = in_rect;
+        const int w = (int)(r.y & 0xFFFFu), h = (int)(r.y >> 16);
+        nt = (uint32_t)(w * h);
+        x0 = (int)(r.x & 0xFFFFu); y0 = (int)(r.x >> 16); x1 = x0 + w;
+    }
+    if (depth_bad) nt = 0;                               // (wave-uniform, grid-uniform)
+    if (nt) off = i == 0 ? 0u : in_off + in_bsum;
+    // ---- housekeeping, behind the wait for the inputs: the wait then covers loads only (the memory counter is in order:
+    //      a wait placed behind these stores would also wait for their acknowledgements)
+    // scratch of the tile sort that follows (was its own launch)
+    grid_zero(zero_ptr, zero_words, (size_t)n_threads, 256);
     if (i == 0 && count) {                               // capacity mode: live instance count + overflow flag (was a launch)
-        const uint32_t R = (P > 0 && !depth_bad) ? block_sums[scan_nblocks_dev(P)] : 0u;
+        const uint32_t R = (P > 0 && !depth_bad) ? block_sums[scan_nblocks_dev(P, scan_sh)] : 0u;
         count[0] = min(R, r_cap);
         count[1] = R > r_cap ? 1u : 0u;
     }
@@ -239,24 +343,14 @@ __global__ void __launch_bounds__(256) duplicate_kernel(int P, const uint2* __re
     // what is still {~0, 0} afterwards into {0, 0})
     if (i < ntiles) ranges[i] = make_uint2(0xFFFFFFFFu, 0u);
     if (i < P) n_touched[i] = 0;                         // (was a memset)
-    uint32_t idx = 0, nt = 0, off = 0, kf = 0;
-    int x0 = 0, y0 = 0, x1 = 0;
-    if (i < P) {                                         // everything in depth (or index) order and coalesced: no gather
-        dup_pair(perm ? perm[i] : (uint32_t)i, depth_key, lo, idx, kf);
-        const uint2 r = rects[i];                        // the rectangle preprocess computed (0 x 0: culled)
-        const int w = (int)(r.y & 0xFFFFu), h = (int)(r.y >> 16);
-        nt = (uint32_t)(w * h);
-        x0 = (int)(r.x & 0xFFFFu); y0 = (int)(r.x >> 16); x1 = x0 + w;
-    }
-    if (depth_bad) nt = 0;                               // (wave-uniform, grid-uniform)
-    if (nt) off = i == 0 ? 0u : offsets[i - 1] + (offsets_global ? 0u : block_sums[(i - 1) / SCAN_ITEMS]);
     // Load-balanced emission.  The 64 Gaussians of the wave own the consecutive output slots [S, E); the wave walks
     // that range 64 slots at a time (aligned, so every store is one coalesced 256-byte line) and each lane finds the
     // owner of its slot: owners mark their first slot in LDS, an inclusive max-scan spreads the mark to the right.
     // A thread walking its own rectangle instead wrote 64 interleaved streams per wave (73 us at C5 for 26 MB).
     __shared__ uint32_t s_own[4][WAVE];
-    __shared__ uint32_t s_idx[4][WAVE], s_off[4][WAVE], s_kf[4][WAVE];
-    __shared__ int s_x0[4][WAVE], s_y0[4][WAVE], s_w[4][WAVE];
+    __shared__ uint4 s_ent[4][WAVE];                                        // dup_entry
+    __shared__ uint32_t s_kf[4][WAVE];
+    const bool small = small_grid != 0;
     // Digit counts of the emitted tile ids (every pass of the tile sort), collected in LDS while the keys are written and
     // added to the global table once per workgroup: the one-sweep sort then needs no histogram launch of its own.
     __shared__ uint32_t s_hist[2][256];                                     // tile ids have <= 16 bits: two digits
@@ -272,14 +366,14 @@ __global__ void __launch_bounds__(256) duplicate_kernel(int P, const uint2* __re
         // 19 us for 5.3 M at C5 where every splat is small).  Here every wave of the launch owns an equal share [s0, s1) of
         // the slots, finds the Gaussian that owns s0 by a 64-way search of the scanned offsets (3 dependent probes at
         // 100 k Gaussians) and walks the Gaussians from there, 64 at a time, with the same owner-marking as below.
-        const uint32_t R_all = (P > 0 && !depth_bad) ? block_sums[scan_nblocks_dev(P)] : 0u;
+        const uint32_t R_all = (P > 0 && !depth_bad) ? block_sums[scan_nblocks_dev(P, scan_sh)] : 0u;
         const uint32_t R_emit = min(R_all, r_cap);
         const uint32_t n_waves = (uint32_t)n_threads / WAVE;
         const uint32_t CH = (((R_emit + n_waves - 1u) / n_waves) + 63u) & ~63u;
         const uint32_t wave_id = (uint32_t)blockIdx.x * 4u + (uint32_t)wv;
         const uint64_t s0w = (uint64_t)wave_id * CH;                             // (64-bit: wave_id * CH may pass 2^32 for R near 2^32)
         const uint32_t s0 = s0w < (uint64_t)R_emit ? (uint32_t)s0w : R_emit, s1 = (uint64_t)s0 + CH < (uint64_t)R_emit ? s0 + CH : R_emit;
-        auto incl = [&](uint32_t k) { return offsets[k] + (offsets_global ? 0u : block_sums[k / SCAN_ITEMS]); };
+        auto incl = [&](uint32_t k) { return offsets[k] + (offsets_global ? 0u : block_sums[k >> scan_sh]); };
         uint32_t g = 0;
         if (s0 < s1) {      // smallest g with incl(g) > s0: it exists because incl(P - 1) = R_all > s0
             uint32_t lo = 0, hi = (uint32_t)P;
@@ -306,14 +400,15 @@ __global__ void __launch_bounds__(256) duplicate_kernel(int P, const uint2* __re
                 gw = (int)(r.y & 0xFFFFu);
                 ntg = (uint32_t)(gw * (int)(r.y >> 16));
                 gx0 = (int)(r.x & 0xFFFFu); gy0 = (int)(r.x >> 16);
-                dup_pair(perm ? perm[gi] : gi, depth_key, lo, idg, kfg);
+                const uint32_t pg = perm ? perm[gi] : gi;
+                dup_pair(pg, depth_key != nullptr, depth_key ? depth_key[pg] : 0u, lo, idg, kfg);
             }
             const uint32_t exc = inc - ntg;                                    // first slot of the Gaussian
             uint32_t Eg = valid ? inc : 0u;                                    // end of the group's slots = the largest inclusive sum
 #pragma unroll
             for (int o2 = 32; o2 > 0; o2 >>= 1) Eg = max(Eg, (uint32_t)__shfl_xor((int)Eg, o2, 64));
             __builtin_amdgcn_wave_barrier();
-            s_idx[wv][lane] = idg; s_kf[wv][lane] = kfg; s_off[wv][lane] = exc; s_x0[wv][lane] = gx0; s_y0[wv][lane] = gy0; s_w[wv][lane] = max(gw, 1);
+            s_ent[wv][lane] = dup_entry(exc, gx0, gy0, gw, gx, idg); s_kf[wv][lane] = kfg;
             const uint32_t e = min(s1, Eg);
             const uint32_t cb0 = sl & ~63u;
             const unsigned long long before = __builtin_amdgcn_ballot_w64(ntg != 0u && exc < cb0);
@@ -334,13 +429,8 @@ __global__ void __launch_bounds__(256) duplicate_kernel(int P, const uint2* __re
                 const uint32_t o = cb + lane;
                 if (owner != 0u && o >= sl && o < e) {                        // (e <= R_emit <= r_cap: never past the buffers)
                     const uint32_t L = owner - 1u;
-                    const uint32_t t = o - s_off[wv][L];
-                    const uint32_t w = (uint32_t)s_w[wv][L];
-                    const uint32_t yy = t / w, xx = t - yy * w;
-                    const uint32_t tid = (uint32_t)((s_y0[wv][L] + (int)yy) * gx + s_x0[wv][L] + (int)xx);
-                    const uint32_t key = (tid << tshift) | s_kf[wv][L];
-                    keys[o] = key;
-                    vals[o] = s_idx[wv][L];
+                    uint32_t key;
+                    dup_emit(s_ent[wv][L], s_kf[wv][L], o, gx, tshift, small, keys, vals, key);
                     if (hist) {
                         atomicAdd(&s_hist[0][(key >> tshift) & 0xFFu], 1u);
                         if (hist_passes > 1) {      // (few values: the lanes that share the first active lane's digit add once)
@@ -364,7 +454,7 @@ __global__ void __launch_bounds__(256) duplicate_kernel(int P, const uint2* __re
         }
         return;
     }
-    s_idx[wv][lane] = idx; s_kf[wv][lane] = kf; s_off[wv][lane] = off; s_x0[wv][lane] = x0; s_y0[wv][lane] = y0; s_w[wv][lane] = max(x1 - x0, 1);
+    s_ent[wv][lane] = dup_entry(off, x0, y0, x1 - x0, gx, idx); s_kf[wv][lane] = kf;
     const unsigned long long live = __builtin_amdgcn_ballot_w64(nt != 0);
     if (live == 0ull && !hist) return;                                      // wave-uniform
     const int first = live ? __builtin_ctzll(live) : 0, lastl = live ? 63 - __builtin_clzll(live) : 0;
@@ -387,13 +477,8 @@ __global__ void __launch_bounds__(256) duplicate_kernel(int P, const uint2* __re
         const uint32_t o = cb + lane;
         if (owner != 0u && o < E && o < r_cap) {                            // capacity mode: never write past the buffers
             const uint32_t L = owner - 1u;
-            const uint32_t t = o - s_off[wv][L];
-            const uint32_t w = (uint32_t)s_w[wv][L];
-            const uint32_t yy = t / w, xx = t - yy * w;
-            const uint32_t tid = (uint32_t)((s_y0[wv][L] + (int)yy) * gx + s_x0[wv][L] + (int)xx);
-            const uint32_t key = (tid << tshift) | s_kf[wv][L];
-            keys[o] = key;
-            vals[o] = s_idx[wv][L];
+            uint32_t key;
+            dup_emit(s_ent[wv][L], s_kf[wv][L], o, gx, tshift, small, keys, vals, key);
             if (hist) {
                 atomicAdd(&s_hist[0][(key >> tshift) & 0xFFu], 1u);
                 if (hist_passes > 1) {
@@ -441,13 +526,14 @@ int launch_duplicate(const mgs_camera& cam, int P, const GeometryState& g, const
     if (sort_n > 0) radix_zero_region(b.sort_temp, sort_n, sort_bits, &zero_ptr, &zero_words);
     const bool count_digits = P > 0 && sort_bits <= 16 && radix_wants_hist(sort_n);
     const int tb = tile_bits(cam.image_width, cam.image_height);
+    const int items = scan_items(P, cam.image_width, cam.image_height);
     hipLaunchKernelGGL(duplicate_kernel, dim3(n_threads / 256), dim3(256), 0, s, P, per_tile ? g.rect : g.rect_sorted,
                        per_tile ? nullptr : g.perm, per_tile ? g.depth_key : nullptr, per_tile ? 32 - tb : 0,
                        per_tile ? tile_depth_lo_bits(tb) : 0, g.point_offsets,
                        g.scan_blocks, b.keys_a, b.vals_a, tiles_x(cam.image_width), tiles_y(cam.image_height),
                        (uint32_t)(r_cap > 0xFFFFFFFFull ? 0xFFFFFFFFull : r_cap), n_touched, img.ranges, ntiles, zero_ptr,
                        zero_words, count, overflow, depth_err,
-                       (P > 0 && scan_is_small(P)) ? 1 : 0,
+                       (P > 0 && scan_is_small(P, items)) ? 1 : 0, scan_shift(items), ntiles <= 65536 ? 1 : 0,
                        count_digits ? g.tile_hist : nullptr, (sort_bits + 7) / 8, n_threads, slot_major ? 1 : 0,
                        P > 0 ? g.prepare : nullptr);
     MGS_HIP(hipGetLastError());

@@ -131,7 +131,7 @@ struct GeometryState {
     uint32_t* iota_alt;       // [P] reads neither)
     uint32_t* perm;           // [P] Gaussian index in (depth, index) order -- culled ones last: written by the sort's final pass
     uint32_t* point_offsets;  // [P] inclusive scan, in depth order, of the tiles each Gaussian touches (w * h of its rectangle)
-    uint32_t* scan_blocks;    // [scan_nblocks(P) + 64]
+    uint32_t* scan_blocks;    // [scan_nblocks(P, SCAN_ITEMS_PRE) + 64]: sized for the finer of the two scan granularities
     uint8_t* clamped;         // [P][4] SH colour clamp flags
     uint2* rect;              // [P] tile rectangle {x0 | y0 << 16, w | h << 16} (w = h = 0: culled), by Gaussian index; or
                               //     (depth_sort_payload()) uint32[2 P]: the first half x0 | y0 << 8 | w << 16 | h << 24,
@@ -179,8 +179,17 @@ struct BinningState {
     static BinningState carve(void* base, uint64_t R, int W, int H);
 };
 
-constexpr int SCAN_ITEMS = 2048;   // items per scan block
-inline int scan_nblocks(int P) { return (P + SCAN_ITEMS - 1) / SCAN_ITEMS; }
+// Items per scan block.  The scan kernels of binning.hip take SCAN_ITEMS Gaussians per workgroup; on the per-tile path
+// preprocess_forward_kernel scans its own 256 Gaussians (SCAN_ITEMS_PRE) and no scan_local launch follows.  Which one a
+// forward uses is decided in ONE place, scan_items(), and travels to the kernels as a shift.
+constexpr int SCAN_ITEMS = 2048;
+constexpr int SCAN_ITEMS_PRE = 256;      // = the workgroup of preprocess_forward_kernel
+inline int scan_nblocks(int P, int items) { return (P + items - 1) / items; }
+// items per scan block of a forward of P Gaussians at W x H (preprocess, launch_scan, launch_duplicate and the exact path's
+// read-back of the grand total all ask here): SCAN_ITEMS_PRE when preprocess scans (per-tile path, option "pre_scan" not 0)
+int scan_items(int P, int W, int H);
+inline int scan_shift(int items) { return items == SCAN_ITEMS_PRE ? 8 : 11; }
+static_assert(SCAN_ITEMS == 1 << 11 && SCAN_ITEMS_PRE == 1 << 8, "scan_shift");
 
 inline int tiles_x(int W) { return (W + TILE - 1) / TILE; }
 inline int tiles_y(int H) { return (H + TILE - 1) / TILE; }
@@ -228,7 +237,8 @@ inline float* backward_tau_out(void* scratch, int P) { return backward_tau_part(
 // `prepare_grad_acc` (or NULL): the pose part behind the accumulator is cleared by the kernel itself; the accumulator's address is
 // left in g.prepare[0] for the render call that follows, whose blend forward clears the P gradient lines (blend.hip)
 // `rects`: the rectangles in the order the scan runs in (rect_sorted after a depth sort, rect by index on the per-tile path)
-int launch_scan(const GeometryState& g, int P, hipStream_t s, bool exclusive, const uint2* rects);
+// `items`: scan_items() of this forward; SCAN_ITEMS_PRE: preprocess wrote the block-local sums, only the block sums are scanned
+int launch_scan(const GeometryState& g, int P, hipStream_t s, bool exclusive, const uint2* rects, int items);
 // `r_cap`: capacity of the binning buffers; `count` (device): [0] live instance count min(R, r_cap), [1] overflow flag
 // `per_tile`: emit in Gaussian-index order with the depth bits packed into the pairs (binning_path() == 1)
 int launch_duplicate(const mgs_camera& cam, int P, const GeometryState& g, const BinningState& b, uint64_t r_cap,
@@ -287,7 +297,7 @@ int launch_tile_depth_sort(const mgs_camera& cam, const TileSortArgs& ts, const 
 int set_radix_spin_limit(uint32_t limit);
 extern bool g_opt_blend_bwd_transposed_set;
 extern int g_dbg_last_bwd_split;
-extern int g_opt_radix_ballot_rank, g_opt_radix_scanned, g_opt_radix_xcd_band, g_opt_knn_grid_min, g_opt_scan_small, g_opt_dup_slot_major, g_opt_blend_bwd_transposed, g_opt_blend_bwd_split, g_opt_blend_bwd_split_min, g_opt_blend_bwd_split_frac;      // test knobs (mgs_debug_set_option)
+extern int g_opt_radix_ballot_rank, g_opt_radix_scanned, g_opt_radix_xcd_band, g_opt_knn_grid_min, g_opt_scan_small, g_opt_pre_scan, g_opt_dup_slot_major, g_opt_blend_bwd_transposed, g_opt_blend_bwd_split, g_opt_blend_bwd_split_min, g_opt_blend_bwd_split_frac;      // test knobs (mgs_debug_set_option)
 // `sort_err`: the tile sort's error words (NULL: nothing was sorted); a raised word empties every tile and sets
 // MGS_STATUS_TILE_SORT_TIMEOUT in *status (what ranges_kernel did until round 4).  `tile_sort` (per-tile depth order, or
 // NULL): every workgroup first sorts its tile's list (tile_sort.h)

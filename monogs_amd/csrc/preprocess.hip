@@ -174,6 +174,8 @@ struct PreArgs {
     int rot_aligned16;        // rotations may be read with 16-byte loads
     uint32_t* zero_ptr;       // scratch of the depth sort that follows: cleared here instead of by its own launch
     size_t zero_words;
+    uint32_t* point_offsets;  // SCAN: [P] block-local inclusive scan of the tiles touched, [ceil(P / 256)] block totals
+    uint32_t* scan_blocks;
     float* grad_acc;          // optional: accumulator of the backward that will follow ([P][16] + pose slots + 16): the
                               //           pose part is cleared here, the P lines by the blend forward that follows, which
     unsigned long long* prepare;   //      finds the accumulator's address (or 0: nothing to clear) in prepare[0]
@@ -281,16 +283,10 @@ __device__ __forceinline__ bool preprocess_one(const PreArgs& a, const Cam& c, i
 
 // COV: the 3-D covariance is given (else scales + rotations).  PRECOMP: colours are given (else spherical harmonics).
 // Compile-time, so that the input loads below form one branch-free group.
+// One Gaussian, idx < P: loads, projection, every per-Gaussian output.  Returns the tiles it touches (w * h of its
+// rectangle; 0: culled).  `s_rec`: the workgroup's record hand-over rows (per wave; a lane's fifth float4 is padding).
 template <bool COV, bool PRECOMP>
-__global__ void __launch_bounds__(256) preprocess_forward_kernel(PreArgs a) {
-    const int idx = blockIdx.x * 256 + threadIdx.x;        // (launched with 256 threads; blockDim would be a packet fetch)
-    grid_zero(a.zero_ptr, a.zero_words, (size_t)((a.P + 255) / 256) * 256, 256);
-    if (a.grad_acc && blockIdx.x == 0) {              // pose-gradient slots + the six output floats: (TAU_SLOTS + 1) lines
-        float4* t4 = reinterpret_cast<float4*>(a.grad_acc + (size_t)a.P * GRAD_FLOATS);
-        for (int i = threadIdx.x; i < (TAU_SLOTS + 1) * 4; i += 256) t4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    if (idx == 0) a.prepare[0] = (unsigned long long)(uintptr_t)a.grad_acc;      // (a forward without prepare_backward: 0)
-    if (idx >= a.P) return;
+__device__ __forceinline__ uint32_t preprocess_gaussian(const PreArgs& a, const int idx, float4 (*s_rec)[WAVE * 5]) {
     // ---- every per-Gaussian input is requested up front: ONE memory round trip before the arithmetic starts (a load
     //      placed behind each early exit used to cost a dependent round trip of its own; the 32 bytes this reads for a
     //      Gaussian that turns out to be culled are cheaper than the latency they hide)
@@ -336,7 +332,6 @@ __global__ void __launch_bounds__(256) preprocess_forward_kernel(PreArgs a) {
         // (rows of 80 bytes: conflict-free 16-byte writes) and lane l stores 16 bytes of the records (l >> 2) + 16 k,
         // k = 0..3: each store instruction covers one contiguous KB minus the culled Gaussians' holes -- the shape the
         // gradient-line clear below already has.
-        __shared__ float4 s_rec[4][WAVE * 5];
         const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, wave_first = idx - lane;
         if (wave_first + WAVE <= a.P) {                       // wave-uniform: every lane is here
             const unsigned long long vm = __builtin_amdgcn_ballot_w64(vis);
@@ -357,6 +352,40 @@ __global__ void __launch_bounds__(256) preprocess_forward_kernel(PreArgs a) {
     // (The gradient lines of the accumulator are NOT cleared here: this kernel runs at the copy ceiling, where their 64 bytes
     //  per Gaussian cost 17 us at 2 M.  The blend forward of the render call that follows clears them while the memory
     //  system is mostly idle -- blend.hip, through a.prepare.)
+    return vis ? (o.rect.y & 0xFFFFu) * (o.rect.y >> 16) : 0u;
+}
+
+// SCAN (per-tile path, scan_items() == SCAN_ITEMS_PRE): the workgroup also writes the block-local inclusive scan of the tiles
+// its 256 Gaussians touch to point_offsets[] and its total to scan_blocks[blockIdx.x] -- what scan_local_kernel
+// (binning.hip) computes from the rectangles this kernel has just had in registers, in the same (index) order; one
+// scan_blocks_kernel launch then finishes the scan.
+template <bool COV, bool PRECOMP, bool SCAN>
+__global__ void __launch_bounds__(256) preprocess_forward_kernel(PreArgs a) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;        // (launched with 256 threads; blockDim would be a packet fetch)
+    grid_zero(a.zero_ptr, a.zero_words, (size_t)((a.P + 255) / 256) * 256, 256);
+    if (a.grad_acc && blockIdx.x == 0) {              // pose-gradient slots + the six output floats: (TAU_SLOTS + 1) lines
+        float4* t4 = reinterpret_cast<float4*>(a.grad_acc + (size_t)a.P * GRAD_FLOATS);
+        for (int i = threadIdx.x; i < (TAU_SLOTS + 1) * 4; i += 256) t4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    if (idx == 0) a.prepare[0] = (unsigned long long)(uintptr_t)a.grad_acc;      // (a forward without prepare_backward: 0)
+    __shared__ float4 s_rec[4][WAVE * 5];
+    // (a predicate, not an early return: with SCAN every thread of every workgroup must reach the barrier below)
+    uint32_t nt = 0u;                                      // lanes past P and culled Gaussians count 0
+    if (idx < a.P) nt = preprocess_gaussian<COV, PRECOMP>(a, idx, s_rec);
+    if (SCAN) {
+        // all 256 threads are here, EXEC is full: DPP wave scan, the four waves joined through LDS.  The wave totals go to
+        // the padding float4 of lane 0's hand-over row (never touched by the hand-over), so the kernel's LDS -- 20 480
+        // bytes, exactly eight workgroups per compute unit -- does not grow.
+        const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+        const uint32_t sc = wave_incl_scan_dpp(nt);
+        uint32_t* tot = reinterpret_cast<uint32_t*>(&s_rec[0][4]);
+        if (lane == 63) tot[wv] = sc;
+        __syncthreads();
+        const uint32_t t0 = tot[0], t1 = tot[1], t2 = tot[2], t3 = tot[3];
+        const uint32_t base = (wv > 0 ? t0 : 0u) + (wv > 1 ? t1 : 0u) + (wv > 2 ? t2 : 0u);
+        if (idx < a.P) a.point_offsets[idx] = base + sc;
+        if (threadIdx.x == 0) a.scan_blocks[blockIdx.x] = (t0 + t1) + (t2 + t3);
+    }
 }
 
 int launch_preprocess_forward(const mgs_camera& cam, int P, const float* means3D, const float* shs,
@@ -389,10 +418,19 @@ int launch_preprocess_forward(const mgs_camera& cam, int P, const float* means3D
     a.zero_words += (size_t)((char*)a.zero_ptr - (char*)g.scan_status) / 4;
     a.zero_ptr = (uint32_t*)g.scan_status;
     const dim3 grid((P + 255) / 256), block(256);
-    if (cov3D_precomp && colors_precomp) hipLaunchKernelGGL((preprocess_forward_kernel<true, true>), grid, block, 0, s, a);
-    else if (cov3D_precomp) hipLaunchKernelGGL((preprocess_forward_kernel<true, false>), grid, block, 0, s, a);
-    else if (colors_precomp) hipLaunchKernelGGL((preprocess_forward_kernel<false, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((preprocess_forward_kernel<false, false>), grid, block, 0, s, a);
+    // the scan folded in (see the kernel): the same host-side decision launch_scan and launch_duplicate take
+    const bool scan = scan_items(P, cam.image_width, cam.image_height) == SCAN_ITEMS_PRE;
+    a.point_offsets = g.point_offsets; a.scan_blocks = g.scan_blocks;
+#define MGS_PRE(COV, PRECOMP)                                                                                      \
+    do {                                                                                                           \
+        if (scan) hipLaunchKernelGGL((preprocess_forward_kernel<COV, PRECOMP, true>), grid, block, 0, s, a);       \
+        else hipLaunchKernelGGL((preprocess_forward_kernel<COV, PRECOMP, false>), grid, block, 0, s, a);           \
+    } while (0)
+    if (cov3D_precomp && colors_precomp) MGS_PRE(true, true);
+    else if (cov3D_precomp) MGS_PRE(true, false);
+    else if (colors_precomp) MGS_PRE(false, true);
+    else MGS_PRE(false, false);
+#undef MGS_PRE
     MGS_HIP(hipGetLastError());
     return 0;
 }

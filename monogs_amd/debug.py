@@ -86,7 +86,8 @@ def forward_tables(rs, means3D, opacities, colors_precomp=None, shs=None, scales
     # geometry scratch after rec (GeometryState::carve, csrc/api.hip): depth_key, depth_alt, iota, iota_alt (the depth
     # sort's ping-pong buffers), perm (its result), point_offsets, scan_blocks, clamped, rect (by Gaussian index: consumed
     # by the sort, possibly as its packed payload), rect_sorted {x0 | y0 << 16, w | h << 16} in depth order
-    o_rect = o + 6 * _au(P * 4) + _au(((P + 2047) // 2048 + 64) * 4) + _au(P * 4)
+    # (scan_blocks holds one sum per 256 Gaussians -- the scan granularity of the per-tile path -- + 64 words)
+    o_rect = o + 6 * _au(P * 4) + _au(((P + 255) // 256 + 64) * 4) + _au(P * 4)
     if per_tile:
         # rect {x0 | y0 << 16, w | h << 16} by Gaussian index (what the scan and duplicate read); perm from the depth keys
         keys = view(geom, o, P * 4, torch.int32).long() & 0xFFFFFFFF
