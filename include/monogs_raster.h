@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define MGS_ABI_VERSION 19
+#define MGS_ABI_VERSION 20
 #define MGS_TILE 16 /* tile edge in pixels; ranges are per 16x16 tile */
 
 /* GaussianRasterizationSettings, minus `prefiltered` / `debug` which are call flags
@@ -331,6 +331,47 @@ int mgs_features_forward(const mgs_camera* cam, int32_t P, int32_t K, uint64_t n
 int mgs_features_backward(const mgs_camera* cam, int32_t P, int32_t K, uint64_t num_rendered, const void* geometry,
                           const void* binning, const void* image, const float* dL_dout /* [K,H,W] */,
                           float* dL_dfeatures /* [P,K], cleared here */, void* stream);
+
+/* ---- headless viewer (ABI v20) ---------------------------------------------------------------------------
+ * What the reference's viewer window shows (viewer/slam_viewer.py: the shaders rgb / segmentation, depth, time, elipsoids and
+ * the camera / trajectory line sets over them), as uint8 [H, W, 3] images on the device.  None of these calls synchronises the
+ * host or keeps state; every clear is a kernel, so all of them may be captured in a hipGraph.
+ *
+ * mgs_viewer_ellipsoids: through the tables of a finished forward (LIFETIME as mgs_features_forward: `geometry`, `binning`,
+ * `image` are only READ), out[:, p] = colour[g] exp(power) of the first entry g of pixel p's tile list, in blend order, with
+ * power <= 0 and min(0.99, opacity exp(power)) > threshold; hit[p] = g (int32; hit may be NULL).  No such entry: black, -1.
+ * The whole list is walked, whatever n_contrib says.  threshold must lie in [1/255, 1) (the viewer passes 0.4); P == 0: black.
+ *
+ * mgs_viewer_lines: segments [S, 4] int32 {x0, y0, x1, y1} in 1/16 pixel, pixel centres at multiples of 16, already clipped to
+ * a guard rectangle by the caller.  Clears the owner image in `scratch` and rasterises with integer arithmetic only: along the
+ * axis of the larger extent (x on a tie) every integer pixel position inside the segment, the other coordinate rounded half
+ * up; a segment without such a position paints the pixel its first endpoint rounds to.  owner = highest segment index + 1.
+ * Pixels outside the image are skipped.  S == 0 only clears.
+ *
+ * mgs_viewer_compose: out [H, W, 3] uint8 from the float image `src` by `mode`:
+ *   MGS_VIEWER_RGB         src [3, H, W]: trunc(clip(c, 0, 1) * 255)                       (also the segmentation shader)
+ *   MGS_VIEWER_DEPTH       src [H, W] >= 0: lut[jet index of src / max(src)], unnormalised when the maximum is 0; the maximum
+ *                          is found on the device (`scratch`) and never read back
+ *   MGS_VIEWER_TIME        src [H, W]: lut[jet index of src]                               (the reference shows the opacity image)
+ *   MGS_VIEWER_ELLIPSOIDS  src [3, H, W]: floor(clip(c, 0, 1) * 255 + 0.5)                 (GL's unorm conversion)
+ * jet index of x = clamp(floor(x * 256), 0, 255); a NaN gives black.  `lut` [256, 3] uint8 is needed by DEPTH and TIME.
+ * n_segments > 0: the owner image a preceding mgs_viewer_lines left in the same `scratch` is resolved on top, pixel p with
+ * owner k > 0 taking seg_rgb[k - 1] ([n_segments, 3] uint8); n_segments == 0: no overlay, the owner image is not read.
+ * `scratch`: mgs_viewer_scratch_bytes(W, H) bytes, 256-byte aligned: the depth maximum's word at byte 0, the owner image
+ * (int32 [H, W]) at byte 256.  Bad arguments (NULL pointers, an unknown mode, non-positive sizes) return 1 before any launch;
+ * mgs_viewer_scratch_bytes returns 0 for them. */
+#define MGS_VIEWER_RGB 0
+#define MGS_VIEWER_DEPTH 1
+#define MGS_VIEWER_TIME 2
+#define MGS_VIEWER_ELLIPSOIDS 3
+size_t mgs_viewer_scratch_bytes(int32_t W, int32_t H);
+int mgs_viewer_ellipsoids(const mgs_camera* cam, int32_t P, uint64_t num_rendered, const void* geometry, const void* binning,
+                          const void* image, float threshold, float* out /* [3,H,W] */, int32_t* hit /* [H,W] or NULL */,
+                          void* stream);
+int mgs_viewer_lines(int32_t W, int32_t H, const int32_t* segments /* [S,4] */, int32_t n_segments, void* scratch, void* stream);
+int mgs_viewer_compose(int32_t mode, int32_t W, int32_t H, const float* src, const uint8_t* lut /* [256,3] */,
+                       const uint8_t* seg_rgb /* [S,3] */, int32_t n_segments, void* scratch, uint8_t* out /* [H,W,3] */,
+                       void* stream);
 
 /* visible[P] (1 byte each) = view-space z > 0.2 (upstream markVisible; unused by MonoGS). */
 int mgs_mark_visible(int32_t P, const float* means3D, const float* viewmatrix, const float* projmatrix,

@@ -12,4 +12,8 @@ def __getattr__(name):
     if name in ("StereoMatcher", "StereoIngest", "EuRoCParser", "StereoDataset", "load_stereo_dataset", "rectify_map"):
         from . import stereo
         return getattr(stereo, name)
+    # the headless viewer (monogs_amd.viewer) likewise
+    if name in ("HeadlessViewer", "Snapshot"):
+        from . import viewer
+        return getattr(viewer, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

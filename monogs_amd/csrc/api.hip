@@ -411,6 +411,45 @@ int mgs_features_backward(const mgs_camera* cam, int32_t P, int32_t K, uint64_t 
     return launch_features_backward(*cam, P, K, g, b, img, dL_dout, dL_dfeatures, (hipStream_t)stream);
 }
 
+size_t mgs_viewer_scratch_bytes(int32_t W, int32_t H) { return (W > 0 && H > 0) ? viewer_scratch_bytes(W, H) : 0; }
+
+int mgs_viewer_ellipsoids(const mgs_camera* cam, int32_t P, uint64_t num_rendered, const void* geometry, const void* binning,
+                          const void* image, float threshold, float* out, int32_t* hit, void* stream) {
+    if (check_cam(cam)) return 1;
+    if (P < 0) { set_error("P must be >= 0"); return 1; }
+    if (check_map_size(P)) return 1;
+    if (!(threshold >= 1.0f / 255.0f && threshold < 1.0f)) { set_error("threshold must lie in [1/255, 1)"); return 1; }
+    if (!out) { set_error("out must be non-NULL"); return 1; }
+    if (P > 0 && (!geometry || !image)) { set_error("geometry, image must be non-NULL"); return 1; }
+    if (P > 0 && num_rendered > 0 && !binning) { set_error("binning scratch is NULL"); return 1; }
+    const int W = cam->image_width, H = cam->image_height;
+    GeometryState g = GeometryState::carve(const_cast<void*>(geometry), P);
+    ImageState img = ImageState::carve(const_cast<void*>(image), W, H);
+    BinningState b = BinningState::carve(const_cast<void*>(binning), num_rendered, W, H);
+    return launch_viewer_ellipsoids(*cam, P, g, b, img, threshold, out, hit, (hipStream_t)stream);
+}
+
+int mgs_viewer_lines(int32_t W, int32_t H, const int32_t* segments, int32_t n_segments, void* scratch, void* stream) {
+    if (W <= 0 || H <= 0) { set_error("image size must be positive"); return 1; }
+    if (n_segments < 0 || (n_segments > 0 && !segments)) { set_error("n_segments must be >= 0 and segments non-NULL"); return 1; }
+    if (!scratch || (size_t)scratch % 256 != 0) { set_error("scratch must be non-NULL and 256-byte aligned"); return 1; }
+    return launch_viewer_lines(W, H, segments, n_segments, scratch, (hipStream_t)stream);
+}
+
+int mgs_viewer_compose(int32_t mode, int32_t W, int32_t H, const float* src, const uint8_t* lut, const uint8_t* seg_rgb,
+                       int32_t n_segments, void* scratch, uint8_t* out, void* stream) {
+    if (mode < MGS_VIEWER_RGB || mode > MGS_VIEWER_ELLIPSOIDS) { set_error("unknown viewer mode"); return 1; }
+    if (W <= 0 || H <= 0) { set_error("image size must be positive"); return 1; }
+    if (!src || !out) { set_error("src, out must be non-NULL"); return 1; }
+    if ((mode == MGS_VIEWER_DEPTH || mode == MGS_VIEWER_TIME) && !lut) { set_error("depth and time need the colour table"); return 1; }
+    if (n_segments < 0 || (n_segments > 0 && !seg_rgb)) { set_error("n_segments must be >= 0 and seg_rgb non-NULL"); return 1; }
+    if ((mode == MGS_VIEWER_DEPTH || n_segments > 0) && (!scratch || (size_t)scratch % 256 != 0)) {
+        set_error("scratch must be non-NULL and 256-byte aligned");
+        return 1;
+    }
+    return launch_viewer_compose(mode, W, H, src, lut, seg_rgb, n_segments, scratch, out, (hipStream_t)stream);
+}
+
 int mgs_debug_blend_stats(const mgs_camera* cam, int32_t P, uint64_t R, const void* geometry, const void* binning,
                            const void* image, uint64_t* stats_dev, void* stream) {
     if (check_cam(cam)) return 1;

@@ -319,6 +319,13 @@ int launch_features_forward(const mgs_camera& cam, int P, int K, const GeometryS
                             float min_opacity, hipStream_t s);
 int launch_features_backward(const mgs_camera& cam, int P, int K, const GeometryState& g, const BinningState& b,
                              const ImageState& img, const float* dL_dout, float* dL_dfeatures, hipStream_t s);
+// the headless viewer (viewer.hip): the ellipsoid walk reads the three scratch states, lines and compose share `scratch`
+int launch_viewer_ellipsoids(const mgs_camera& cam, int P, const GeometryState& g, const BinningState& b, const ImageState& img,
+                             float threshold, float* out, int32_t* hit, hipStream_t s);
+size_t viewer_scratch_bytes(int W, int H);
+int launch_viewer_lines(int W, int H, const int32_t* segs, int S, void* scratch, hipStream_t s);
+int launch_viewer_compose(int mode, int W, int H, const float* src, const uint8_t* lut, const uint8_t* seg_rgb, int S,
+                          void* scratch, uint8_t* out, hipStream_t s);
 struct GeomBackwardArgs {
     const float *means3D, *shs, *colors_precomp, *opacities, *scales, *rotations, *cov3D_precomp;
     const int32_t* radii;

@@ -64,6 +64,13 @@ def _setup(c):
         raise ValueError('sensor must be "depth" or "monocular"')
     if c.kf_selection not in ("interval", "overlap"):
         raise ValueError('kf_selection must be "interval" or "overlap"')
+    if c.viewer_dir is not None:
+        from .viewer import MODES
+        c.viewer_modes = tuple(c.viewer_modes)
+        if [m for m in c.viewer_modes if m not in MODES]:
+            raise ValueError(f"viewer_modes must be among {MODES}")
+        if "segmentation" in c.viewer_modes and c.nr_objects is None:
+            raise ValueError("the segmentation mode needs nr_objects")
     if c.prune_after_mapping is None:
         c.prune_after_mapping = bool(c.map_surgery)
     if c.sequence is not None:
@@ -103,7 +110,8 @@ def _setup(c):
         size_trace=[],                                  # (frame, Gaussians in the map after that keyframe's mapping)
         stats=dict(kf_extend_s=0.0, track_capture_s=0.0, track_s=0.0, track_iters=0, tracked=0, map_s=0.0, map_iters=0,
                    keyframes=0, renders=0),
-        stats_kf=dict(keyframes_selected=0, evicted_by_cutoff=0, evicted_by_size=0))
+        stats_kf=dict(keyframes_selected=0, evicted_by_cutoff=0, evicted_by_size=0),
+        viewer=None, viewer_files=[])                   # ``viewer_dir``: the HeadlessViewer of the run and the PNGs it wrote
 
 
 def _map_window(s, iters, init=False):
@@ -236,6 +244,34 @@ def _map_keyframe(s, i, vp, pkg=None, t0=None):
     _drop_tracking_graph(s)                      # the map changed: the captured tracking graph is stale
 
 
+def _viewer_frames(s, vp, tag):
+    """``viewer_dir``: one PNG per mode of ``viewer_modes`` from a camera behind ``vp``'s pose (the reference's ``view_dir_behind``,
+    what its viewer follows the tracker with), ``<tag>_<mode>.png``: the map as it is, the keyframes' frustums and trajectory, the
+    current and the ground-truth camera.  Outside every time bracket; the capacity hint of the map's shape is put back afterwards
+    (an exact forward from another camera would overwrite the one the captured iterations were sized with)."""
+    import os
+
+    from . import rasterizer as R
+    from .viewer import HeadlessViewer, Snapshot, save_png, view_behind
+    c = s.c
+    if s.viewer is None:
+        os.makedirs(c.viewer_dir, exist_ok=True)
+        s.viewer = HeadlessViewer(s.intr, s.bg)
+    key = (len(s.gmap), int(s.intr.width), int(s.intr.height))
+    hint = R.capacity_hint(*key)
+    snap = Snapshot.from_map(s.gmap, [s.frames[k] for k in s.kf_list], current=vp, gt=vp if vp.R_gt is not None else None)
+    cam = view_behind(vp, s.intr)
+    with R.exact_counts():
+        for mode in c.viewer_modes:
+            path = os.path.join(c.viewer_dir, f"{tag}_{mode}.png")
+            save_png(s.viewer.frame(snap, cam, mode=mode), path)
+            s.viewer_files.append(path)
+    if hint is None:
+        R.forget_capacity(*key)
+    else:
+        R.reserve_capacity(*key, hint)
+
+
 def _finish(s):
     """What follows the last frame; returns the result keys it adds.  ``eval_render``: ``eval`` (``evaluation.eval_rendering`` before
     and after the refinement) and ``ate`` over the keyframes, as the reference reports them.  ``refine_iters``: that many iterations
@@ -291,6 +327,8 @@ def _report(s, extra):
         gaussians_after_keyframe=[n for _, n in s.size_trace], log=sl[:6] + sl[-4:] if len(sl) > 10 else sl)
     if c.nr_objects is not None:
         out.update(map=gmap, frame_list=frames, intr=s.intr)
+    if c.viewer_dir is not None:         # (only then: tests/golden/run_slam_contract.json pins the keys of the default flags)
+        out["viewer"] = dict(dir=str(c.viewer_dir), modes=list(c.viewer_modes), every=int(c.viewer_every), files=list(s.viewer_files))
     if c.sensor == "monocular":          # (a depth run keeps exactly the keys it always had)
         from .evaluation import eval_ate
         out.update(sensor="monocular", ate_sim3=eval_ate(frames, align=True, correct_scale=True),
@@ -327,16 +365,20 @@ def run_slam(n_frames=12, intrinsics="fr3_office", tracking_itr_num=100, mapping
              track_lookahead=1, map_surgery=False, reference_lrs=False, prune_after_mapping=None,
              scene="cloud", reference_densify=False, eager_probe=0, exclusive_device=False,
              kf_selection="interval", check_viewpoints_overlap=False, kf_trace=None, refine_iters=0, eval_render=False,
-             sequence=None, nr_objects=None, sensor="depth"):
+             sequence=None, nr_objects=None, sensor="depth", viewer_dir=None, viewer_modes=("rgb",), viewer_every=0):
     """Tracks and maps a sequence in one process; returns tracking / mapping rates, iterations and the trajectory error (``_report``).
     Every argument is described where it acts: ``_setup``, ``_track_frame``, ``_select_keyframe``, ``_map_keyframe``, ``_map_window``,
     ``_finish`` (what follows the last frame).  ``log``: a callable that gets a line per frame.  ``sensor="monocular"`` adds the result
-    keys ``sensor``, ``ate_sim3`` (Sim(3)-aligned ATE over all frames) and ``pseudo_depth_stats``; ``run_slam_two_process`` stays RGB-D."""
+    keys ``sensor``, ``ate_sim3`` (Sim(3)-aligned ATE over all frames) and ``pseudo_depth_stats``; ``run_slam_two_process`` stays RGB-D.
+    ``viewer_dir``: write headless-viewer frames there (``monogs_amd.viewer``), one per mode of ``viewer_modes``, after every
+    ``viewer_every``-th keyframe (0: never) and at the end; only then does the result hold a ``viewer`` entry."""
     s = _setup(SimpleNamespace(**locals()))              # (every argument, by name: must stay the first statement)
     for i, vp in enumerate(s.frames):
         if i == 0:
             vp.update_RT(vp.R_gt, vp.T_gt)
             _map_keyframe(s, 0, vp)
+            if viewer_dir is not None and viewer_every > 0 and s.stats["keyframes"] % viewer_every == 0:
+                _viewer_frames(s, vp, f"kf{s.stats['keyframes']:04d}")
             continue
         n_it = _track_frame(s, vp, s.frames[i - 1], tracking_itr_num, graph_tracking, exclusive_device, track_lookahead)
         s.stats["renders"] += n_it
@@ -344,11 +386,16 @@ def run_slam(n_frames=12, intrinsics="fr3_office", tracking_itr_num=100, mapping
         pkg, t0 = _select_keyframe(s, i, vp)
         if pkg is not None:
             _map_keyframe(s, i, vp, pkg, t0)
+            if viewer_dir is not None and viewer_every > 0 and s.stats["keyframes"] % viewer_every == 0:
+                _viewer_frames(s, vp, f"kf{s.stats['keyframes']:04d}")
         if log:
             cov = (_render_frozen(vp, s.intr, s.gmap, s.bg)["opacity"] > 0.99).float().mean().item()
             log(f"frame {i}: P={s.gmap.get_xyz.shape[0]} track_iters={s.stats['track_iters']} kf={s.stats['keyframes']} "
                 f"pos_err={position_error(vp).item():.4f} m  opaque>0.99={cov:.2f}")
-    return _report(s, _finish(s))
+    extra = _finish(s)
+    if viewer_dir is not None:
+        _viewer_frames(s, s.frames[-1], "final")
+    return _report(s, extra)
 
 
 # ---- the two-process topology of the reference (/root/reference/slam.py:102-179): tracker here, mapper in a spawned process;

@@ -9,6 +9,8 @@ stand-in; the TUM / Replica sequences are not available offline).  Prints one JS
   python tools/slam_bench.py --config tum --room --graph --sensor monocular
       # no depth: RGB-only losses, keyframes back-projected from depth hypotheses (monogs_amd.monocular); with --dataset the depth
       # files are not read (a YAML with Dataset.sensor_type: monocular selects this by itself).  Prints both ATEs to stderr.
+  python tools/slam_bench.py --config tum --room --viewer frames/ --viewer-modes rgb depth elipsoids --viewer-every 2
+      # PNGs of what the reference's viewer window would show, from a camera behind the current pose (monogs_amd.viewer)
 """
 import argparse
 import json
@@ -63,6 +65,10 @@ if __name__ == "__main__":
     ap.add_argument("--stride", type=int, default=1, help="with --dataset: take every N-th frame")
     ap.add_argument("--sensor", default=None, choices=["depth", "monocular"],
                     help="monocular: run without depth (default: what the --dataset YAML's Dataset.sensor_type says, else depth)")
+    ap.add_argument("--viewer", default=None, metavar="DIR",
+                    help="write headless-viewer frames (monogs_amd.viewer) to DIR: after every --viewer-every-th keyframe and at the end")
+    ap.add_argument("--viewer-modes", nargs="+", default=["rgb"], choices=["rgb", "segmentation", "depth", "time", "elipsoids"])
+    ap.add_argument("--viewer-every", type=int, default=0, help="with --viewer: a frame set after every N-th keyframe (0: only at the end)")
     a = ap.parse_args()
     from monogs_amd.slam_harness import run_slam
     cfg = dict(CONFIGS[a.config])
@@ -89,7 +95,8 @@ if __name__ == "__main__":
                    graph_mapping=a.graph and not a.eager_mapping, track_lookahead=a.lookahead, map_surgery=a.surgery,
                    reference_lrs=a.reference_lrs, scene="room" if a.room else "cloud", reference_densify=a.reference_densify,
                    eager_probe=a.eager_probe, kf_selection=a.kf_selection, check_viewpoints_overlap=a.check_overlap,
-                   refine_iters=a.refine, eval_render=a.eval, sensor=sensor, log=lambda s: print("[slam]", s, file=sys.stderr, flush=True), **cfg)
+                   refine_iters=a.refine, eval_render=a.eval, sensor=sensor, viewer_dir=a.viewer,
+                   viewer_modes=tuple(a.viewer_modes), viewer_every=a.viewer_every, log=lambda s: print("[slam]", s, file=sys.stderr, flush=True), **cfg)
     what = f"{a.dataset}, every {a.stride}. frame" if a.dataset else f"synthetic {a.config}-like sequence"
     out["workload"] = f"{what}, {a.frames} frames" + (" (fork's hard-coded run configuration)" if a.fork else "")
     if sensor == "monocular":
