@@ -740,31 +740,52 @@ struct BtLane {
     unsigned long long m_out, m_q0, m_q1;
     float* grad_acc;
     int qxi = 0, qyi = 0;           // the same origin as integers (WIDE_META flush)
+    // WIDE_META only: what the flush derives from the lane's number, formed ONCE per walk by bs_lane_consts() -- the lane's
+    // float4 of its row's h factors (the w factors are BS_W_OFF behind), its row's metadata record, its float4 of dL/dpixel and
+    // its first pixel
+    const float* hp = nullptr;
+    const BtMetaRec* mp = nullptr;
+    const float* fp = nullptr;
+    float u0 = 0.f, v0 = 0.f;
 };
+// (blend_backward_s_kernel: it walks the forward's survivor masks and compiles to ~50 VGPRs, so the five registers these take
+//  over a whole walk fit under 64; the t-kernel, the A/B partner, keeps re-deriving them per batch)
+__device__ __forceinline__ BtLane bs_lane_consts(BtLane L) {
+    const int q = L.lane & 15, row = L.lane >> 4;
+    L.hp = L.fac + row * (BS_STRIDE / 4) + 4 * q;
+    L.mp = L.meta + row * (BS_STRIDE / 16);
+    L.fp = L.pix + q * 4;
+    L.u0 = (float)(L.qxi + 4 * (q & 1));
+    L.v0 = (float)(L.qyi + (q >> 1));
+    return L;
+}
 template <bool POSE_ONLY, bool WIDE_META = false>     // WIDE_META: metadata records 256 bytes apart, holding index << 6 (blend_backward_s_kernel)
 __device__ __forceinline__ void bt_flush(const BtLane L, int n) {
     // Everything a lane derives from its number here (row, q, three LDS addresses, its first pixel) is RE-derived per batch,
     // ~8 VALU per four survivors: hoisted out of the walk by the compiler these values cost six more VGPRs over the whole
-    // kernel, i.e. a wave per SIMD.  The empty asm keeps the loop-invariant code motion from undoing that.
-    int lane = L.lane;
-    asm volatile("" : "+v"(lane));
-    const int q = lane & 15, row = lane >> 4;
-    // [row][4 q .. 4 q + 3]; WIDE_META (blend_backward_s_kernel): rows BS_STRIDE bytes apart in all three arrays
-    const float* const hp = WIDE_META ? L.fac + row * (BS_STRIDE / 4) + 4 * q : L.fac + 4 * lane;
-    const float4 h4 = *reinterpret_cast<const float4*>(hp);
-    const float4 w4 = *reinterpret_cast<const float4*>(hp + (WIDE_META ? BS_W_OFF / 4 : BT_SLOTS * WAVE));
-    const BtMetaRec me = L.meta[WIDE_META ? row * (BS_STRIDE / 16) : row];
-    // [channel][q][4]: the sixteen lanes of a row read 256 contiguous bytes per channel (conflict-free; laid out [q][channel]
-    // the 64-byte lane stride put four lanes on every bank: 48 M conflict cycles per launch at C5, r03 PMC)
-    const float* const fp = L.pix + q * 4;
+    // kernel, i.e. a wave per SIMD of blend_backward_t_kernel.  The empty asm keeps the loop-invariant code motion from undoing
+    // that.  WIDE_META (blend_backward_s_kernel, which has the registers): they come with L, formed once per walk
+    // (bs_lane_consts) -- the same addresses and the same two floats, so every sum below is unchanged.
+    const float* hp;
+    const BtMetaRec* mp;
+    const float* fp;            // [channel][q][4]: the sixteen lanes of a row read 256 contiguous bytes per channel (conflict-free;
+                                // laid out [q][channel] the 64-byte lane stride put four lanes on every bank: 48 M conflict cycles
+                                // per launch at C5, r03 PMC)
     float u0, v0;
-    if (WIDE_META) {                    // the origin stays in scalar INTEGER registers (see blend_backward_s_kernel); same values
-        int oqx = L.qxi, oqy = L.qyi;
-        asm volatile("" : "+s"(oqx), "+s"(oqy));
-        u0 = (float)(oqx + 4 * (q & 1)), v0 = (float)(oqy + (q >> 1));
+    if (WIDE_META) {            // rows BS_STRIDE bytes apart in all three arrays
+        hp = L.hp; mp = L.mp; fp = L.fp; u0 = L.u0; v0 = L.v0;
     } else {
+        int lane = L.lane;
+        asm volatile("" : "+v"(lane));
+        const int q = lane & 15, row = lane >> 4;
+        hp = L.fac + 4 * lane;  // [row][4 q .. 4 q + 3]
+        mp = L.meta + row;
+        fp = L.pix + q * 4;
         u0 = L.qx0 + (float)(4 * (q & 1)), v0 = L.qy0 + (float)(q >> 1);
     }
+    const float4 h4 = *reinterpret_cast<const float4*>(hp);
+    const float4 w4 = *reinterpret_cast<const float4*>(hp + (WIDE_META ? BS_W_OFF / 4 : BT_SLOTS * WAVE));
+    const BtMetaRec me = *mp;
     const float dy = me.y - v0;
     const float dx0 = me.x - u0, dx1 = dx0 - 1.f, dx2 = dx0 - 2.f, dx3 = dx0 - 3.f;
     const float hx0 = h4.x * dx0, hx1 = h4.y * dx1, hx2 = h4.z * dx2, hx3 = h4.w * dx3;
@@ -1033,7 +1054,7 @@ __device__ __forceinline__ void bs_walk(const BlendArgs& a, const int tile, cons
     const uint32_t slot_bytes = slot < 0 ? 0u : (uint32_t)slot * 4u;
     const unsigned long long m_out = __builtin_amdgcn_ballot_w64(slot >= 0);
     const unsigned long long m_q0 = __builtin_amdgcn_ballot_w64((q & 3) == 0), m_q1 = __builtin_amdgcn_ballot_w64((q & 3) == 1);
-    const BtLane bl{&s_w_ws->h[0][0], s_pix_ws, &s_w_ws->meta[0][0], lane, 0.f, 0.f, slot_bytes, m_out, m_q0, m_q1, grad_acc, qx0i, qy0i};
+    const BtLane bl = bs_lane_consts(BtLane{&s_w_ws->h[0][0], s_pix_ws, &s_w_ws->meta[0][0], lane, 0.f, 0.f, slot_bytes, m_out, m_q0, m_q1, grad_acc, qx0i, qy0i});
     const uint32_t wbase = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)s_w_ws);   // LDS address (SGPR)
     const const_float_p recs = MGS_CONST(reinterpret_cast<const float*>(a.rec));
     uint32_t koff = 0;              // open batch: survivors x 272 = byte offset of the open slot in the slab and in the metadata (SGPR)
