@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define MGS_ABI_VERSION 20
+#define MGS_ABI_VERSION 21
 #define MGS_TILE 16 /* tile edge in pixels; ranges are per 16x16 tile */
 
 /* GaussianRasterizationSettings, minus `prefiltered` / `debug` which are call flags
@@ -331,6 +331,43 @@ int mgs_features_forward(const mgs_camera* cam, int32_t P, int32_t K, uint64_t n
 int mgs_features_backward(const mgs_camera* cam, int32_t P, int32_t K, uint64_t num_rendered, const void* geometry,
                           const void* binning, const void* image, const float* dL_dout /* [K,H,W] */,
                           float* dL_dfeatures /* [P,K], cleared here */, void* stream);
+
+/* ---- Label loss and confusion count of the object layer (ABI v21) ----------------------------------------
+ * Softmax cross-entropy of a blended K-channel image against 8-bit ids, value + gradient to the image, for learning the
+ * per-Gaussian object rows: feat is mgs_features_forward's `out` on the RAW rows (no background term), taken as logits, and
+ * d_feat is what mgs_features_backward takes as dL_dout.
+ *
+ *     counted(p)   = (valid == NULL || valid[p] != 0) && labels[p] < K,    N = number of counted pixels
+ *     L            = (1 / N) sum over counted p of [ logsumexp_k feat[k, p] - feat[labels[p], p] ]
+ *     d_feat[k, p] = (softmax_k(feat[:, p]) - [k == labels[p]]) / N  on counted pixels, exactly 0 elsewhere
+ *
+ * N == 0: L = 0 and d_feat = 0, no NaN.  The softmax is max-subtracted: feat of +-1e4 stays finite.
+ * LAYOUT: feat and d_feat [K, H, W] float32, labels and valid [H, W] bytes (valid may be NULL = every pixel), K is
+ * 1 .. MGS_MAX_FEATURE_CHANNELS, width x height < 2^31.
+ * mgs_label_prepare (once per keyframe: N depends on labels and valid alone) stores count_out[2] = {N, width x height - N} on
+ * the device; mgs_label_loss_grads reads them there (`count`) and, in two launches, writes d_feat (every element, once) and
+ * the loss, a float at scratch + MGS_LABEL_SCRATCH_LOSS.  `scratch`: mgs_label_scratch_bytes() bytes, 8-byte aligned, per
+ * call; the two calls may share one.  Nothing is assumed of scratch, count_out or d_feat on entry and nothing is cleared:
+ * every word read was stored by the same call (per-workgroup partial sums, added in a fixed order).  No atomics: loss and
+ * gradient are bitwise reproducible from call to call.  No state is kept and the host is never synchronised.
+ *
+ * mgs_label_confusion ADDS into counts [K, K] uint32, indexed [gt, pred], one per counted pixel (the rule above, with gt as
+ * labels) whose pred [H, W] int32 -- the `labels` of mgs_features_forward -- lies in 0 .. K-1, and into side[2] =
+ * {counted pixels without such a prediction (-1 = not seen), pixels not counted}.  The caller clears counts and side before
+ * the first call; integer atomics only, so the result is exact and independent of order.
+ *
+ * Bad arguments (K outside 1 .. MGS_MAX_FEATURE_CHANNELS, non-positive sizes, NULL required pointers, a misaligned scratch)
+ * return 1 before anything is launched. */
+#define MGS_LABEL_SCRATCH_LOSS 0
+size_t mgs_label_scratch_bytes(void);
+int mgs_label_prepare(int32_t width, int32_t height, int32_t K, const uint8_t* labels, const uint8_t* valid /* or NULL */,
+                      void* scratch, uint32_t* count_out /* [2] */, void* stream);
+int mgs_label_loss_grads(int32_t width, int32_t height, int32_t K, const float* feat /* [K,H,W] */, const uint8_t* labels,
+                         const uint8_t* valid /* or NULL */, const uint32_t* count /* [2], of mgs_label_prepare */,
+                         void* scratch, float* d_feat /* [K,H,W] */, void* stream);
+int mgs_label_confusion(int32_t width, int32_t height, int32_t K, const int32_t* pred /* [H,W] */, const uint8_t* gt,
+                        const uint8_t* valid /* or NULL */, uint32_t* counts /* [K,K], added to */,
+                        uint32_t* side /* [2], added to */, void* stream);
 
 /* ---- headless viewer (ABI v20) ---------------------------------------------------------------------------
  * What the reference's viewer window shows (viewer/slam_viewer.py: the shaders rgb / segmentation, depth, time, elipsoids and

@@ -16,4 +16,9 @@ def __getattr__(name):
     if name in ("HeadlessViewer", "Snapshot"):
         from . import viewer
         return getattr(viewer, name)
+    # learning and scoring the object layer (monogs_amd.object_layer) likewise
+    if name in ("LabelTarget", "LabelGrads", "label_loss_grads", "get_loss_labels", "label_confusion", "segmentation_scores",
+                "ObjectLayerTrainer", "eval_segmentation", "render_labels"):
+        from . import object_layer
+        return getattr(object_layer, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -11,7 +11,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MGS_LIB_PATH") or os.path.join(_HERE, "lib", "libmonogs_raster.so")   # (override: kernel experiments)
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 c_float_p = C.c_void_p   # device pointers travel as integers (tensor.data_ptr())
 
@@ -92,6 +92,10 @@ SIGNATURES = {
     "mgs_features_forward": (C.c_int, [C.POINTER(MgsCamera), C.c_int32, C.c_int32, C.c_uint64] + [C.c_void_p] * 7
                              + [C.c_float, C.c_void_p]),
     "mgs_features_backward": (C.c_int, [C.POINTER(MgsCamera), C.c_int32, C.c_int32, C.c_uint64] + [C.c_void_p] * 5 + [C.c_void_p]),
+    "mgs_label_scratch_bytes": (C.c_size_t, []),
+    "mgs_label_prepare": (C.c_int, [C.c_int32] * 3 + [C.c_void_p] * 5),
+    "mgs_label_loss_grads": (C.c_int, [C.c_int32] * 3 + [C.c_void_p] * 7),
+    "mgs_label_confusion": (C.c_int, [C.c_int32] * 3 + [C.c_void_p] * 6),
     "mgs_viewer_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "mgs_viewer_ellipsoids": (C.c_int, [C.POINTER(MgsCamera), C.c_int32, C.c_uint64] + [C.c_void_p] * 3 + [C.c_float]
                               + [C.c_void_p] * 3),

@@ -104,16 +104,21 @@ class _RenderFeatures(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out, grad_labels=None):
-        lib = _lib.load()
-        t, K = ctx.tables, ctx.K
-        g = grad_out.to(torch.float32).contiguous()
-        d_feat = torch.empty(t.P, K, dtype=torch.float32, device=t.device)
-        base = t.arena.data_ptr()
-        with _device_guard(t.device):
-            _lib.check(lib.mgs_features_backward(C.byref(t.cam), t.P, K, t.num_rendered, base + t.geom_off,
-                                                 t.binning.data_ptr(), base + t.img_off, g.data_ptr(), d_feat.data_ptr(),
-                                                 _stream()), "mgs_features_backward")
-        return d_feat, None, None, None, None
+        return features_backward(ctx.tables, grad_out, ctx.K), None, None, None, None
+
+
+def features_backward(t: _Tables, d_out: torch.Tensor, K: int) -> torch.Tensor:
+    """``mgs_features_backward`` on the tables ``t`` (``_tables(color)``): ``d_features [P, K]`` from ``d_out [K, H, W]``.  What the
+    autograd node's backward runs; a loop that steps the rows itself (``object_layer.ObjectLayerTrainer``) calls it directly."""
+    lib = _lib.load()
+    g = d_out.to(torch.float32).contiguous()
+    d_feat = torch.empty(t.P, K, dtype=torch.float32, device=t.device)
+    base = t.arena.data_ptr()
+    with _device_guard(t.device):
+        _lib.check(lib.mgs_features_backward(C.byref(t.cam), t.P, K, t.num_rendered, base + t.geom_off,
+                                             t.binning.data_ptr(), base + t.img_off, g.data_ptr(), d_feat.data_ptr(),
+                                             _stream()), "mgs_features_backward")
+    return d_feat
 
 
 def render_features(color: torch.Tensor, features: torch.Tensor, bg: Optional[torch.Tensor] = None,

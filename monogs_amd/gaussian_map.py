@@ -53,18 +53,37 @@ REFERENCE_LR_SCHEDULE = dict(lr_init=0.0016 * 6.0, lr_final=0.0000016 * 6.0, lr_
 
 
 class GaussianMap:
-    """Isotropic RGB map with the reference's activations."""
+    """Isotropic RGB map with the reference's activations.
+
+    ``nr_objects=K``: a row of K object scores per Gaussian.  ``learn_objects=True``: the rows are learned logits with an
+    optimiser of their own, ``object_optimizer = GaussianAdam([rows], [object_lr])``, stepped by
+    ``object_layer.ObjectLayerTrainer`` and carried through every piece of map surgery.  ``object_lr = 0.05`` is a CHOICE: the
+    reference has no value, because its row is not learned; 0.05 is this project's rate for the other logit-like parameter,
+    the raw opacity.  With the default ``False`` nothing changes: no optimiser, rows without grad, not in ``params()``."""
 
     def __init__(self, device, capturable=False, fused_adam=True, lrs: Sequence[float] = DEFAULT_LRS,
-                 percent_dense: float = 0.01, nr_objects: Optional[int] = None):
+                 percent_dense: float = 0.01, nr_objects: Optional[int] = None, learn_objects: bool = False,
+                 object_lr: float = 0.05):
         self.device = device
         # The object layer (gaussian_model.py:47,55,66,108-110): a row of ``nr_objects`` object scores per Gaussian, one-hot
         # from the segment id of the pixel it was back-projected from (:373-382), carried through every piece of map surgery,
-        # NOT in the optimiser and without grad, as the reference has it.  None: no such layer, nothing below touches it.
+        # NOT in the optimiser and without grad, as the reference has it (unless ``learn_objects``, below).  None: no such layer,
+        # nothing below touches it.
         if nr_objects is not None and not 1 <= int(nr_objects) <= 256:
             raise ValueError("nr_objects must be 1..256 (segmentation ids are 8-bit)")
         self.nr_objects = None if nr_objects is None else int(nr_objects)
         self._obj_prob = None if nr_objects is None else torch.empty(0, self.nr_objects, device=device)
+        # ``learn_objects``: the rows are logits that ``object_layer.ObjectLayerTrainer`` learns from the keyframes' segmentation
+        # (the reference's TODO at gaussian_model.py:381).  They get an optimiser of their OWN -- ``params()`` and ``optimizer``
+        # stay the five groups the mapper steps -- whose moments every piece of map surgery carries as ``GaussianAdam.extend`` /
+        # ``prune`` carry the others.  ``object_lr``: the reference has no value (its rows are not learned); 0.05 is this
+        # project's rate for the other logit-like parameter, the raw opacity -- a choice, not a measurement.
+        if learn_objects and nr_objects is None:
+            raise ValueError("learn_objects needs nr_objects")
+        self.learn_objects, self.object_lr = False, float(object_lr)
+        self.object_optimizer = None
+        if learn_objects:
+            self.enable_object_learning()
         self.capturable = capturable        # torch.optim.Adam(capturable=True): step counters on the device (hipGraph)
         self.fused_adam = fused_adam        # monogs_amd.gaussian_optim.GaussianAdam (one launch, always capturable)
         self.lrs = [float(x) for x in lrs]
@@ -113,7 +132,7 @@ class GaussianMap:
         if self._obj_prob is not None:       # (checked before anything grows: the rows and the map stay the same length)
             if new_obj_prob is None or tuple(new_obj_prob.shape) != (n_new, self.nr_objects):
                 raise ValueError(f"a map with an object layer grows by new_obj_prob [{n_new}, {self.nr_objects}]")
-            self._obj_prob = torch.cat((self._obj_prob, new_obj_prob.detach().to(self._obj_prob)), 0)
+            self._extend_obj_rows(new_obj_prob.detach().to(self._obj_prob))
         if self.optimizer is None:
             self._set_params([torch.cat([o.detach(), n.detach()], 0).requires_grad_(True)
                               for o, n in zip(self.params(), new)])
@@ -128,6 +147,25 @@ class GaussianMap:
                                                else torch.zeros(n_new, **i32)).to(**i32)))
         self.nr_obs = torch.cat((self.nr_obs, (new_nr_obs if new_nr_obs is not None
                                                else torch.zeros(n_new, **i32)).to(**i32)))
+
+    def enable_object_learning(self, object_lr: Optional[float] = None):
+        """Turn the rows of a map built (or loaded) without ``learn_objects`` into learned ones, as they are: they become a leaf
+        with grad and get ``object_optimizer`` with zero moments.  No effect on a map that learns them already."""
+        if self._obj_prob is None:
+            raise ValueError("learn_objects needs nr_objects")
+        if object_lr is not None:
+            self.object_lr = float(object_lr)
+        if self.object_optimizer is None:
+            self._obj_prob = self._obj_prob.detach().requires_grad_(True)
+            self.object_optimizer = GaussianAdam([self._obj_prob], [self.object_lr], eps=1e-15)
+        self.learn_objects = True
+
+    def _extend_obj_rows(self, new_rows):
+        """Append object rows; a learned layer's moments grow by zeros, its step count stays (``GaussianAdam.extend``)."""
+        if self.object_optimizer is None:
+            self._obj_prob = torch.cat((self._obj_prob, new_rows), 0)
+        else:
+            (self._obj_prob,) = self.object_optimizer.extend([new_rows])
 
     def _make_optimizer(self):
         if self.fused_adam:
@@ -162,12 +200,14 @@ class GaussianMap:
         self.max_radii_2d = self.max_radii_2d[keep]
         self.kf_idx = self.kf_idx[keep]
         self.nr_obs = self.nr_obs[keep]
-        if self._obj_prob is not None:
+        if self.object_optimizer is not None:
+            (self._obj_prob,) = self.object_optimizer.prune(keep)
+        elif self._obj_prob is not None:
             self._obj_prob = self._obj_prob[keep]
 
     def _obj_rows(self, sel, N: int = 1):
         """The object rows of the selected Gaussians, repeated as clone (N = 1) / split (``.repeat(N, 1)``) repeat them."""
-        return None if self._obj_prob is None else self._obj_prob[sel].repeat(N, 1)
+        return None if self._obj_prob is None else self._obj_prob.detach()[sel].repeat(N, 1)
 
     # ---- densify (gaussian_model.py:778-886) -------------------------------------------------------------------
     @torch.no_grad()
@@ -287,7 +327,7 @@ class GaussianMap:
             self.kf_idx = torch.cat((self.kf_idx, kf))
             self.nr_obs = torch.cat((self.nr_obs, torch.zeros_like(kf)))
             if obj is not None:
-                self._obj_prob = torch.cat((self._obj_prob, obj), 0)
+                self._extend_obj_rows(obj)
         return n_new
 
 

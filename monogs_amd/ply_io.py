@@ -11,32 +11,38 @@ Parity unpinned: the reference holds no PLY fixture.
 from __future__ import annotations
 
 import os
-from typing import Dict, List
+from typing import Dict, List, Optional
 
 import numpy as np
 import torch
 
 
-def attribute_names(n_dc: int, n_scale: int, n_rot: int = 4) -> List[str]:
+def attribute_names(n_dc: int, n_scale: int, n_rot: int = 4, n_obj: int = 0) -> List[str]:
     names = ["x", "y", "z", "nx", "ny", "nz"]
     names += [f"f_dc_{i}" for i in range(n_dc)]
     names += ["opacity"]
     names += [f"scale_{i}" for i in range(n_scale)]
     names += [f"rot_{i}" for i in range(n_rot)]
+    names += [f"obj_prob_{i}" for i in range(n_obj)]
     return names
 
 
 def save_ply(path: str, xyz: torch.Tensor, f_dc: torch.Tensor, opacity: torch.Tensor, scaling: torch.Tensor,
-             rotation: torch.Tensor) -> None:
-    """xyz [P,3], f_dc [P,3] (or [P,C,1]/[P,1,C] as the reference stores it), opacity [P,1], scaling [P,1|3], rotation [P,4]."""
+             rotation: torch.Tensor, obj_prob: Optional[torch.Tensor] = None) -> None:
+    """xyz [P,3], f_dc [P,3] (or [P,C,1]/[P,1,C] as the reference stores it), opacity [P,1], scaling [P,1|3], rotation [P,4].
+    ``obj_prob`` [P,K]: the map's RAW object rows, written as ``obj_prob_0..K-1`` after ``rot_*`` (the reference's TODO at
+    gaussian_model.py:505; a reader that does not know them skips them by name); None: the file of a map without the layer."""
     def cpu(t):
         t = t.detach().to("cpu", torch.float32)
         return t.reshape(t.shape[0], int(np.prod(t.shape[1:]))).numpy()
 
     xyz_, dc, op, sc, rot = cpu(xyz), cpu(f_dc), cpu(opacity), cpu(scaling), cpu(rotation)
     P = xyz_.shape[0]
-    names = attribute_names(dc.shape[1], sc.shape[1], rot.shape[1])
-    table = np.concatenate([xyz_, np.zeros_like(xyz_), dc, op, sc, rot], axis=1).astype("<f4")
+    obj = [] if obj_prob is None else [cpu(obj_prob)]
+    if obj and obj[0].shape[0] != P:
+        raise ValueError(f"obj_prob has {obj[0].shape[0]} rows, the map {P}")
+    names = attribute_names(dc.shape[1], sc.shape[1], rot.shape[1], obj[0].shape[1] if obj else 0)
+    table = np.concatenate([xyz_, np.zeros_like(xyz_), dc, op, sc, rot] + obj, axis=1).astype("<f4")
     assert table.shape == (P, len(names))
     d = os.path.dirname(path)
     if d:
@@ -90,7 +96,8 @@ def read_vertex_table(path: str) -> Dict[str, np.ndarray]:
 
 
 def load_ply(path: str, device="cpu") -> Dict[str, torch.Tensor]:
-    """{'xyz' [P,3], 'f_dc' [P,C], 'opacity' [P,1], 'scaling' [P,S], 'rotation' [P,4]} as float32 tensors."""
+    """{'xyz' [P,3], 'f_dc' [P,C], 'opacity' [P,1], 'scaling' [P,S], 'rotation' [P,4]} as float32 tensors, and 'obj_prob'
+    [P,K] when (and only when) the file has ``obj_prob_*`` properties."""
     v = read_vertex_table(path)
 
     def stack(prefix):
@@ -99,4 +106,6 @@ def load_ply(path: str, device="cpu") -> Dict[str, torch.Tensor]:
 
     out = {"xyz": np.stack([v["x"], v["y"], v["z"]], axis=1).astype(np.float32), "f_dc": stack("f_dc_"),
            "opacity": v["opacity"].astype(np.float32)[:, None], "scaling": stack("scale_"), "rotation": stack("rot_")}
+    if any(k.startswith("obj_prob_") for k in v):
+        out["obj_prob"] = stack("obj_prob_")
     return {k: torch.from_numpy(a).to(device) for k, a in out.items()}

@@ -58,8 +58,12 @@ def _setup(c):
     ``reference_lrs`` / ``map_surgery``: the reference's learning rates / densify, prune and opacity-reset schedule.
     ``kf_selection="overlap"``: a ``KeyframeWindow``, ``check_viewpoints_overlap`` being the tracker's flag (False in the fork).
     ``sensor="monocular"``: the frames carry no depth (a synthetic or RGB-D sequence is stripped of it, a monocular ``sequence`` is
-    taken as it is); the tracker and the mapper then run the RGB-only losses and ``_map_keyframe`` back-projects depth hypotheses."""
+    taken as it is); the tracker and the mapper then run the RGB-only losses and ``_map_keyframe`` back-projects depth hypotheses.
+    ``learn_objects=N`` (needs ``nr_objects``): the map's object rows are learned, N iterations of ``ObjectLayerTrainer`` over the
+    window after every mapping call (``_learn_objects``)."""
     from .gaussian_map import REFERENCE_LRS, REFERENCE_LR_SCHEDULE
+    if c.learn_objects and c.nr_objects is None:
+        raise ValueError("learn_objects needs nr_objects")
     if c.sensor not in ("depth", "monocular"):
         raise ValueError('sensor must be "depth" or "monocular"')
     if c.kf_selection not in ("interval", "overlap"):
@@ -91,7 +95,8 @@ def _setup(c):
     else:
         c.extend_kw = lambda init: dict(downsample=c.init_downsample if init else c.kf_downsample, point_size=c.point_size)
     bg = torch.zeros(3, device=c.device)
-    gmap = GaussianMap(c.device, nr_objects=c.nr_objects, **(dict(lrs=REFERENCE_LRS) if c.reference_lrs else {}))
+    gmap = GaussianMap(c.device, nr_objects=c.nr_objects, **(dict(learn_objects=True) if c.learn_objects else {}),
+                       **(dict(lrs=REFERENCE_LRS) if c.reference_lrs else {}))
     if c.reference_lrs:
         gmap.lr_schedule = dict(REFERENCE_LR_SCHEDULE)
     gmap.surgery_log = []
@@ -111,7 +116,8 @@ def _setup(c):
         stats=dict(kf_extend_s=0.0, track_capture_s=0.0, track_s=0.0, track_iters=0, tracked=0, map_s=0.0, map_iters=0,
                    keyframes=0, renders=0),
         stats_kf=dict(keyframes_selected=0, evicted_by_cutoff=0, evicted_by_size=0),
-        viewer=None, viewer_files=[])                   # ``viewer_dir``: the HeadlessViewer of the run and the PNGs it wrote
+        viewer=None, viewer_files=[],                   # ``viewer_dir``: the HeadlessViewer of the run and the PNGs it wrote
+        obj_trainer=None, obj_loss=[])                  # ``learn_objects``: the trainer of the run, (first, last) loss per call
 
 
 def _map_window(s, iters, init=False):
@@ -244,6 +250,17 @@ def _map_keyframe(s, i, vp, pkg=None, t0=None):
     _drop_tracking_graph(s)                      # the map changed: the captured tracking graph is stale
 
 
+def _learn_objects(s):
+    """``learn_objects``: that many ``ObjectLayerTrainer`` steps over the window, after the mapping call that just ended and
+    outside every time bracket (the rates of ``_report`` stay those of tracking and mapping)."""
+    if not s.c.learn_objects:
+        return
+    if s.obj_trainer is None:
+        from .object_layer import ObjectLayerTrainer
+        s.obj_trainer = ObjectLayerTrainer(s.gmap, s.intr, s.bg)
+    s.obj_loss.append(s.obj_trainer.run(s.window, int(s.c.learn_objects)))
+
+
 def _viewer_frames(s, vp, tag):
     """``viewer_dir``: one PNG per mode of ``viewer_modes`` from a camera behind ``vp``'s pose (the reference's ``view_dir_behind``,
     what its viewer follows the tracker with), ``<tag>_<mode>.png``: the map as it is, the keyframes' frustums and trajectory, the
@@ -276,7 +293,8 @@ def _finish(s):
     """What follows the last frame; returns the result keys it adds.  ``eval_render``: ``eval`` (``evaluation.eval_rendering`` before
     and after the refinement) and ``ate`` over the keyframes, as the reference reports them.  ``refine_iters``: that many iterations
     of ``refinement.Refiner`` over all keyframes (``refinement``).  ``eager_probe``: that many iterations of
-    ``eager_probe.eager_tracking_probe`` against the final map (``eager_tracking``)."""
+    ``eager_probe.eager_tracking_probe`` against the final map (``eager_tracking``).  ``learn_objects``: ``objects`` = the trainer's
+    iteration count, its first and last loss and ``object_layer.eval_segmentation`` over the run's frames."""
     c, frames, gmap, intr, bg, mapper, kf_list = s.c, s.frames, s.gmap, s.intr, s.bg, s.mapper, s.kf_list
     _drop_tracking_graph(s)
     extra = {}
@@ -299,6 +317,12 @@ def _finish(s):
             extra["eval"]["final"] = (eval_rendering(frames, gmap, intr, bg, kf_list, tag="final") if c.refine_iters
                                       else extra["eval"]["before_opt"])
             extra["ate"] = eval_ate(frames, kf_ids=kf_list)
+    if c.learn_objects:
+        from .object_layer import eval_segmentation
+        extra["objects"] = dict(iters=s.obj_trainer.steps if s.obj_trainer is not None else 0,
+                                loss_first=s.obj_loss[0][0] if s.obj_loss else None,
+                                loss_last=s.obj_loss[-1][1] if s.obj_loss else None,
+                                **eval_segmentation(frames, gmap, intr, bg, kf_list))
     if c.eager_probe:
         # (the captured graphs of the run and their private pools go first: the probe measures an eager caller, not one that
         #  shares its process with a few dozen instantiated hipGraphs)
@@ -365,18 +389,22 @@ def run_slam(n_frames=12, intrinsics="fr3_office", tracking_itr_num=100, mapping
              track_lookahead=1, map_surgery=False, reference_lrs=False, prune_after_mapping=None,
              scene="cloud", reference_densify=False, eager_probe=0, exclusive_device=False,
              kf_selection="interval", check_viewpoints_overlap=False, kf_trace=None, refine_iters=0, eval_render=False,
-             sequence=None, nr_objects=None, sensor="depth", viewer_dir=None, viewer_modes=("rgb",), viewer_every=0):
+             sequence=None, nr_objects=None, sensor="depth", viewer_dir=None, viewer_modes=("rgb",), viewer_every=0,
+             learn_objects=0):
     """Tracks and maps a sequence in one process; returns tracking / mapping rates, iterations and the trajectory error (``_report``).
     Every argument is described where it acts: ``_setup``, ``_track_frame``, ``_select_keyframe``, ``_map_keyframe``, ``_map_window``,
     ``_finish`` (what follows the last frame).  ``log``: a callable that gets a line per frame.  ``sensor="monocular"`` adds the result
     keys ``sensor``, ``ate_sim3`` (Sim(3)-aligned ATE over all frames) and ``pseudo_depth_stats``; ``run_slam_two_process`` stays RGB-D.
     ``viewer_dir``: write headless-viewer frames there (``monogs_amd.viewer``), one per mode of ``viewer_modes``, after every
-    ``viewer_every``-th keyframe (0: never) and at the end; only then does the result hold a ``viewer`` entry."""
+    ``viewer_every``-th keyframe (0: never) and at the end; only then does the result hold a ``viewer`` entry.
+    ``learn_objects=N`` (with ``nr_objects``): learn the object rows, N trainer iterations over the window after each mapping call; only
+    then does the result hold an ``objects`` entry (iterations, first and last label loss, label accuracy and mIoU)."""
     s = _setup(SimpleNamespace(**locals()))              # (every argument, by name: must stay the first statement)
     for i, vp in enumerate(s.frames):
         if i == 0:
             vp.update_RT(vp.R_gt, vp.T_gt)
             _map_keyframe(s, 0, vp)
+            _learn_objects(s)
             if viewer_dir is not None and viewer_every > 0 and s.stats["keyframes"] % viewer_every == 0:
                 _viewer_frames(s, vp, f"kf{s.stats['keyframes']:04d}")
             continue
@@ -386,6 +414,7 @@ def run_slam(n_frames=12, intrinsics="fr3_office", tracking_itr_num=100, mapping
         pkg, t0 = _select_keyframe(s, i, vp)
         if pkg is not None:
             _map_keyframe(s, i, vp, pkg, t0)
+            _learn_objects(s)
             if viewer_dir is not None and viewer_every > 0 and s.stats["keyframes"] % viewer_every == 0:
                 _viewer_frames(s, vp, f"kf{s.stats['keyframes']:04d}")
         if log:

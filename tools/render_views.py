@@ -6,8 +6,9 @@ cameras with the headless viewer (monogs_amd.viewer): ``DIR/view_0000.png`` ...
         [--radius R] [--height-offset H] [--scale-modifier S]
 
 The orbit circles the map's median centre at ``--radius`` (default: twice the median distance of the Gaussians from it), the
-image's up direction being -y of the map's frame (the first camera's up in a SLAM map).  The ``segmentation`` mode needs the
-object layer, which a PLY does not hold."""
+image's up direction being -y of the map's frame (the first camera's up in a SLAM map).  The ``segmentation`` mode needs a PLY that
+carries the object rows (``save_ply(..., obj_prob=gmap._obj_prob)``): each Gaussian is painted with the palette colour of its
+most probable object, as the reference's viewer does."""
 import argparse
 import math
 import os
@@ -23,7 +24,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("ply")
     ap.add_argument("--orbit", type=int, default=8, metavar="N")
-    ap.add_argument("--mode", default="rgb", choices=["rgb", "depth", "time", "elipsoids"])
+    ap.add_argument("--mode", default="rgb", choices=["rgb", "segmentation", "depth", "time", "elipsoids"])
     ap.add_argument("--out", required=True, metavar="DIR")
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--height", type=int, default=480)
@@ -40,8 +41,11 @@ def main():
     dev = "cuda:0"
     m = load_ply(a.ply, device=dev)
     # the file holds raw parameters: the reference's activations (gaussian_model.py:84-106); colours are stored as they are used
+    if a.mode == "segmentation" and "obj_prob" not in m:
+        sys.exit(f"{a.ply} holds no obj_prob_* properties: the segmentation mode needs a map saved with its object rows")
+    obj_idx = m["obj_prob"].argmax(dim=1) if "obj_prob" in m else None        # (argmax of the raw row = argmax of its softmax)
     snap = V.Snapshot(m["xyz"], torch.nn.functional.normalize(m["rotation"]), torch.exp(m["scaling"]), torch.sigmoid(m["opacity"]),
-                      m["f_dc"][:, :3].contiguous(), None, (), None, None)
+                      m["f_dc"][:, :3].contiguous(), obj_idx, (), None, None)
     f = a.width / (2.0 * math.tan(math.radians(a.fov) / 2.0))
     intr = Intrinsics(dict(fx=f, fy=f, cx=a.width / 2.0, cy=a.height / 2.0, W=a.width, H=a.height), dev)
     centre = snap.means.median(0).values

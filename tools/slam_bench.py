@@ -69,6 +69,10 @@ if __name__ == "__main__":
                     help="write headless-viewer frames (monogs_amd.viewer) to DIR: after every --viewer-every-th keyframe and at the end")
     ap.add_argument("--viewer-modes", nargs="+", default=["rgb"], choices=["rgb", "segmentation", "depth", "time", "elipsoids"])
     ap.add_argument("--viewer-every", type=int, default=0, help="with --viewer: a frame set after every N-th keyframe (0: only at the end)")
+    ap.add_argument("--learn-objects", type=int, default=0, metavar="N",
+                    help="with --room: an object row per Gaussian (one score per room surface), learned from the frames' surface ids, "
+                         "N trainer iterations over the window after each mapping call (monogs_amd.object_layer); the result gains "
+                         "`objects`: label loss, pixel accuracy and mIoU on every fifth non-keyframe")
     a = ap.parse_args()
     from monogs_amd.slam_harness import run_slam
     cfg = dict(CONFIGS[a.config])
@@ -91,17 +95,23 @@ if __name__ == "__main__":
         mono = dict(monocular=True, config=config) if sensor == "monocular" else {}
         sequence = dataset_frames(load_dataset(config, device="cuda:0"), a.frames, device="cuda:0", stride=a.stride, **mono)
         cfg.pop("intrinsics")                           # (the YAML's calibration is the camera)
+    objects = {}
+    if a.learn_objects:
+        if not a.room or a.dataset:
+            ap.error("--learn-objects needs the segmentation of the --room sequence")
+        from monogs_amd.sequences import ROOM_SURFACES
+        objects = dict(nr_objects=ROOM_SURFACES, learn_objects=a.learn_objects)
     out = run_slam(sequence=sequence, n_frames=a.frames, init_itr_num=init_iters, n_gaussians=a.gaussians, graph_tracking=a.graph,
                    graph_mapping=a.graph and not a.eager_mapping, track_lookahead=a.lookahead, map_surgery=a.surgery,
                    reference_lrs=a.reference_lrs, scene="room" if a.room else "cloud", reference_densify=a.reference_densify,
                    eager_probe=a.eager_probe, kf_selection=a.kf_selection, check_viewpoints_overlap=a.check_overlap,
                    refine_iters=a.refine, eval_render=a.eval, sensor=sensor, viewer_dir=a.viewer,
-                   viewer_modes=tuple(a.viewer_modes), viewer_every=a.viewer_every, log=lambda s: print("[slam]", s, file=sys.stderr, flush=True), **cfg)
+                   viewer_modes=tuple(a.viewer_modes), viewer_every=a.viewer_every, log=lambda s: print("[slam]", s, file=sys.stderr, flush=True), **objects, **cfg)
     what = f"{a.dataset}, every {a.stride}. frame" if a.dataset else f"synthetic {a.config}-like sequence"
     out["workload"] = f"{what}, {a.frames} frames" + (" (fork's hard-coded run configuration)" if a.fork else "")
     if sensor == "monocular":
         print(f"[slam] monocular: ATE rmse {out['ate_rmse_m']:.4f} m raw, {out['ate_sim3']['rmse']:.4f} m after Sim(3) alignment "
               f"({out['ate_sim3']['n']} frames)", file=sys.stderr, flush=True)
-    for k in ("poses", "camera_centers", "camera_centers_gt"):      # tensors: not JSON
+    for k in ("poses", "camera_centers", "camera_centers_gt", "map", "frame_list", "intr"):      # tensors and objects: not JSON
         out.pop(k, None)
     print(json.dumps(out))
