@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define MGS_ABI_VERSION 21
+#define MGS_ABI_VERSION 22
 #define MGS_TILE 16 /* tile edge in pixels; ranges are per 16x16 tile */
 
 /* GaussianRasterizationSettings, minus `prefiltered` / `debug` which are call flags
@@ -111,6 +111,17 @@ size_t mgs_binning_bytes(uint64_t num_rendered, int32_t width, int32_t height);
 size_t mgs_backward_bytes(int32_t P);
 /* The six floats inside a backward scratch that a PREPARED backward (below) accumulates dL/dtau into. */
 float* mgs_backward_tau(void* backward_scratch, int32_t P);
+/* TEST USE ONLY, pure: byte offset (from the 256-byte-aligned base the carving uses) and length of a named
+ * sub-buffer; non-zero with mgs_last_error() set for an unknown name.  This export is the statement of the scratch layout:
+ * tests and tools ask here and compute no offset of their own.
+ * Names: a caller may rely on "<scratch>.<member>" with <scratch> one of geometry (sized by P), image (W, H), binning
+ * (R, W, H), backward (P) and <member> as csrc/common.h spells it (geometry.rec, image.ranges, binning.fwd_masks,
+ * backward.grad_acc, ...), plus "binning.point_list": the Gaussian index per instance in blend order, i.e. whichever of
+ * vals_a / vals_b the tile sort's pass count leaves its result in.
+ * Alignment: the base is the scratch pointer rounded up to 256 bytes; every sub-buffer of the geometry, image and binning
+ * scratch starts at a multiple of 256 from it, every one of the backward scratch at a multiple of 64. */
+int mgs_debug_scratch_field(const char* field, int32_t P, uint64_t R, int32_t W, int32_t H,
+                            uint64_t* offset, uint64_t* bytes);
 
 /* Forward, stage 1: per-Gaussian projection (cull, covariance, radius, tile rectangle, colour), the depth
  * order of the Gaussians and the prefix sum of tiles touched in that order.  Writes radii[P] and the geometry scratch, then copies the total number
@@ -166,7 +177,7 @@ int mgs_forward_render(const mgs_camera* cam, int32_t P, uint64_t num_rendered,
  * an algorithm path or to time a kernel.  Defaults are restored by the values given with each. */
 /* TEST USE ONLY, process-global, not thread-safe: the bound of those waits, in polls (all later sorts); 0xFFFFFFFF restores the default. */
 int mgs_debug_set_radix_spin_limit(uint32_t limit);
-/* TEST USE ONLY, process-global, not thread-safe: knobs that force an algorithm path whatever the problem size (-1 restores the default):
+/* TEST USE ONLY, process-global, not thread-safe: knobs that force an algorithm path whatever the problem size (one table in csrc/api.hip; any negative value, -1 by convention, restores the default of EVERY knob):
  * "radix_scanned" (0 = one kernel per pass with a gather of the earlier tiles' counts, 1 = counted tiles: two kernels per
  * pass, no waiting between workgroups -- honoured from 64 k pairs), "radix_ballot_rank" (1 = rank with wave ballots instead of
  * returning LDS atomics: the reference the sort tests compare with), "scan_small" (0 = the two-launch scan at every size),
@@ -198,7 +209,7 @@ int mgs_debug_set_option(const char* name, int64_t value);
  * 1 = per tile: the instances emitted in Gaussian-index order with their depth bits packed into the tile sort's pairs,
  *     grouped by tile, and each tile's list sorted by (depth bits, index) in LDS -- taken where the depth sort would
  *     take the counted-tiles path (P > 512 k, or any P with "radix_scanned" = 1), the tile id has <= 16 bits and
- *     P <= 2^(37 - tile bits).  Both orders are identical; what the geometry scratch holds differs (monogs_amd/debug.py). */
+ *     P <= 2^(37 - tile bits).  Both orders are identical; what the geometry scratch holds differs (monogs_amd/debug.py, forward_tables). */
 int mgs_binning_path(int32_t P, int32_t W, int32_t H);
 
 /* Test entry: the library's stable radix sort of n (key, value) pairs on key bits [0, bits) -- what the forward runs on

@@ -11,7 +11,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MGS_LIB_PATH") or os.path.join(_HERE, "lib", "libmonogs_raster.so")   # (override: kernel experiments)
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 c_float_p = C.c_void_p   # device pointers travel as integers (tensor.data_ptr())
 
@@ -87,6 +87,8 @@ SIGNATURES = {
                      + [C.c_void_p] * 4 + [C.c_void_p] * 4 + [C.c_void_p] * 9
                      + [C.c_void_p, C.c_int32, C.POINTER(MgsTiming), C.c_void_p]),
     "mgs_backward_tau": (C.c_void_p, [C.c_void_p, C.c_int32]),
+    "mgs_debug_scratch_field": (C.c_int, [C.c_char_p, C.c_int32, C.c_uint64, C.c_int32, C.c_int32,
+                                          C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "mgs_debug_blend_stats": (C.c_int, [C.POINTER(MgsCamera), C.c_int32, C.c_uint64] + [C.c_void_p] * 5),
     "mgs_debug_blend_mask_stats": (C.c_int, [C.POINTER(MgsCamera), C.c_int32, C.c_uint64] + [C.c_void_p] * 5),
     "mgs_features_forward": (C.c_int, [C.POINTER(MgsCamera), C.c_int32, C.c_int32, C.c_uint64] + [C.c_void_p] * 7

@@ -1,6 +1,7 @@
 // extern "C" entry points of libmonogs_raster.so (see include/monogs_raster.h).
 #include "common.h"
 
+#include <limits.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -16,78 +17,104 @@ void set_error(const char* fmt, ...) {
     va_end(ap);
 }
 
-// ---- scratch carving -------------------------------------------------------------------------
-static inline char* take(char*& p, size_t bytes) {
-    char* r = p;
-    p += align_up(bytes, 256);
-    return r;
+// ---- scratch layouts ----------------------------------------------------------------------
+// ONE ordered description per scratch: *_layout(dimensions, f) calls f(name, member, bytes[, min_bytes]) for every
+// sub-buffer in the order it lies in memory.  A sub-buffer starts where the one before it ended, rounded up to the
+// scratch's ALIGN, and takes max(bytes, min_bytes).  carve(), bytes() and mgs_debug_scratch_field() all walk these, so a
+// sub-buffer is added, moved or resized here and nowhere else.
+template <class F> static void geometry_layout(int P, F& f) {
+    const size_t n = (size_t)P;
+    f("rec", &GeometryState::rec, n * REC_FLOATS * sizeof(float));
+    f("depth_key", &GeometryState::depth_key, n * sizeof(uint32_t));
+    f("depth_alt", &GeometryState::depth_alt, n * sizeof(uint32_t));
+    f("iota", &GeometryState::iota, n * sizeof(uint32_t));
+    f("iota_alt", &GeometryState::iota_alt, n * sizeof(uint32_t));
+    f("perm", &GeometryState::perm, n * sizeof(uint32_t));
+    f("point_offsets", &GeometryState::point_offsets, n * sizeof(uint32_t));
+    f("scan_blocks", &GeometryState::scan_blocks, ((size_t)scan_nblocks(P, SCAN_ITEMS_PRE) + 64) * sizeof(uint32_t));
+    f("clamped", &GeometryState::clamped, n * 4);
+    f("rect", &GeometryState::rect, n * sizeof(uint2));
+    f("rect_sorted", &GeometryState::rect_sorted, n * sizeof(uint2));
+    f("scan_status", &GeometryState::scan_status, (SCAN_SMALL_MAX_BLOCKS + 1) * sizeof(uint64_t));
+    f("tile_hist", &GeometryState::tile_hist, 4 * 256 * sizeof(uint32_t));
+    f("sort_temp", &GeometryState::sort_temp, radix_depth_temp_bytes((uint64_t)P));      // directly behind tile_hist
+    f("prepare", &GeometryState::prepare, 2 * sizeof(unsigned long long));
 }
-
-GeometryState GeometryState::carve(void* base, int P) {
-    char* p = (char*)align_up((size_t)base, 256);
-    GeometryState g;
-    g.rec = (float*)take(p, (size_t)P * REC_FLOATS * sizeof(float));
-    g.depth_key = (uint32_t*)take(p, (size_t)P * sizeof(uint32_t));
-    g.depth_alt = (uint32_t*)take(p, (size_t)P * sizeof(uint32_t));
-    g.iota = (uint32_t*)take(p, (size_t)P * sizeof(uint32_t));
-    g.iota_alt = (uint32_t*)take(p, (size_t)P * sizeof(uint32_t));
-    g.perm = (uint32_t*)take(p, (size_t)P * sizeof(uint32_t));
-    g.point_offsets = (uint32_t*)take(p, (size_t)P * sizeof(uint32_t));
-    g.scan_blocks = (uint32_t*)take(p, ((size_t)scan_nblocks(P, SCAN_ITEMS_PRE) + 64) * sizeof(uint32_t));
-    g.clamped = (uint8_t*)take(p, (size_t)P * 4);
-    g.rect = (uint2*)take(p, (size_t)P * sizeof(uint2));
-    g.rect_sorted = (uint2*)take(p, (size_t)P * sizeof(uint2));
-    g.scan_status = (uint64_t*)take(p, (SCAN_SMALL_MAX_BLOCKS + 1) * sizeof(uint64_t));
-    g.tile_hist = (uint32_t*)take(p, 4 * 256 * sizeof(uint32_t));
-    g.sort_temp_bytes = radix_depth_temp_bytes((uint64_t)P);
-    g.sort_temp = take(p, g.sort_temp_bytes);           // 256-aligned, directly behind tile_hist
-    g.prepare = (unsigned long long*)take(p, 2 * sizeof(unsigned long long));
-    g.end = p;
-    return g;
-}
-size_t GeometryState::bytes(int P) {
-    const GeometryState g = carve(nullptr, P);
-    return (size_t)g.end + 256;
-}
-
-size_t ImageState::bytes(int W, int H) {
+template <class F> static void image_layout(int W, int H, F& f) {
     const size_t HW = (size_t)W * H, nt = (size_t)tiles_x(W) * tiles_y(H);
-    return align_up(HW * 4, 256) * 2 + align_up(nt * sizeof(uint2), 256) + 256;
+    f("final_T", &ImageState::final_T, HW * 4);
+    f("n_contrib", &ImageState::n_contrib, HW * 4);
+    f("ranges", &ImageState::ranges, nt * sizeof(uint2));
 }
-ImageState ImageState::carve(void* base, int W, int H) {
-    const size_t HW = (size_t)W * H, nt = (size_t)tiles_x(W) * tiles_y(H);
-    char* p = (char*)align_up((size_t)base, 256);
-    ImageState s;
-    s.final_T = (float*)take(p, HW * 4);
-    s.n_contrib = (uint32_t*)take(p, HW * 4);
-    s.ranges = (uint2*)take(p, nt * sizeof(uint2));
-    return s;
-}
-
 size_t BinningState::fwd_mask_rows(uint64_t R, int W, int H) {
     return (size_t)(R / 64) + (size_t)tiles_x(W) * tiles_y(H) + 1;
 }
-size_t BinningState::bytes(uint64_t R, int W, int H) {
-    const size_t r = (size_t)(R ? R : 1);
-    return align_up(r * 4, 256) * 4 + align_up(mgs::sort_temp_bytes(R, tile_bits(W, H)), 256) + 256 +
-           align_up(fwd_mask_rows(R, W, H) * 4 * sizeof(unsigned long long), 256) + 256;
+template <class F> static void binning_layout(uint64_t R, int W, int H, F& f) {
+    const size_t r = (size_t)R * 4;                     // (R = 0 still reserves an element per buffer)
+    f("keys_a", &BinningState::keys_a, r, 4);
+    f("keys_b", &BinningState::keys_b, r, 4);
+    f("vals_a", &BinningState::vals_a, r, 4);
+    f("vals_b", &BinningState::vals_b, r, 4);
+    f("sort_temp", &BinningState::sort_temp, mgs::sort_temp_bytes(R, tile_bits(W, H)));
+    f("count", &BinningState::count, 2 * sizeof(uint32_t));
+    f("fwd_masks", &BinningState::fwd_masks, BinningState::fwd_mask_rows(R, W, H) * 4 * sizeof(unsigned long long));   // behind everything older
 }
+template <class F> static void backward_layout(int P, F& f) {
+    f("grad_acc", &BackwardState::grad_acc, (size_t)P * GRAD_FLOATS * sizeof(float));
+    f("tau_part", &BackwardState::tau_part, (size_t)TAU_SLOTS * 16 * sizeof(float));     // right behind the accumulator
+    f("tau", &BackwardState::tau, 16 * sizeof(float));
+}
+
+// hands out the pointers of a scratch whose (256-byte-aligned) base is `base`; walked from NULL it measures the scratch
+template <class S> struct Carver {
+    S s{};
+    char* p;
+    explicit Carver(const void* base) : p((char*)align_up((size_t)base, 256)) {}
+    template <class T> void operator()(const char*, T* S::*member, size_t bytes, size_t min_bytes = 0) {
+        s.*member = (T*)p;
+        p += align_up(bytes > min_bytes ? bytes : min_bytes, S::ALIGN);
+    }
+    size_t bytes() const { return (size_t)p + 256; }    // (+ 256: the caller's base need not be aligned)
+};
+// finds one sub-buffer by name: its offset from the aligned base and its length
+struct FieldFinder {
+    const char* want;
+    size_t p = 0, offset = 0, bytes = 0;
+    bool found = false;
+    template <class T, class S> void operator()(const char* name, T* S::*, size_t n, size_t min_bytes = 0) {
+        if (!strcmp(name, want)) { found = true; offset = p; bytes = n; }
+        p += align_up(n > min_bytes ? n : min_bytes, S::ALIGN);
+    }
+};
+
+GeometryState GeometryState::carve(void* base, int P) {
+    Carver<GeometryState> c(base);
+    geometry_layout(P, c);
+    c.s.sort_temp_bytes = radix_depth_temp_bytes((uint64_t)P);
+    c.s.end = c.p;
+    return c.s;
+}
+ImageState ImageState::carve(void* base, int W, int H) { Carver<ImageState> c(base); image_layout(W, H, c); return c.s; }
 BinningState BinningState::carve(void* base, uint64_t R, int W, int H) {
-    const size_t r = (size_t)(R ? R : 1);
-    char* p = (char*)align_up((size_t)base, 256);
-    BinningState b;
-    b.keys_a = (uint32_t*)take(p, r * 4);
-    b.keys_b = (uint32_t*)take(p, r * 4);
-    b.vals_a = (uint32_t*)take(p, r * 4);
-    b.vals_b = (uint32_t*)take(p, r * 4);
+    Carver<BinningState> c(base);
+    binning_layout(R, W, H, c);
     const bool in_b = radix_result_in_b(tile_bits(W, H));
-    b.keys_sorted = in_b ? b.keys_b : b.keys_a;
-    b.vals_sorted = in_b ? b.vals_b : b.vals_a;
-    b.sort_temp_bytes = mgs::sort_temp_bytes(R, tile_bits(W, H));
-    b.sort_temp = take(p, b.sort_temp_bytes);
-    b.count = (uint32_t*)take(p, 2 * sizeof(uint32_t));
-    b.fwd_masks = (unsigned long long*)take(p, fwd_mask_rows(R, W, H) * 4 * sizeof(unsigned long long));   // behind everything older
-    return b;
+    c.s.keys_sorted = in_b ? c.s.keys_b : c.s.keys_a;
+    c.s.vals_sorted = in_b ? c.s.vals_b : c.s.vals_a;
+    c.s.sort_temp_bytes = mgs::sort_temp_bytes(R, tile_bits(W, H));
+    return c.s;
+}
+BackwardState BackwardState::carve(void* base, int P) { Carver<BackwardState> c(base); backward_layout(P, c); return c.s; }
+size_t GeometryState::bytes(int P) { Carver<GeometryState> c(nullptr); geometry_layout(P, c); return c.bytes(); }
+size_t ImageState::bytes(int W, int H) { Carver<ImageState> c(nullptr); image_layout(W, H, c); return c.bytes(); }
+size_t BinningState::bytes(uint64_t R, int W, int H) { Carver<BinningState> c(nullptr); binning_layout(R, W, H, c); return c.bytes(); }
+size_t BackwardState::bytes(int P) { Carver<BackwardState> c(nullptr); backward_layout(P, c); return c.bytes(); }
+
+// the three scratches of a finished (or running) forward, carved together
+struct ForwardStates { GeometryState g; ImageState img; BinningState b; };
+static ForwardStates carve_forward(const void* geometry, const void* binning, const void* image, int P, uint64_t R, int W, int H) {
+    return {GeometryState::carve(const_cast<void*>(geometry), P), ImageState::carve(const_cast<void*>(image), W, H),
+            BinningState::carve(const_cast<void*>(binning), R, W, H)};
 }
 
 // ---- per-stage timing with HIP events on the launch stream -------------------------------
@@ -150,10 +177,27 @@ const char* mgs_last_error(void) { return g_err; }
 size_t mgs_geometry_bytes(int32_t P) { return GeometryState::bytes(P < 0 ? 0 : P); }
 size_t mgs_image_bytes(int32_t W, int32_t H) { return ImageState::bytes(W, H); }
 size_t mgs_binning_bytes(uint64_t R, int32_t W, int32_t H) { return BinningState::bytes(R, W, H); }
-size_t mgs_backward_bytes(int32_t P) {
-    return (size_t)(P < 0 ? 0 : P) * GRAD_FLOATS * sizeof(float) + (size_t)(TAU_SLOTS + 1) * 16 * sizeof(float) + 256;
+size_t mgs_backward_bytes(int32_t P) { return BackwardState::bytes(P < 0 ? 0 : P); }
+float* mgs_backward_tau(void* backward_scratch, int32_t P) { return BackwardState::carve(backward_scratch, P < 0 ? 0 : P).tau; }
+
+int mgs_debug_scratch_field(const char* field, int32_t P, uint64_t R, int32_t W, int32_t H, uint64_t* offset, uint64_t* bytes) {
+    if (!field || !offset || !bytes) { set_error("mgs_debug_scratch_field: field, offset, bytes must be non-NULL"); return 1; }
+    if (P < 0) P = 0;
+    const char* name = field;
+    if (!strcmp(name, "binning.point_list")) name = radix_result_in_b(tile_bits(W, H)) ? "binning.vals_b" : "binning.vals_a";
+    const char* dot = strchr(name, '.');
+    const size_t n = dot ? (size_t)(dot - name) : 0;
+    FieldFinder f{dot ? dot + 1 : ""};
+    auto scratch = [&](const char* s) { return strlen(s) == n && !strncmp(name, s, n); };
+    if (scratch("geometry")) geometry_layout(P, f);
+    else if (scratch("image")) image_layout(W, H, f);
+    else if (scratch("binning")) binning_layout(R, W, H, f);
+    else if (scratch("backward")) backward_layout(P, f);
+    if (!f.found) { set_error("mgs_debug_scratch_field: unknown field \"%s\"", field); return 1; }
+    *offset = f.offset;
+    *bytes = f.bytes;
+    return 0;
 }
-float* mgs_backward_tau(void* backward_scratch, int32_t P) { return backward_tau_out(backward_scratch, P < 0 ? 0 : P); }
 
 int mgs_forward_preprocess(const mgs_camera* cam, int32_t P, const float* means3D, const float* shs,
                            const float* colors_precomp, const float* opacities, const float* scales,
@@ -192,7 +236,7 @@ int mgs_forward_preprocess(const mgs_camera* cam, int32_t P, const float* means3
     tm.mark();
     if (int rc = launch_preprocess_forward(*cam, P, means3D, shs, colors_precomp, opacities, scales, rotations,
                                            cov3D_precomp, g, radii,
-                                           prepare_backward ? backward_grad_acc(prepare_backward) : nullptr, s)) return rc;
+                                           prepare_backward ? BackwardState::carve(prepare_backward, P).grad_acc : nullptr, s)) return rc;
     tm.mark();
     const bool exclusive = (cam->flags & MGS_FLAG_EXCLUSIVE_DEVICE) != 0;
     const bool per_tile = binning_path(P, cam->image_width, cam->image_height) != 0;
@@ -245,9 +289,7 @@ static int forward_render_impl(const mgs_camera* cam, int32_t P, uint64_t R, boo
     if (P == 0) R = 0;
     hipStream_t s = (hipStream_t)stream;
     const int W = cam->image_width, H = cam->image_height;
-    GeometryState g = GeometryState::carve(geometry, P);
-    ImageState img = ImageState::carve(image, W, H);
-    BinningState b = BinningState::carve(binning, R, W, H);
+    auto [g, img, b] = carve_forward(geometry, binning, image, P, R, W, H);
     const uint32_t* n_dev = nullptr;
     StageTimer tm(s, timing != nullptr);
     const bool cap = capacity && binning;
@@ -333,16 +375,15 @@ int mgs_backward(const mgs_camera* cam, int32_t P, uint64_t R, const float* mean
     }
     if (R > 0 && !binning) { set_error("binning scratch is NULL"); return 1; }
     const int W = cam->image_width, H = cam->image_height;
-    GeometryState g = GeometryState::carve(const_cast<void*>(geometry), P);
-    ImageState img = ImageState::carve(const_cast<void*>(image), W, H);
-    BinningState b = BinningState::carve(const_cast<void*>(binning), R, W, H);
-    float* grad_acc = backward_grad_acc(backward_scratch);
+    auto [g, img, b] = carve_forward(geometry, binning, image, P, R, W, H);
+    const BackwardState bw = BackwardState::carve(backward_scratch, P);
+    float* grad_acc = bw.grad_acc;
     StageTimer tm(s, timing != nullptr);
     // (the pose-gradient slots sit right behind the accumulator: one clear covers both)
-    float* tau_part = (dL_dtau && (P + 255) / 256 > TAU_DIRECT_MAX_BLOCKS) ? backward_tau_part(backward_scratch, P) : nullptr;
+    float* tau_part = (dL_dtau && (P + 255) / 256 > TAU_DIRECT_MAX_BLOCKS) ? bw.tau_part : nullptr;
     if (scratch_prepared) {
         // the matching forward cleared the lines of the visible Gaussians, the slots and the six floats of dL/dtau
-        if (dL_dtau && dL_dtau != backward_tau_out(backward_scratch, P)) {
+        if (dL_dtau && dL_dtau != bw.tau) {
             set_error("scratch_prepared: dL_dtau must be mgs_backward_tau(backward_scratch, P)");
             return 1;
         }
@@ -392,9 +433,7 @@ int mgs_features_forward(const mgs_camera* cam, int32_t P, int32_t K, uint64_t n
     if (P > 0 && (!geometry || !image || !features)) { set_error("geometry, image, features must be non-NULL"); return 1; }
     if (P > 0 && num_rendered > 0 && !binning) { set_error("binning scratch is NULL"); return 1; }
     const int W = cam->image_width, H = cam->image_height;
-    GeometryState g = GeometryState::carve(const_cast<void*>(geometry), P);
-    ImageState img = ImageState::carve(const_cast<void*>(image), W, H);
-    BinningState b = BinningState::carve(const_cast<void*>(binning), num_rendered, W, H);
+    auto [g, img, b] = carve_forward(geometry, binning, image, P, num_rendered, W, H);
     return launch_features_forward(*cam, P, K, g, b, img, features, bg, out, labels, min_opacity, (hipStream_t)stream);
 }
 
@@ -405,9 +444,7 @@ int mgs_features_backward(const mgs_camera* cam, int32_t P, int32_t K, uint64_t 
     if (!geometry || !image || !dL_dout || !dL_dfeatures) { set_error("geometry, image, dL_dout, dL_dfeatures must be non-NULL"); return 1; }
     if (num_rendered > 0 && !binning) { set_error("binning scratch is NULL"); return 1; }
     const int W = cam->image_width, H = cam->image_height;
-    GeometryState g = GeometryState::carve(const_cast<void*>(geometry), P);
-    ImageState img = ImageState::carve(const_cast<void*>(image), W, H);
-    BinningState b = BinningState::carve(const_cast<void*>(binning), num_rendered, W, H);
+    auto [g, img, b] = carve_forward(geometry, binning, image, P, num_rendered, W, H);
     return launch_features_backward(*cam, P, K, g, b, img, dL_dout, dL_dfeatures, (hipStream_t)stream);
 }
 
@@ -423,9 +460,7 @@ int mgs_viewer_ellipsoids(const mgs_camera* cam, int32_t P, uint64_t num_rendere
     if (P > 0 && (!geometry || !image)) { set_error("geometry, image must be non-NULL"); return 1; }
     if (P > 0 && num_rendered > 0 && !binning) { set_error("binning scratch is NULL"); return 1; }
     const int W = cam->image_width, H = cam->image_height;
-    GeometryState g = GeometryState::carve(const_cast<void*>(geometry), P);
-    ImageState img = ImageState::carve(const_cast<void*>(image), W, H);
-    BinningState b = BinningState::carve(const_cast<void*>(binning), num_rendered, W, H);
+    auto [g, img, b] = carve_forward(geometry, binning, image, P, num_rendered, W, H);
     return launch_viewer_ellipsoids(*cam, P, g, b, img, threshold, out, hit, (hipStream_t)stream);
 }
 
@@ -458,9 +493,7 @@ int mgs_debug_blend_stats(const mgs_camera* cam, int32_t P, uint64_t R, const vo
     MGS_HIP(zero_fill(stats_dev, MGS_BLEND_STATS_WORDS * sizeof(uint64_t), s));
     if (P == 0 || R == 0) return 0;
     const int W = cam->image_width, H = cam->image_height;
-    GeometryState g = GeometryState::carve(const_cast<void*>(geometry), P);
-    ImageState img = ImageState::carve(const_cast<void*>(image), W, H);
-    BinningState b = BinningState::carve(const_cast<void*>(binning), R, W, H);
+    auto [g, img, b] = carve_forward(geometry, binning, image, P, R, W, H);
     return launch_blend_backward_stats(*cam, g, b, img, (unsigned long long*)stats_dev, s);
 }
 
@@ -472,9 +505,7 @@ int mgs_debug_blend_mask_stats(const mgs_camera* cam, int32_t P, uint64_t R, con
     MGS_HIP(zero_fill(stats_dev, MGS_BLEND_MASK_STATS_WORDS * sizeof(uint64_t), s));
     if (P == 0 || R == 0) return 0;
     const int W = cam->image_width, H = cam->image_height;
-    GeometryState g = GeometryState::carve(const_cast<void*>(geometry), P);
-    ImageState img = ImageState::carve(const_cast<void*>(image), W, H);
-    BinningState b = BinningState::carve(const_cast<void*>(binning), R, W, H);
+    auto [g, img, b] = carve_forward(geometry, binning, image, P, R, W, H);
     return launch_blend_mask_stats(*cam, g, b, img, (unsigned long long*)stats_dev, s);
 }
 
@@ -523,23 +554,29 @@ int mgs_debug_sort_pairs(uint32_t* keys, uint32_t* vals, uint32_t* keys_alt, uin
 }
 
 int mgs_debug_set_option(const char* name, int64_t value) {
-    if (name && !strcmp(name, "radix_scanned")) { g_opt_radix_scanned = (int)value; return 0; }
-    if (name && !strcmp(name, "radix_ballot_rank")) { g_opt_radix_ballot_rank = (int)value; return 0; }
-    if (name && !strcmp(name, "radix_xcd_band")) { g_opt_radix_xcd_band = (int)value; return 0; }
-    if (name && !strcmp(name, "debug_sort_exclusive")) { g_opt_debug_sort_exclusive = (int)value; return 0; }
-    if (name && !strcmp(name, "dup_slot_major")) { g_opt_dup_slot_major = (int)value; return 0; }
-    if (name && !strcmp(name, "blend_bwd_transposed")) {       // (2 / 1 / 0 name one kernel each: 2 set by hand is the UNSPLIT s-kernel; -1: the default)
-        g_opt_blend_bwd_transposed = value < 0 ? 2 : (int)value;
-        g_opt_blend_bwd_transposed_set = value >= 0;
+    // name, variable, default, largest value (larger ones saturate).  Any negative value restores the default.
+    static const struct { const char* name; int* var; int def, max; } options[] = {
+        {"radix_scanned", &g_opt_radix_scanned, -1, INT_MAX},
+        {"radix_ballot_rank", &g_opt_radix_ballot_rank, 0, 1},
+        {"radix_xcd_band", &g_opt_radix_xcd_band, 1, 1},
+        {"debug_sort_exclusive", &g_opt_debug_sort_exclusive, 0, 1},
+        {"dup_slot_major", &g_opt_dup_slot_major, -1, 1},
+        {"blend_bwd_transposed", &g_opt_blend_bwd_transposed, 2, INT_MAX},     // (2 / 1 / 0 name one kernel each)
+        {"blend_bwd_split", &g_opt_blend_bwd_split, -1, INT_MAX},
+        {"blend_bwd_split_min", &g_opt_blend_bwd_split_min, 4, INT_MAX},       // (both clamped where they are used: blend.hip)
+        {"blend_bwd_split_frac", &g_opt_blend_bwd_split_frac, 32, INT_MAX},
+        {"scan_small", &g_opt_scan_small, -1, 1},
+        {"pre_scan", &g_opt_pre_scan, -1, 1},
+        {"tile_sort_fused", &g_opt_tile_sort_fused, 1, 1},
+        {"knn_grid_min", &g_opt_knn_grid_min, -1, INT_MAX},
+    };
+    for (const auto& o : options) {
+        if (!name || strcmp(name, o.name)) continue;
+        *o.var = value < 0 ? o.def : value > o.max ? o.max : (int)value;
+        // the one row with a side effect: 2 SET BY HAND is the unsplit s-kernel, the A/B partner of 1 and 0
+        if (o.var == &g_opt_blend_bwd_transposed) g_opt_blend_bwd_transposed_set = value >= 0;
         return 0;
     }
-    if (name && !strcmp(name, "blend_bwd_split")) { g_opt_blend_bwd_split = value < 0 ? -1 : (int)value; return 0; }
-    if (name && !strcmp(name, "blend_bwd_split_min")) { g_opt_blend_bwd_split_min = value < 0 ? 4 : (int)value; return 0; }
-    if (name && !strcmp(name, "blend_bwd_split_frac")) { g_opt_blend_bwd_split_frac = value < 0 ? 32 : (int)value; return 0; }
-    if (name && !strcmp(name, "scan_small")) { g_opt_scan_small = (int)value; return 0; }
-    if (name && !strcmp(name, "pre_scan")) { g_opt_pre_scan = (int)value; return 0; }
-    if (name && !strcmp(name, "tile_sort_fused")) { g_opt_tile_sort_fused = value < 0 ? 1 : (int)value; return 0; }
-    if (name && !strcmp(name, "knn_grid_min")) { g_opt_knn_grid_min = value > 0x7FFFFFFF ? 0x7FFFFFFF : (int)value; return 0; }
     set_error("mgs_debug_set_option: unknown option");
     return 1;
 }

@@ -122,7 +122,7 @@ static inline hipError_t zero_fill(void* ptr, size_t bytes, hipStream_t s) {
     return hipGetLastError();
 }
 
-// ---- scratch carving (every sub-buffer 256-byte aligned) ---------------------------------
+// ---- scratch carving (the layouts themselves: api.hip; every sub-buffer of the forward 256-byte aligned) ----
 struct GeometryState {
     float* rec;               // [P][16]
     uint32_t* depth_key;      // [P] float32 bits of the view-space depth (0xFFFFFFFF when culled); sort input
@@ -148,6 +148,7 @@ struct GeometryState {
                               //     [0] written by preprocess (mgs_forward_preprocess's prepare_backward), moved to [1] by
                               //     duplicate_kernel and read there by blend_forward_kernel -- one render call per hand-over
     char* end;                // one past the last carved byte
+    static constexpr size_t ALIGN = 256;
     static size_t bytes(int P);
     static GeometryState carve(void* base, int P);
 };
@@ -157,6 +158,7 @@ struct ImageState {
     float* final_T;      // [H*W]
     uint32_t* n_contrib; // [H*W]
     uint2* ranges;       // [tiles]
+    static constexpr size_t ALIGN = 256;
     static size_t bytes(int W, int H);
     static ImageState carve(void* base, int W, int H);
 };
@@ -175,6 +177,7 @@ struct BinningState {
                                //     quadrant): step b of a tile whose list starts at x has the row x / 64 + tile + b, which
                                //     no other tile's step has; written by blend_forward_kernel, walked by blend_backward_s_kernel
     static size_t fwd_mask_rows(uint64_t R, int W, int H);
+    static constexpr size_t ALIGN = 256;
     static size_t bytes(uint64_t R, int W, int H);
     static BinningState carve(void* base, uint64_t R, int W, int H);
 };
@@ -229,11 +232,16 @@ int launch_preprocess_forward(const mgs_camera& cam, int P, const float* means3D
                               const float* colors_precomp, const float* opacities, const float* scales,
                               const float* rotations, const float* cov3D_precomp,
                               const GeometryState& g, int32_t* radii, float* prepare_grad_acc, hipStream_t s);
-// backward scratch: [grad_acc P x 16][pose-gradient slots TAU_SLOTS x 16][dL/dtau of a prepared backward: 16]
+// backward scratch: the accumulator, then -- 64-byte lines like its own, so that one clear covers both -- the pose part
 constexpr int TAU_SLOTS = 256;              // one 64-byte line each
-inline float* backward_grad_acc(void* scratch) { return (float*)align_up((size_t)scratch, 256); }
-inline float* backward_tau_part(void* scratch, int P) { return backward_grad_acc(scratch) + (size_t)P * GRAD_FLOATS; }
-inline float* backward_tau_out(void* scratch, int P) { return backward_tau_part(scratch, P) + (size_t)TAU_SLOTS * 16; }
+struct BackwardState {
+    float* grad_acc;     // [P][16] gradient lines
+    float* tau_part;     // [TAU_SLOTS][16] pose-gradient slots
+    float* tau;          // [16] dL/dtau of a prepared backward (six floats used)
+    static constexpr size_t ALIGN = 64;
+    static size_t bytes(int P);
+    static BackwardState carve(void* base, int P);
+};
 // `prepare_grad_acc` (or NULL): the pose part behind the accumulator is cleared by the kernel itself; the accumulator's address is
 // left in g.prepare[0] for the render call that follows, whose blend forward clears the P gradient lines (blend.hip)
 // `rects`: the rectangles in the order the scan runs in (rect_sorted after a depth sort, rect by index on the per-tile path)

@@ -15,52 +15,18 @@ the colour and depth losses shape.
 from __future__ import annotations
 
 import ctypes as C
-from typing import NamedTuple, Optional
+from typing import Optional
 
 import torch
 
 from . import _lib
-from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, _device_guard, _ptr, _stream
+from .rasterizer import (ForwardScratch, GaussianRasterizationSettings, GaussianRasterizer, _device_guard, _ptr, _stream,
+                         forward_scratch)
 
 MAX_FEATURE_CHANNELS = 256          # MGS_MAX_FEATURE_CHANNELS
 
 
-class _Tables(NamedTuple):
-    """What the feature kernels read from a finished forward.  Strong references: they outlive the rasteriser's own backward,
-    which frees its saved tensors, for as long as the colour image (its ``grad_fn``) or a feature image rendered from it lives."""
-    cam: object                 # _lib.MgsCamera of the forward
-    keep: list                  # the tensors its pointers name
-    arena: torch.Tensor         # geometry + image scratch
-    binning: torch.Tensor
-    geom_off: int
-    img_off: int
-    num_rendered: int           # the capacity, after a capacity-mode forward
-    P: int
-    H: int
-    W: int
-    device: torch.device
-
-
-def _tables(color: torch.Tensor) -> _Tables:
-    fn = getattr(color, "grad_fn", None)
-    if fn is None or not hasattr(fn, "raster_settings"):
-        raise RuntimeError("render_features needs the colour image of a differentiable rasteriser forward")
-    t = getattr(fn, "_feature_tables", None)
-    if t is None:
-        try:
-            saved = fn.saved_tensors
-        except RuntimeError as e:
-            raise RuntimeError("render_features: the rasteriser's backward has already freed this forward's scratch; "
-                               "call render_features once before that backward to keep it") from e
-        means3D, arena, binning = saved[0], saved[8], saved[9]
-        rs = fn.raster_settings
-        t = _Tables(fn.cam, fn.keep, arena, binning, int(fn.geom_off), int(fn.img_off), int(fn.num_rendered),
-                    int(means3D.shape[0]), int(rs.image_height), int(rs.image_width), means3D.device)
-        fn._feature_tables = t
-    return t
-
-
-def _check(t: _Tables, features, bg) -> int:
+def _check(t: ForwardScratch, features, bg) -> int:
     """Shape, dtype and device errors, raised before the library is touched.  Returns K."""
     if not isinstance(features, torch.Tensor) or features.dim() != 2:
         raise ValueError("features must be a [P, K] tensor")
@@ -83,18 +49,16 @@ def _check(t: _Tables, features, bg) -> int:
 
 class _RenderFeatures(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, features, t: _Tables, bg, want_labels, min_opacity):
+    def forward(ctx, features, t: ForwardScratch, bg, want_labels, min_opacity):
         lib = _lib.load()
         f = features.detach().contiguous()
         K = int(f.shape[1])
         bg_ = None if bg is None else bg.detach().contiguous()
         out = torch.empty(K, t.H, t.W, dtype=torch.float32, device=t.device)
         labels = torch.empty(t.H, t.W, dtype=torch.int32, device=t.device) if want_labels else None
-        base = t.arena.data_ptr()
         with _device_guard(t.device):
-            _lib.check(lib.mgs_features_forward(C.byref(t.cam), t.P, K, t.num_rendered, base + t.geom_off,
-                                                t.binning.data_ptr(), base + t.img_off, f.data_ptr(), _ptr(bg_),
-                                                out.data_ptr(), _ptr(labels), float(min_opacity), _stream()),
+            _lib.check(lib.mgs_features_forward(C.byref(t.cam), t.P, K, t.num_rendered, *t.pointers(), f.data_ptr(),
+                                                _ptr(bg_), out.data_ptr(), _ptr(labels), float(min_opacity), _stream()),
                        "mgs_features_forward")
         ctx.tables, ctx.K = t, K
         if labels is None:
@@ -107,17 +71,15 @@ class _RenderFeatures(torch.autograd.Function):
         return features_backward(ctx.tables, grad_out, ctx.K), None, None, None, None
 
 
-def features_backward(t: _Tables, d_out: torch.Tensor, K: int) -> torch.Tensor:
-    """``mgs_features_backward`` on the tables ``t`` (``_tables(color)``): ``d_features [P, K]`` from ``d_out [K, H, W]``.  What the
+def features_backward(t: ForwardScratch, d_out: torch.Tensor, K: int) -> torch.Tensor:
+    """``mgs_features_backward`` on the handle ``t`` (``forward_scratch(color)``): ``d_features [P, K]`` from ``d_out [K, H, W]``.  What the
     autograd node's backward runs; a loop that steps the rows itself (``object_layer.ObjectLayerTrainer``) calls it directly."""
     lib = _lib.load()
     g = d_out.to(torch.float32).contiguous()
     d_feat = torch.empty(t.P, K, dtype=torch.float32, device=t.device)
-    base = t.arena.data_ptr()
     with _device_guard(t.device):
-        _lib.check(lib.mgs_features_backward(C.byref(t.cam), t.P, K, t.num_rendered, base + t.geom_off,
-                                             t.binning.data_ptr(), base + t.img_off, g.data_ptr(), d_feat.data_ptr(),
-                                             _stream()), "mgs_features_backward")
+        _lib.check(lib.mgs_features_backward(C.byref(t.cam), t.P, K, t.num_rendered, *t.pointers(), g.data_ptr(),
+                                             d_feat.data_ptr(), _stream()), "mgs_features_backward")
     return d_feat
 
 
@@ -130,7 +92,7 @@ def render_features(color: torch.Tensor, features: torch.Tensor, bg: Optional[to
     ``color`` is the colour image of a differentiable ``GaussianRasterizer`` forward: its scratch is found through
     ``color.grad_fn`` and referenced from here on, so this may be called again, and ``features.grad`` obtained, after the
     rasteriser's own backward has run; that backward is not disturbed.  Differentiable in ``features`` only."""
-    t = _tables(color)
+    t = forward_scratch(color, "render_features")
     _check(t, features, bg)
     return _RenderFeatures.apply(features, t, bg, bool(want_labels), float(min_opacity))
 

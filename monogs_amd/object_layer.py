@@ -209,13 +209,13 @@ def _frozen_geometry(gmap):
 def _forward_tables(vp, intr, geometry, bg):
     """One rasteriser forward with detached geometry and a dummy colour (what ``FeatureRasterizer`` does) through ``render()``,
     so that the camera tensors are the cached ones; returns the tables the feature kernels read."""
-    from .feature_render import _tables
+    from .rasterizer import forward_scratch
     from .renderer import render
     xyz, rot, scales3, opac = geometry
     # (requires_grad: the forward keeps its tables for a backward only then)
     dummy = torch.zeros(xyz.shape[0], 3, dtype=torch.float32, device=xyz.device, requires_grad=True)
     pkg = render(vp, intr, xyz, rot, scales3, opac, dummy, bg)
-    return _tables(pkg["render"]), pkg
+    return forward_scratch(pkg["render"], "render_features"), pkg
 
 
 def _target_of(vp) -> LabelTarget:

@@ -403,22 +403,61 @@ class _RasterizeGaussians(torch.autograd.Function):
         return (d_means3D, d_means2D, d_sh, d_col, d_opac, d_scales, d_rot, d_cov, d_theta, d_rho, None)
 
 
+class ForwardScratch(NamedTuple):
+    """What a finished forward left behind for whoever reads its lists afterwards (the feature kernels, the viewer's ellipsoid
+    walk, the blend statistics).  Strong references: they outlive the rasteriser's own backward, which frees its saved tensors,
+    for as long as the colour image (its ``grad_fn``) or anything rendered from the handle lives."""
+    cam: object                 # _lib.MgsCamera of the forward
+    keep: list                  # the tensors its pointers name
+    arena: torch.Tensor         # geometry + image scratch
+    binning: torch.Tensor
+    geom_off: int
+    img_off: int
+    num_rendered: int           # the capacity, after a capacity-mode forward
+    P: int
+    H: int
+    W: int
+    device: torch.device
+
+    def pointers(self):
+        """``(geometry, binning, image)`` as the C ABI takes them."""
+        base = self.arena.data_ptr()
+        return base + self.geom_off, self.binning.data_ptr(), base + self.img_off
+
+
+def forward_scratch(color: torch.Tensor, who: str = "forward_scratch") -> ForwardScratch:
+    """The handle of the forward that produced ``color``.  Built on the first request and kept on the autograd node, so the
+    forward itself does nothing for it; ask once before the rasteriser's backward to read the scratch after it."""
+    fn = getattr(color, "grad_fn", None)
+    if fn is None or not hasattr(fn, "raster_settings"):
+        raise RuntimeError(f"{who} needs the colour image of a differentiable rasteriser forward")
+    t = getattr(fn, "_forward_scratch", None)
+    if t is None:
+        try:
+            means3D, _, _, _, _, _, _, _, arena, binning = fn.saved_tensors
+        except RuntimeError as e:
+            raise RuntimeError(f"{who}: the rasteriser's backward has already freed this forward's scratch; "
+                               f"call {who} once before that backward to keep it") from e
+        rs = fn.raster_settings
+        t = ForwardScratch(fn.cam, fn.keep, arena, binning, int(fn.geom_off), int(fn.img_off), int(fn.num_rendered),
+                           int(means3D.shape[0]), int(rs.image_height), int(rs.image_width), means3D.device)
+        fn._forward_scratch = t
+    return t
+
+
+def _blend_counters(color, symbol: str, words: int) -> list:
+    t = forward_scratch(color, symbol[4:])
+    out = torch.zeros(words, dtype=torch.int64, device=t.device)
+    with _device_guard(t.device):
+        _lib.check(getattr(_lib.load(), symbol)(C.byref(t.cam), t.P, t.num_rendered, *t.pointers(), out.data_ptr(), _stream()),
+                   symbol)
+    return out.tolist()
+
+
 def debug_blend_stats(color: torch.Tensor) -> dict:
     """Diagnostic: what the blend backward of the forward that produced ``color`` walks, fetches and reduces
     (``mgs_debug_blend_stats``; call before ``backward()`` frees the saved scratch).  Synchronises."""
-    fn = color.grad_fn
-    if fn is None or not hasattr(fn, "raster_settings"):
-        raise RuntimeError("debug_blend_stats needs the colour image of a differentiable rasteriser forward")
-    lib = _lib.load()
-    means3D, _, _, _, _, _, _, _, arena, binning = fn.saved_tensors
-    cam = fn.cam
-    out = torch.zeros(24, dtype=torch.int64, device=means3D.device)      # MGS_BLEND_STATS_WORDS
-    with _device_guard(means3D.device):
-        _lib.check(lib.mgs_debug_blend_stats(C.byref(cam), means3D.shape[0], fn.num_rendered,
-                                             arena.data_ptr() + fn.geom_off, binning.data_ptr(),
-                                             arena.data_ptr() + fn.img_off, out.data_ptr(), _stream()),
-                   "mgs_debug_blend_stats")
-    v = out.tolist()
+    v = _blend_counters(color, "mgs_debug_blend_stats", 24)                  # MGS_BLEND_STATS_WORDS
     groups = {}
     for d, name in enumerate(("halves_8x4", "halves_4x8", "blocks_4x4", "strips_8x2", "blocks_4x2")):
         groups[name] = dict(trips_paired_per_step=v[8 + 3 * d], rows=v[9 + 3 * d], trips_own_lists=v[10 + 3 * d])
@@ -430,18 +469,7 @@ def debug_blend_mask_stats(color: torch.Tensor) -> dict:
     """Diagnostic: the survivor masks the blend forward that produced ``color`` left for its backward, against the cull the
     backward would run for itself (``mgs_debug_blend_mask_stats``; call before ``backward()`` frees the saved scratch).
     Synchronises."""
-    fn = color.grad_fn
-    if fn is None or not hasattr(fn, "raster_settings"):
-        raise RuntimeError("debug_blend_mask_stats needs the colour image of a differentiable rasteriser forward")
-    lib = _lib.load()
-    means3D, _, _, _, _, _, _, _, arena, binning = fn.saved_tensors
-    out = torch.zeros(4, dtype=torch.int64, device=means3D.device)       # MGS_BLEND_MASK_STATS_WORDS
-    with _device_guard(means3D.device):
-        _lib.check(lib.mgs_debug_blend_mask_stats(C.byref(fn.cam), means3D.shape[0], fn.num_rendered,
-                                                  arena.data_ptr() + fn.geom_off, binning.data_ptr(),
-                                                  arena.data_ptr() + fn.img_off, out.data_ptr(), _stream()),
-                   "mgs_debug_blend_mask_stats")
-    v = out.tolist()
+    v = _blend_counters(color, "mgs_debug_blend_mask_stats", 4)              # MGS_BLEND_MASK_STATS_WORDS
     return dict(steps=v[0], own_cull=v[1], forward_masks=v[2], missing=v[3])
 
 

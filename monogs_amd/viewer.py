@@ -6,7 +6,7 @@ server.  Here ``HeadlessViewer.frame(snapshot, camera, mode)`` renders what it w
 * ``rgb`` / ``segmentation`` / ``depth`` / ``time``: one rasteriser forward (``segmentation`` with ``palette[obj_idx]`` as the colour
   override, slam_viewer.py:700), converted to bytes by ``mgs_viewer_compose`` with the reference's own rules (:600-636, :767-768);
 * ``elipsoids`` (the reference's spelling; its GL renderer with ``render_mod = -4``, gl_render/shaders/gau_frag.glsl:20-35): the
-  nearest splat with alpha > 0.4 per pixel, ``mgs_viewer_ellipsoids`` through the tables of that forward, which also gives the pick
+  nearest splat with alpha > 0.4 per pixel, ``mgs_viewer_ellipsoids`` through the scratch of that forward, which also gives the pick
   buffer (``want_hit=True``);
 * keyframe frustums, the current and the ground-truth camera and the trajectory are drawn over the image without a depth test, as
   Open3D draws its line sets over the background image: the host clips and projects the segments in float64 and quantises them
@@ -27,9 +27,8 @@ import torch
 
 from . import _lib
 from .camera import fused_camera_matrices
-from .feature_render import _tables
 from .gaussian_map import object_labels
-from .rasterizer import GaussianRasterizer, _device_guard, _ptr, _stream
+from .rasterizer import GaussianRasterizer, _device_guard, _ptr, _stream, forward_scratch
 from .renderer import raster_settings
 
 MODES = ("rgb", "segmentation", "depth", "time", "elipsoids")
@@ -299,16 +298,14 @@ def compose(mode: str, src: torch.Tensor, lut: Optional[torch.Tensor] = None, se
 
 
 def ellipsoids(color: torch.Tensor, threshold: float = ELLIPSOID_THRESHOLD, want_hit: bool = True):
-    """``mgs_viewer_ellipsoids`` through the tables of the differentiable rasteriser forward that produced ``color`` (found as
+    """``mgs_viewer_ellipsoids`` through the scratch of the differentiable rasteriser forward that produced ``color`` (found as
     ``render_features`` finds them): ``float32 [3, H, W]`` and, with ``want_hit``, the pick buffer ``int32 [H, W]``."""
-    t = _tables(color)
+    t = forward_scratch(color, "ellipsoids")
     out = torch.empty(3, t.H, t.W, dtype=torch.float32, device=t.device)
     hit = torch.empty(t.H, t.W, dtype=torch.int32, device=t.device) if want_hit else None
-    base = t.arena.data_ptr()
     with _device_guard(t.device):
-        _lib.check(_lib.load().mgs_viewer_ellipsoids(C.byref(t.cam), t.P, t.num_rendered, base + t.geom_off, t.binning.data_ptr(),
-                                                     base + t.img_off, float(threshold), out.data_ptr(), _ptr(hit), _stream()),
-                   "mgs_viewer_ellipsoids")
+        _lib.check(_lib.load().mgs_viewer_ellipsoids(C.byref(t.cam), t.P, t.num_rendered, *t.pointers(), float(threshold),
+                                                     out.data_ptr(), _ptr(hit), _stream()), "mgs_viewer_ellipsoids")
     return (out, hit) if want_hit else out
 
 

@@ -12,8 +12,8 @@ P, H, W = 10, 12, 20
 
 
 class _FakeForward(torch.autograd.Function):
-    """What render_features reads from the rasteriser's grad_fn: raster_settings, cam, keep, offsets, the count and ten saved
-    tensors with means3D first and the arena and the binning scratch last."""
+    """A node ``rasterizer.forward_scratch`` accepts: what ``_RasterizeGaussians.forward`` leaves on its own ctx (raster_settings,
+    cam, keep, offsets, the count, its saved tensors), with placeholders for every tensor."""
 
     @staticmethod
     def forward(ctx, colors):

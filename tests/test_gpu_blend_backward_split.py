@@ -21,20 +21,10 @@ def _settings(sc):
     return scene_settings(sc, GaussianRasterizationSettings, device=DEV)
 
 
-class _Split:
+def _Split(lib, split, **knobs):
     """blend_bwd_split (and optionally the split's own knobs) for the duration of a block; the defaults afterwards."""
-    def __init__(self, lib, split, **knobs):
-        self.lib, self.split, self.knobs = lib, split, knobs
-
-    def __enter__(self):
-        assert self.lib.mgs_debug_set_option(b"blend_bwd_split", self.split) == 0
-        for k, v in self.knobs.items():
-            assert self.lib.mgs_debug_set_option(("blend_bwd_split_" + k).encode(), v) == 0
-
-    def __exit__(self, *exc):
-        self.lib.mgs_debug_set_option(b"blend_bwd_split", -1)
-        for k in self.knobs:
-            self.lib.mgs_debug_set_option(("blend_bwd_split_" + k).encode(), -1)
+    from monogs_amd.debug import options
+    return options(blend_bwd_split=split, **{"blend_bwd_split_" + k: v for k, v in knobs.items()})
 
 
 def _grads(sc, pose_only=False, passes=1):

@@ -18,26 +18,12 @@ import functools
 import pytest
 import torch
 
+from monogs_amd.debug import options
 from monogs_amd.synthetic import make_scene, scene_settings
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 L2_TOL, RTOL, ATOL_OF_MAX, MAX_OUTLIER_FRAC = 1e-4, 1e-3, 1e-5, 2e-4      # test_gpu_parity._check_grads
-TAU_SLOTS = 256                                                           # pose-gradient lines behind the accumulator (csrc/common.h)
-
-
-class _Options:
-    """mgs_debug_set_option settings for the duration of a block; the defaults (-1) afterwards."""
-    def __init__(self, lib, **opts):
-        self.lib, self.opts = lib, opts
-
-    def __enter__(self):
-        for k, v in self.opts.items():
-            assert self.lib.mgs_debug_set_option(k.encode(), v) == 0
-
-    def __exit__(self, *exc):
-        for k in self.opts:
-            self.lib.mgs_debug_set_option(k.encode(), -1)
 
 
 def _hold(got, ref, what):
@@ -107,13 +93,13 @@ def test_default_backward_matches_the_transposed_kernel(native_lib, name, scanne
     reference is blend_backward_t_kernel (blend_bwd_transposed = 1).  Both binning paths (radix_scanned).  The forward's
     images are those of a run whose per-tile depth sort is a launch of its own, bit for bit."""
     lib, sc = native_lib, _scene(name)
-    with _Options(lib, radix_scanned=scanned):
-        with _Options(lib, blend_bwd_transposed=1):
+    with options(radix_scanned=scanned):
+        with options(blend_bwd_transposed=1):
             img_ref, ref = _grads(sc, pose_only)
-        with _Options(lib, tile_sort_fused=0):
+        with options(tile_sort_fused=0):
             img_unfused, _ = _grads(sc, pose_only)
         for split in (0, 1):
-            with _Options(lib, blend_bwd_split=split):
+            with options(blend_bwd_split=split):
                 img, got = _grads(sc, pose_only)
                 assert lib.mgs_debug_last_backward_split() == split
             for a, b, c in zip(img, img_ref, img_unfused):
@@ -127,8 +113,8 @@ def test_default_backward_matches_the_transposed_kernel(native_lib, name, scanne
 @pytest.mark.parametrize("name", SCENES)
 def test_the_forward_masks_cover_the_backward_cull(native_lib, name, scanned):
     lib = native_lib
-    with _Options(lib, radix_scanned=scanned):
-        a = _Abi(lib, _scene(name))
+    with options(radix_scanned=scanned):
+        a = _abi(_scene(name))
         a.render(a.preprocess(prepare=False))
         stats = torch.zeros(4, dtype=torch.int64, device=DEV)
         from monogs_amd import _lib
@@ -144,98 +130,36 @@ def test_the_forward_masks_cover_the_backward_cull(native_lib, name, scanned):
 
 # ---- cleared lines, through the C ABI ------------------------------------------------------------------------------------------
 
-class _Abi:
-    """One scene's buffers and the three calls: preprocess (+ prepare_backward), render (exact or capacity), backward."""
-    def __init__(self, lib, sc):
-        from monogs_amd.rasterizer import GaussianRasterizationSettings, _camera
-        self.lib, self.sc = lib, sc
-        self.P = P = sc.means3D.shape[0]
-        self.H, self.W = H, W = sc.grad_depth.shape[1:]
-        st = scene_settings(sc, GaussianRasterizationSettings, device=DEV)
-        self.keep = []
-        self.cam = _camera(st, 0, self.keep, 3)
-        d = lambda t: t.to(DEV).contiguous()  # noqa: E731
-        self.means, self.opac, self.col, self.rot = d(sc.means3D), d(sc.opacities), d(sc.colors), d(sc.rotations)
-        self.scales = d(sc.scales if sc.scales.shape[1] == 3 else sc.scales.repeat(1, 3))
-        self.g_color, self.g_depth = d(sc.grad_color), d(sc.grad_depth)
-        u8 = dict(dtype=torch.uint8, device=DEV)
-        self.geom = torch.empty(lib.mgs_geometry_bytes(P), **u8)
-        self.img = torch.empty(lib.mgs_image_bytes(W, H), **u8)
-        self.radii = torch.empty(P, dtype=torch.int32, device=DEV)
-        self.n_touched = torch.empty(P, dtype=torch.int32, device=DEV)
-        self.out = torch.empty(5, H, W, dtype=torch.float32, device=DEV)
-        self.status = torch.zeros(1, dtype=torch.int32, device=DEV)
-        self.scratch = torch.empty(lib.mgs_backward_bytes(P), **u8)
-        tau = int(lib.mgs_backward_tau(self.scratch.data_ptr(), P)) - self.scratch.data_ptr()
-        self.tau_off = tau
-        self.acc_off = tau - (P + TAU_SLOTS) * 64
-        assert self.acc_off >= 0 and tau + 64 <= self.scratch.numel()
-        self.binning, self.R = None, 0
+def _abi(sc):
+    """debug.RawForward on the scene: preprocess (+ prepare_backward), render (exact or capacity), backward."""
+    from monogs_amd.debug import RawForward
+    from monogs_amd.rasterizer import GaussianRasterizationSettings
+    d = lambda t: t.to(DEV)  # noqa: E731
+    return RawForward(scene_settings(sc, GaussianRasterizationSettings, device=DEV), d(sc.means3D), d(sc.opacities),
+                      colors_precomp=d(sc.colors), scales=d(sc.scales if sc.scales.shape[1] == 3 else sc.scales.repeat(1, 3)),
+                      rotations=d(sc.rotations), grad_color=d(sc.grad_color), grad_depth=d(sc.grad_depth))
 
-    def lines(self):                           # [P][16] words of the accumulator
-        return self.scratch[self.acc_off:self.acc_off + self.P * 64].view(torch.int32).reshape(self.P, 16)
 
-    def pose_part(self):                       # the pose slots and the line that holds the six output floats
-        return self.scratch[self.acc_off + self.P * 64:self.tau_off + 64].view(torch.int32)
-
-    def preprocess(self, prepare):
-        from monogs_amd import _lib
-        from monogs_amd.rasterizer import _stream
-        nr = C.c_uint64(0)
-        _lib.check(self.lib.mgs_forward_preprocess(
-            C.byref(self.cam), self.P, self.means.data_ptr(), None, self.col.data_ptr(), self.opac.data_ptr(),
-            self.scales.data_ptr(), self.rot.data_ptr(), None, self.geom.data_ptr(), self.radii.data_ptr(),
-            self.scratch.data_ptr() if prepare else None, C.byref(nr), None, None, None, _stream()), "mgs_forward_preprocess")
-        return int(nr.value)
-
-    def render(self, R, capacity=False):
-        from monogs_amd import _lib
-        from monogs_amd.rasterizer import _stream
-        # (torch.empty: the library must not rely on a cleared binning scratch)
-        self.binning = torch.empty(self.lib.mgs_binning_bytes(R, self.W, self.H), dtype=torch.uint8, device=DEV)
-        self.R = R
-        o = self.out
-        fn = self.lib.mgs_forward_render_capacity if capacity else self.lib.mgs_forward_render
-        _lib.check(fn(C.byref(self.cam), self.P, R, self.geom.data_ptr(), self.binning.data_ptr(), self.img.data_ptr(),
-                      o[0:3].data_ptr(), o[3:4].data_ptr(), o[4:5].data_ptr(), self.n_touched.data_ptr(),
-                      self.status.data_ptr(), None, _stream()), "render")
-        torch.cuda.synchronize()
-
-    def backward(self, prepared):
-        from monogs_amd import _lib
-        from monogs_amd.rasterizer import _stream
-        P, f32 = self.P, dict(dtype=torch.float32, device=DEV)
-        g = dict(means2D=torch.empty(P, 3, **f32), colors=torch.empty(P, 3, **f32), opacities=torch.empty(P, 1, **f32),
-                 means3D=torch.empty(P, 3, **f32), scales=torch.empty(P, 3, **f32), rotations=torch.empty(P, 4, **f32))
-        tau = self.scratch[self.tau_off:self.tau_off + 24].view(torch.float32)
-        o = self.out
-        _lib.check(self.lib.mgs_backward(
-            C.byref(self.cam), P, self.R, self.means.data_ptr(), None, self.col.data_ptr(), self.opac.data_ptr(),
-            self.scales.data_ptr(), self.rot.data_ptr(), None, self.radii.data_ptr(), self.geom.data_ptr(),
-            self.binning.data_ptr(), self.img.data_ptr(), self.g_color.data_ptr(), self.g_depth.data_ptr(),
-            o[0:3].data_ptr(), o[3:4].data_ptr(), g["means2D"].data_ptr(), g["colors"].data_ptr(), g["opacities"].data_ptr(),
-            g["means3D"].data_ptr(), None, None, g["scales"].data_ptr(), g["rotations"].data_ptr(), tau.data_ptr(),
-            self.scratch.data_ptr(), 1 if prepared else 0, None, _stream()), "mgs_backward")
-        torch.cuda.synchronize()
-        g["tau"] = tau.clone()
-        return g
+def _lines(a):                                 # [P][16] words of the accumulator
+    return a.table("backward.grad_acc", torch.int32).reshape(a.P, 16)
 
 
 def _prepared_forward_and_backward(lib, sc, what, capacity_of=None):
     """0xFF-filled scratch -> preprocess(prepare_backward) + render: the lines of the visible Gaussians, the pose slots and the
     six output floats are zero bits.  Then the gradients of a prepared backward against those of one that clears the same
     (caller-zeroed) scratch itself.  `capacity_of`: R -> capacity of a capacity-mode render."""
-    a = _Abi(lib, sc)
+    a = _abi(sc)
     a.scratch.fill_(0xFF)
     R = a.preprocess(prepare=True)
     cap = capacity_of(R) if capacity_of else None
     a.render(cap if cap is not None else R, capacity=cap is not None)
     vis = a.radii > 0
-    dirty = int((a.lines()[vis] != 0).sum())
+    dirty = int((_lines(a)[vis] != 0).sum())
     print(f"{what}: P {a.P}, visible {int(vis.sum())}, num_rendered {R}, capacity {cap}, status {int(a.status.item())}, "
           f"dirty words in visible lines {dirty}")
     assert dirty == 0
-    assert int((a.pose_part() != 0).sum()) == 0
+    for part in ("backward.tau_part", "backward.tau"):      # the pose slots and the line that holds the six output floats
+        assert int((a.table(part, torch.int32) != 0).sum()) == 0
     if cap is not None and cap < R:
         assert int(a.status.item()) & 1                 # the overflow was raised
     got = a.backward(prepared=True)
@@ -251,13 +175,13 @@ def _prepared_forward_and_backward(lib, sc, what, capacity_of=None):
 def test_the_forward_clears_the_gradient_lines(native_lib, P, intr, scanned):
     """P = 1 and 100: fewer lines than tiles (most workgroups have no share); 20 001: shares that do not divide P and a last
     share cut short; 640x480 and 1200x680 (tile counts 1200 and 3225); both binning paths."""
-    with _Options(native_lib, radix_scanned=scanned):
+    with options(radix_scanned=scanned):
         _prepared_forward_and_backward(native_lib, make_scene(P, intr, seed=11 + P % 7), f"P {P} {intr} scanned {scanned}")
 
 
 @pytest.mark.parametrize("scanned", [0, 1])
 def test_capacity_mode_overflow_still_clears(native_lib, scanned):
-    with _Options(native_lib, radix_scanned=scanned):
+    with options(radix_scanned=scanned):
         _prepared_forward_and_backward(native_lib, make_scene(20001, "fr3_office", seed=131), f"capacity R // 2, scanned {scanned}",
                                        capacity_of=lambda R: max(R // 2, 1))
 
@@ -270,7 +194,7 @@ def test_nothing_in_view(native_lib):
     sc = sc._replace(means3D=((pc - sc.t[None, :]) @ sc.R).contiguous())
     a, R = _prepared_forward_and_backward(native_lib, sc, "behind the camera")
     assert R == 0 and int((a.radii > 0).sum()) == 0
-    assert int((a.lines() != 0).sum()) == 0             # (all P lines are cleared, visible or not)
+    assert int((_lines(a) != 0).sum()) == 0             # (all P lines are cleared, visible or not)
 
 
 def test_an_unprepared_forward_clears_nothing(native_lib):
@@ -278,11 +202,11 @@ def test_an_unprepared_forward_clears_nothing(native_lib):
     the same geometry scratch; and the hand-over is good for ONE render call: a second render of the same preprocess result
     does not touch the scratch again (the caller may have freed it)."""
     lib = native_lib
-    a = _Abi(lib, make_scene(5000, "fr3_office", seed=0))
+    a = _abi(make_scene(5000, "fr3_office", seed=0))
     a.scratch.fill_(0xFF)
     R = a.preprocess(prepare=True)
     a.render(R)
-    assert int((a.lines() != 0).sum()) == 0
+    assert int((_lines(a) != 0).sum()) == 0
     a.scratch.fill_(0xFF)
     a.render(R)                                         # the same geometry scratch, rendered again
     assert bool((a.scratch == 0xFF).all())

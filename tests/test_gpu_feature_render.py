@@ -19,6 +19,7 @@ import math
 import pytest
 import torch
 
+from monogs_amd.debug import options
 from monogs_amd.synthetic import make_scene, scene_settings
 from oracle import OracleSettings, rasterize, rasterize_autograd
 
@@ -259,12 +260,9 @@ def test_binning_paths_and_forward_modes(native_lib):
     R.set_sync_free(False)
     assert native_lib.mgs_binning_path(P, W, H) == 0
     ref = render_features(_forward(sc)[0], feat)          # exact mode, global depth sort (records the capacity hint)
-    try:
-        native_lib.mgs_debug_set_option(b"radix_scanned", 1)
+    with options(radix_scanned=1):
         assert native_lib.mgs_binning_path(P, W, H) == 1
         per_tile = render_features(_forward(sc)[0], feat)
-    finally:
-        native_lib.mgs_debug_set_option(b"radix_scanned", -1)
     assert (per_tile - ref).abs().max() <= 1e-6
     try:
         R.set_sync_free(True, headroom=1.2)

@@ -5,6 +5,7 @@ import pytest
 import torch
 
 from monogs_amd import camera as cam
+from monogs_amd.debug import options
 from monogs_amd.synthetic import make_scene, scene_settings
 from oracle import OracleSettings, gs_oracle, rasterize, rasterize_autograd
 
@@ -311,11 +312,9 @@ def test_radix_lookback_timeout_is_reported_in_every_mode(native_lib):
 def test_scan_paths_agree(native_lib):
     """The single-launch scan of SLAM-sized maps (block totals all-gathered through status words) and the two-launch scan of
     large ones give the same offsets: tables and image bit for bit, in the exact and in the capacity mode."""
-    from monogs_amd import _lib
     from monogs_amd import rasterizer as R
     from monogs_amd.debug import forward_tables
     from monogs_amd.rasterizer import GaussianRasterizer
-    lib = _lib.load()
     sc = make_scene(70000, "fr3_office", seed=9)          # 35 scan blocks
     st = _hip_st(sc)
     dev = lambda t: t.to(DEV)  # noqa: E731
@@ -326,13 +325,12 @@ def test_scan_paths_agree(native_lib):
     try:
         with torch.no_grad():
             cap_one = GaussianRasterizer(st)(**full)
-        lib.mgs_debug_set_option(b"scan_small", 0)
-        two = forward_tables(st, dev(sc.means3D), dev(sc.opacities), **args)
-        with torch.no_grad():
-            cap_two = GaussianRasterizer(st)(**full)
+        with options(scan_small=0):
+            two = forward_tables(st, dev(sc.means3D), dev(sc.opacities), **args)
+            with torch.no_grad():
+                cap_two = GaussianRasterizer(st)(**full)
         assert not R.check_overflow()
     finally:
-        lib.mgs_debug_set_option(b"scan_small", -1)
         R.set_sync_free(False)
     assert one["num_rendered"] == two["num_rendered"] > 0
     for k in ("ranges", "point_list", "tile_sorted", "color", "n_contrib", "n_touched"):
@@ -378,11 +376,9 @@ def test_duplicate_emission_paths_agree(native_lib, n, intr):
     """duplicate_kernel emits the (tile, Gaussian) instances either Gaussian-major (a wave owns the slots of its 64
     Gaussians) or slot-major (every wave owns an equal share of the output slots and searches its first Gaussian): same
     keys, same values, hence the same tables and image, in the exact and in the capacity mode."""
-    from monogs_amd import _lib
     from monogs_amd import rasterizer as R
     from monogs_amd.debug import forward_tables
     from monogs_amd.rasterizer import GaussianRasterizer
-    lib = _lib.load()
     sc = make_scene(n, intr, seed=13)
     st = _hip_st(sc)
     dev = lambda t: t.to(DEV)  # noqa: E731
@@ -391,16 +387,15 @@ def test_duplicate_emission_paths_agree(native_lib, n, intr):
     out = {}
     try:
         for mode in (0, 1):
-            lib.mgs_debug_set_option(b"dup_slot_major", mode)
-            out[mode] = forward_tables(st, dev(sc.means3D), dev(sc.opacities), **args)
-            R.set_sync_free(True)
-            with torch.no_grad():
-                GaussianRasterizer(st)(**full)                                  # (records the capacity hint)
-                out[mode]["cap"] = GaussianRasterizer(st)(**full)[0]
-            assert not R.check_overflow()
-            R.set_sync_free(False)
+            with options(dup_slot_major=mode):
+                out[mode] = forward_tables(st, dev(sc.means3D), dev(sc.opacities), **args)
+                R.set_sync_free(True)
+                with torch.no_grad():
+                    GaussianRasterizer(st)(**full)                              # (records the capacity hint)
+                    out[mode]["cap"] = GaussianRasterizer(st)(**full)[0]
+                assert not R.check_overflow()
+                R.set_sync_free(False)
     finally:
-        lib.mgs_debug_set_option(b"dup_slot_major", -1)
         R.set_sync_free(False)
     assert out[0]["num_rendered"] == out[1]["num_rendered"] > 0
     for k in ("ranges", "point_list", "tile_sorted", "color", "n_contrib", "n_touched"):
@@ -474,15 +469,14 @@ def test_tile_sort_timeout_raises_its_own_status_bit_and_blends_nothing(native_l
     st = _hip_st(sc)
     dev = lambda t: t.to(DEV)  # noqa: E731
     args = dict(colors_precomp=dev(sc.colors), scales=dev(sc.scales), rotations=dev(sc.rotations))
-    lib.mgs_debug_set_option(b"radix_scanned", 0)         # one-sweep tile sort whatever the instance count
     try:
-        good = forward_tables(st, dev(sc.means3D), dev(sc.opacities), **args)
-        assert good["status"] == 0 and float(good["opacity"].max()) > 0.5 and good["num_rendered"] > 8192
-        bad = forward_tables(st, dev(sc.means3D), dev(sc.opacities), **args,
-                             between=lambda: lib.mgs_debug_set_radix_spin_limit(0))
+        with options(radix_scanned=0):                    # one-sweep tile sort whatever the instance count
+            good = forward_tables(st, dev(sc.means3D), dev(sc.opacities), **args)
+            assert good["status"] == 0 and float(good["opacity"].max()) > 0.5 and good["num_rendered"] > 8192
+            bad = forward_tables(st, dev(sc.means3D), dev(sc.opacities), **args,
+                                 between=lambda: lib.mgs_debug_set_radix_spin_limit(0))
     finally:
         lib.mgs_debug_set_radix_spin_limit(0xFFFFFFFF)
-        lib.mgs_debug_set_option(b"radix_scanned", -1)
     assert bad["status"] == 4                             # MGS_STATUS_TILE_SORT_TIMEOUT only: the depth sort had finished
     assert float(bad["opacity"].abs().max()) == 0.0 and int(bad["n_contrib"].max()) == 0
     assert int(bad["ranges"].abs().max()) == 0

@@ -8,6 +8,7 @@ tests/test_gpu_parity.py::test_blend_backward_paths_agree: 1e-6 relative L2 per 
 import pytest
 import torch
 
+from monogs_amd.debug import options
 from monogs_amd.synthetic import make_scene, scene_settings
 
 DEV = "cuda:0"
@@ -34,18 +35,13 @@ def _run(lib, sc, pose_only, transposed, split):
     theta = torch.zeros(3, device=DEV, requires_grad=True)
     rho = torch.zeros(3, device=DEV, requires_grad=True)
     m2 = torch.zeros_like(leaves["means3D"], requires_grad=not pose_only)
-    try:
-        assert lib.mgs_debug_set_option(b"blend_bwd_transposed", transposed) == 0
-        assert lib.mgs_debug_set_option(b"blend_bwd_split", split) == 0
+    with options(blend_bwd_transposed=transposed, blend_bwd_split=split):
         out = GaussianRasterizer(st)(means3D=leaves["means3D"], means2D=m2, opacities=leaves["opacities"],
                                      colors_precomp=leaves["colors_precomp"], scales=leaves["scales"],
                                      rotations=leaves["rotations"], theta=theta, rho=rho)
         # (the split launch needs the forward's images: `out` stays alive across the backward)
         torch.autograd.backward([out[0], out[2]], [sc.grad_color.to(DEV), sc.grad_depth.to(DEV)])
         torch.cuda.synchronize()
-    finally:
-        lib.mgs_debug_set_option(b"blend_bwd_transposed", -1)
-        lib.mgs_debug_set_option(b"blend_bwd_split", -1)
     g = dict(theta=theta.grad.clone(), rho=rho.grad.clone())
     if not pose_only:
         g.update({k: v.grad.clone() for k, v in leaves.items()}, means2D=m2.grad.clone())

@@ -8,6 +8,7 @@ different but equally valid exp rounding flips them, upstream included.
 import pytest
 import torch
 
+from monogs_amd.debug import options
 from monogs_amd.synthetic import make_scene, scene_settings
 from oracle import OracleSettings, rasterize, rasterize_autograd
 
@@ -266,15 +267,11 @@ def test_blend_backward_paths_agree(native_lib, P, intr, seed, pose_only):
         if not pose_only:
             g.update({k: v.grad.clone() for k, v in leaves.items()}, means2D=m2.grad.clone())
         return g
-    try:
-        native_lib.mgs_debug_set_option(b"blend_bwd_transposed", 2)
-        a = run()
-        native_lib.mgs_debug_set_option(b"blend_bwd_transposed", 1)
-        b1 = run()
-        native_lib.mgs_debug_set_option(b"blend_bwd_transposed", 0)
-        b0 = run()
-    finally:
-        native_lib.mgs_debug_set_option(b"blend_bwd_transposed", 2)
+    res = {}
+    for kernel in (2, 1, 0):
+        with options(blend_bwd_transposed=kernel):
+            res[kernel] = run()
+    a, b1, b0 = res[2], res[1], res[0]
     for b in (b1, b0):
         assert set(a) == set(b) and len(a) == (2 if pose_only else 8)
         for k in a:
@@ -347,11 +344,8 @@ def test_c5_full_size_properties(native_lib, monkeypatch):
     assert torch.equal(t["color"], t2["color"]) and torch.equal(t["point_list"], t2["point_list"])
     assert torch.equal(t["n_touched"], t2["n_touched"])
     # the two radix-sort paths (pre-scanned offsets, the default at this size, and one-sweep look-back) agree bit for bit
-    native_lib.mgs_debug_set_option(b"radix_scanned", 0)
-    try:
+    with options(radix_scanned=0):
         t3 = forward_tables(st, dev(sc.means3D), dev(sc.opacities), **args)
-    finally:
-        native_lib.mgs_debug_set_option(b"radix_scanned", -1)
     assert torch.equal(t["point_list"], t3["point_list"]) and torch.equal(t["ranges"], t3["ranges"])
     assert torch.equal(t["color"], t3["color"])
     # capacity mode (device-side instance count; what bench.py times) renders the same image as the exact path
@@ -393,13 +387,12 @@ def test_knn_morton_path(native_lib, monkeypatch):
     mixed = torch.cat([sheet, clusters, dup, uniform[:5000], torch.tensor([[1e4, -1e4, 3e3]])])
     for name, pts in (("uniform", uniform), ("mixed", mixed), ("tiny", uniform[:70]), ("same", torch.ones(300, 3))):
         d = pts.to(DEV)
-        native_lib.mgs_debug_set_option(b"knn_grid_min", 4)            # force the Morton-box path
-        grid = distCUDA2(d).cpu()
-        native_lib.mgs_debug_set_option(b"knn_grid_min", 1 << 30)      # force the all-pairs sweep
-        sweep = distCUDA2(d).cpu()
+        with options(knn_grid_min=4):                                  # force the Morton-box path
+            grid = distCUDA2(d).cpu()
+        with options(knn_grid_min=1 << 30):                            # force the all-pairs sweep
+            sweep = distCUDA2(d).cpu()
         assert torch.equal(grid, sweep), (name, (grid - sweep).abs().max())
         assert torch.allclose(grid, dist2_knn(pts), rtol=1e-5, atol=1e-9), name
-    native_lib.mgs_debug_set_option(b"knn_grid_min", -1)
     # full size: 2 M points (the C5 map) in milliseconds; property check = every result is a true 3-NN mean on a sample
     big = (torch.rand(2_000_000, 3, generator=g) * 20 - 10).to(DEV)
     distCUDA2(big)

@@ -5,7 +5,6 @@ Scenes are forced onto the per-tile path (radix_scanned = 1) at 640x480.  Sizes:
 one block, one past the block boundary, a partial third block, and two sizes with many blocks (20 000: 79 blocks of 256,
 10 of 2048).  Both emission orders of duplicate_kernel (Gaussian-major, slot-major) decode their slots with the
 reciprocal multiply of dup_divmod (tests/test_dup_slot_decode.py) from the 16-byte LDS entries."""
-import ctypes as C
 import functools
 
 import pytest
@@ -28,24 +27,9 @@ def _args(sc):
     return dict(colors_precomp=sc.colors.to(DEV), scales=sc.scales.repeat(1, 3).to(DEV), rotations=sc.rotations.to(DEV))
 
 
-class _opts:
-    """Per-tile path with the given options for the duration of a block (the options are process-global)."""
-
-    def __init__(self, lib, **kw):
-        self.lib, self.kw = lib, dict(radix_scanned=1, **kw)
-
-    def __enter__(self):
-        for k, v in self.kw.items():
-            assert self.lib.mgs_debug_set_option(k.encode(), v) == 0
-
-    def __exit__(self, *exc):
-        for k in self.kw:
-            self.lib.mgs_debug_set_option(k.encode(), -1)
-
-
 def _tables(lib, sc, **kw):
-    from monogs_amd.debug import forward_tables
-    with _opts(lib, **kw):
+    from monogs_amd.debug import forward_tables, options
+    with options(radix_scanned=1, **kw):                    # (the per-tile path, whatever the size)
         t = forward_tables(_settings(sc), sc.means3D.to(DEV), sc.opacities.to(DEV), **_args(sc))
     assert t["depth_path"] == "per_tile" and t["status"] == 0
     return t
@@ -100,62 +84,24 @@ def test_pre_scan_both_emission_orders_on_large_splats(native_lib):
         _same(_tables(native_lib, sc, pre_scan=pre, dup_slot_major=major), ref)
 
 
-def _au(v, a=256):
-    return (v + a - 1) // a * a
-
-
 @pytest.mark.gpu
 def test_pre_scan_capacity_below_the_instance_count(native_lib):
     """Capacity mode with half the slots (the shape of test_gpu_tile_sort_fused.py's case): the same overflow word, images,
     ranges and live point list under both scans."""
-    from monogs_amd import _lib
-    from monogs_amd.rasterizer import _camera, _f32, _ptr, _stream
-    lib = native_lib
+    from monogs_amd.debug import RawForward, options
     sc = make_scene(20000, "replica", seed=2)
-    st = _settings(sc)
-    H, W, P = int(st.image_height), int(st.image_width), sc.means3D.shape[0]
-    ntiles = ((W + 15) // 16) * ((H + 15) // 16)
-    tile_bits = max(1, (ntiles - 1).bit_length())
-    args = _args(sc)
-    means, opac = _f32(sc.means3D.to(DEV), "means3D"), _f32(sc.opacities.to(DEV), "opacities")
-    cols, scales, rots = _f32(args["colors_precomp"], "c"), _f32(args["scales"], "s"), _f32(args["rotations"], "r")
     out = {}
     for pre in (1, 0):
-        with _opts(lib, pre_scan=pre):
-            keep = []
-            cam = _camera(st, 0, keep, 3)
-            u8 = dict(dtype=torch.uint8, device=DEV)
-            geom = torch.zeros(lib.mgs_geometry_bytes(P), **u8)
-            img = torch.zeros(lib.mgs_image_bytes(W, H), **u8)
-            radii = torch.empty(P, dtype=torch.int32, device=DEV)
-            n_touched = torch.empty(P, dtype=torch.int32, device=DEV)
-            o = [torch.empty(c, H, W, dtype=torch.float32, device=DEV) for c in (3, 1, 1)]
-            nr = C.c_uint64(0)
-            _lib.check(lib.mgs_forward_preprocess(C.byref(cam), P, _ptr(means), None, _ptr(cols), _ptr(opac), _ptr(scales),
-                                                  _ptr(rots), None, geom.data_ptr(), radii.data_ptr(), None, C.byref(nr),
-                                                  None, None, None, _stream()), "preprocess")
-            R = int(nr.value)
-            cap = R // 2
-            binning = torch.zeros(lib.mgs_binning_bytes(cap, W, H), **u8)
-            over = torch.zeros(1, dtype=torch.int32, device=DEV)
-            _lib.check(lib.mgs_forward_render_capacity(C.byref(cam), P, cap, geom.data_ptr(), binning.data_ptr(),
-                                                       img.data_ptr(), o[0].data_ptr(), o[1].data_ptr(), o[2].data_ptr(),
-                                                       n_touched.data_ptr(), over.data_ptr(), None, _stream()),
-                       "render_capacity")
-            torch.cuda.synchronize()
-            assert lib.mgs_binning_path(P, W, H) == 1
-
-            def view(buf, off, nbytes, dtype):
-                base = _au(buf.data_ptr()) - buf.data_ptr()
-                return buf[base + off: base + off + nbytes].view(dtype)
-
-            ranges = view(img, 2 * _au(H * W * 4), ntiles * 8, torch.int32).reshape(ntiles, 2).clone()
-            in_b = ((tile_bits + 7) // 8) % 2 == 1
-            point_list = view(binning, (3 if in_b else 2) * _au(cap * 4), cap * 4, torch.int32)
+        with options(radix_scanned=1, pre_scan=pre):
+            f = RawForward(_settings(sc), sc.means3D.to(DEV), sc.opacities.to(DEV), **_args(sc), zero=True)
+            R = f.preprocess()
+            f.render(R // 2, capacity=True)
+            assert native_lib.mgs_binning_path(f.P, f.W, f.H) == 1
+            ranges = f.table("image.ranges").reshape(-1, 2).clone()
             live = int(ranges[:, 1].max())
-            out[pre] = dict(over=int(over.item()), R=R, color=o[0].clone(), depth=o[1].clone(), opacity=o[2].clone(),
-                            n_touched=n_touched.clone(), radii=radii.clone(), ranges=ranges, live=live,
-                            point_list=point_list[:live].clone())
+            out[pre] = dict(over=int(f.status.item()), R=R, color=f.color.clone(), depth=f.depth.clone(),
+                            opacity=f.opacity.clone(), n_touched=f.n_touched.clone(), radii=f.radii.clone(), ranges=ranges,
+                            live=live, point_list=f.table("binning.point_list")[:live].clone())
     a, b = out[1], out[0]
     assert a["over"] != 0 and a["over"] == b["over"] and a["R"] == b["R"]
     assert 0 < a["live"] <= a["R"] // 2

@@ -9,6 +9,8 @@ test knob) put them, on every path (1024 / 2048-pair tiles with the all-gather o
 import pytest
 import torch
 
+from monogs_amd.debug import options
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
@@ -63,11 +65,8 @@ def test_atomic_ranking_equals_ballot_ranking(native_lib, n):
     gen = torch.Generator().manual_seed(n)
     keys = _keys("five", n, 16, gen).to(DEV).to(torch.int32)
     a = _sort(native_lib, keys, 16)
-    native_lib.mgs_debug_set_option(b"radix_ballot_rank", 1)
-    try:
+    with options(radix_ballot_rank=1):
         b = _sort(native_lib, keys, 16)
-    finally:
-        native_lib.mgs_debug_set_option(b"radix_ballot_rank", 0)
     assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
 
 
@@ -79,11 +78,8 @@ def test_block_ids_as_tile_ids_on_an_exclusive_device(native_lib, n, kind, bits)
     gen = torch.Generator().manual_seed(n * 17 + bits)
     keys = _keys(kind, n, bits, gen).to(DEV)
     k32 = keys.to(torch.int32) if bits < 32 else (keys - ((keys >> 31) << 32)).to(torch.int32)
-    native_lib.mgs_debug_set_option(b"debug_sort_exclusive", 1)
-    try:
+    with options(debug_sort_exclusive=1):
         got = _sort(native_lib, k32, bits)
-    finally:
-        native_lib.mgs_debug_set_option(b"debug_sort_exclusive", 0)
     ref_k, ref_v = torch.sort(keys, stable=True)
     assert torch.equal(got[0].long() & 0xFFFFFFFF, ref_k) and torch.equal(got[1].long(), ref_v)
 
@@ -96,11 +92,8 @@ def test_xcd_band_tile_order_changes_nothing(native_lib, n):
     keys = _keys("depth", n, 32, gen).to(DEV)
     k32 = (keys - ((keys >> 31) << 32)).to(torch.int32)
     a = _sort(native_lib, k32, 32)
-    native_lib.mgs_debug_set_option(b"radix_xcd_band", 0)
-    try:
+    with options(radix_xcd_band=0):
         b = _sort(native_lib, k32, 32)
-    finally:
-        native_lib.mgs_debug_set_option(b"radix_xcd_band", 1)
     assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
     ref_k, ref_v = torch.sort(keys, stable=True)
     assert torch.equal(a[0].long() & 0xFFFFFFFF, ref_k) and torch.equal(a[1].long(), ref_v)
@@ -111,11 +104,8 @@ def test_both_offset_paths_agree_on_a_large_sort(native_lib):
     keys = _keys("depth", 2_000_000, 32, gen).to(DEV)
     k32 = (keys - ((keys >> 31) << 32)).to(torch.int32)
     a = _sort(native_lib, k32, 32)
-    native_lib.mgs_debug_set_option(b"radix_scanned", 0)
-    try:
+    with options(radix_scanned=0):
         b = _sort(native_lib, k32, 32)
-    finally:
-        native_lib.mgs_debug_set_option(b"radix_scanned", -1)
     assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
 
 
@@ -142,11 +132,8 @@ def test_depths_beyond_the_narrow_range_take_the_fourth_pass(native_lib):
     key = (t["tile_sorted"].long() << 32) | (t["depth_key"].long() & 0xFFFFFFFF)[pl]
     d = key[1:] - key[:-1]
     assert bool((d >= 0).all()) and bool((pl[1:][d == 0] > pl[:-1][d == 0]).all())
-    native_lib.mgs_debug_set_option(b"radix_scanned", 0)
-    try:
+    with options(radix_scanned=0):
         t2 = forward_tables(st, dev(sc.means3D), dev(sc.opacities), **args)
-    finally:
-        native_lib.mgs_debug_set_option(b"radix_scanned", -1)
     assert torch.equal(t["point_list"], t2["point_list"]) and torch.equal(t["ranges"], t2["ranges"])
     assert torch.equal(t["perm"], t2["perm"]) and torch.equal(t["color"], t2["color"])
 

@@ -4,11 +4,10 @@ Large maps no longer sort all Gaussians by depth: the instances are emitted in i
 into the tile sort's pairs, and one workgroup per tile sorts its list by (depth bits, index) in LDS
 (csrc/binning.hip, tile_depth_sort_kernel).  The "radix_scanned" option forces either path at any size (1: per tile,
 0: the global sort), so small scenes exercise both and compare them."""
-import ctypes as C
-
 import pytest
 import torch
 
+from monogs_amd.debug import options
 from monogs_amd.synthetic import make_scene, scene_settings
 
 DEV = "cuda:0"
@@ -23,28 +22,15 @@ def _args(sc):
     return dict(colors_precomp=sc.colors.to(DEV), scales=sc.scales.repeat(1, 3).to(DEV), rotations=sc.rotations.to(DEV))
 
 
-class _path:
-    """Force the binning path for the duration of a block (the option is process-global)."""
-
-    def __init__(self, lib, value):
-        self.lib, self.value = lib, value
-
-    def __enter__(self):
-        assert self.lib.mgs_debug_set_option(b"radix_scanned", self.value) == 0
-
-    def __exit__(self, *exc):
-        self.lib.mgs_debug_set_option(b"radix_scanned", -1)
-
-
 def _tables(lib, sc, value):
     from monogs_amd.debug import forward_tables
-    with _path(lib, value):
+    with options(radix_scanned=value):
         return forward_tables(_settings(sc), sc.means3D.to(DEV), sc.opacities.to(DEV), **_args(sc))
 
 
 def _grads(lib, sc, value):
     from monogs_amd.rasterizer import GaussianRasterizer
-    with _path(lib, value):
+    with options(radix_scanned=value):
         leaves = {k: v.to(DEV).clone().requires_grad_(True) for k, v in
                   dict(means3D=sc.means3D, opacities=sc.opacities, colors_precomp=sc.colors,
                        scales=sc.scales.repeat(1, 3), rotations=sc.rotations).items()}
@@ -103,14 +89,11 @@ def test_binning_path_at_the_bit_budget_edges(native_lib):
     assert lib.mgs_binning_path(600_000, 4112, 4096) == 0              # 17 tile bits: a third tile-sort pass
     assert lib.mgs_binning_path(600_000, 64, 64) == 1                  # 16 tiles: no low depth bits in the value
     assert lib.mgs_binning_path(0, 640, 480) == 0
-    try:
-        lib.mgs_debug_set_option(b"radix_scanned", 1)
+    with options(radix_scanned=1):
         assert lib.mgs_binning_path(5000, 640, 480) == 1
         assert lib.mgs_binning_path((1 << 26) - 1, 640, 480) == 1     # 1200 tiles: 11 bits, any P the library takes
-        lib.mgs_debug_set_option(b"radix_scanned", 0)
+    with options(radix_scanned=0):
         assert lib.mgs_binning_path(2_000_000, 1920, 1080) == 0
-    finally:
-        lib.mgs_debug_set_option(b"radix_scanned", -1)
 
 
 @pytest.mark.gpu
@@ -173,40 +156,15 @@ def test_lists_longer_than_the_lds_take_the_global_segment_sort(native_lib):
 def test_capacity_below_the_instance_count(native_lib):
     """Capacity mode with fewer slots than instances: both paths report the overflow and neither reads or writes past
     the capacity (the per-tile kernel clamps its ranges to the live count)."""
-    from monogs_amd import _lib
-    from monogs_amd.rasterizer import _camera, _f32, _ptr, _stream
-    lib = native_lib
+    from monogs_amd.debug import RawForward
     sc = make_scene(20000, "replica", seed=2)
-    st = _settings(sc)
-    H, W, P = int(st.image_height), int(st.image_width), sc.means3D.shape[0]
-    args = _args(sc)
-    means, opac = _f32(sc.means3D.to(DEV), "means3D"), _f32(sc.opacities.to(DEV), "opacities")
-    cols, scales, rots = _f32(args["colors_precomp"], "c"), _f32(args["scales"], "s"), _f32(args["rotations"], "r")
     status = {}
     for value in (1, 0):
-        with _path(lib, value):
-            keep = []
-            cam = _camera(st, 0, keep, 3)
-            u8 = dict(dtype=torch.uint8, device=DEV)
-            geom = torch.zeros(lib.mgs_geometry_bytes(P), **u8)
-            img = torch.zeros(lib.mgs_image_bytes(W, H), **u8)
-            radii = torch.empty(P, dtype=torch.int32, device=DEV)
-            n_touched = torch.empty(P, dtype=torch.int32, device=DEV)
-            out = [torch.empty(c, H, W, dtype=torch.float32, device=DEV) for c in (3, 1, 1)]
-            nr = C.c_uint64(0)
-            _lib.check(lib.mgs_forward_preprocess(C.byref(cam), P, _ptr(means), None, _ptr(cols), _ptr(opac), _ptr(scales),
-                                                  _ptr(rots), None, geom.data_ptr(), radii.data_ptr(), None, C.byref(nr),
-                                                  None, None, None, _stream()), "preprocess")
-            R = int(nr.value)
-            cap = R // 2
-            binning = torch.zeros(lib.mgs_binning_bytes(cap, W, H), **u8)
-            over = torch.zeros(1, dtype=torch.int32, device=DEV)
-            _lib.check(lib.mgs_forward_render_capacity(C.byref(cam), P, cap, geom.data_ptr(), binning.data_ptr(),
-                                                       img.data_ptr(), out[0].data_ptr(), out[1].data_ptr(),
-                                                       out[2].data_ptr(), n_touched.data_ptr(), over.data_ptr(), None,
-                                                       _stream()), "render_capacity")
-            torch.cuda.synchronize()
-            assert lib.mgs_binning_path(P, W, H) == value
-            status[value] = (R, int(over.item()))
-            assert bool(torch.isfinite(out[0]).all())
+        with options(radix_scanned=value):
+            f = RawForward(_settings(sc), sc.means3D.to(DEV), sc.opacities.to(DEV), **_args(sc), zero=True)
+            R = f.preprocess()
+            f.render(R // 2, capacity=True)
+            assert native_lib.mgs_binning_path(f.P, f.W, f.H) == value
+            status[value] = (R, int(f.status.item()))
+            assert bool(torch.isfinite(f.color).all())
     assert status[1] == status[0] and status[1][1] != 0

@@ -70,8 +70,7 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("feature_bench needs a GPU: there is no CPU path and no CPU number")
     from monogs_amd import _lib
-    from monogs_amd.feature_render import _tables
-    from monogs_amd.rasterizer import _stream, collect_timing
+    from monogs_amd.rasterizer import _stream, collect_timing, forward_scratch
     lib = _lib.load()
     dev = "cuda:0"
     for wname, make in (("room_640x480", room_workload), ("scene_100k_640x480", scene_workload)):
@@ -83,13 +82,12 @@ def main():
             cols[:, :K] = feats
             triples = [cols[:, 3 * i:3 * i + 3].contiguous() for i in range(cols.shape[1] // 3)]
             color = forward(triples[0].clone().requires_grad_(True))       # the forward whose tables the feature kernels walk
-            t = _tables(color)
+            t = forward_scratch(color)
             H, W = t.H, t.W
             out = torch.empty(K, H, W, device=dev)
             d_out = (torch.rand(K, H, W, generator=g) / (H * W)).to(dev)
             d_feat = torch.empty(P, K, device=dev)
-            base = t.arena.data_ptr()
-            scratch = (base + t.geom_off, t.binning.data_ptr(), base + t.img_off)
+            scratch = t.pointers()
 
             def feat_fwd():
                 _lib.check(lib.mgs_features_forward(C.byref(t.cam), P, K, t.num_rendered, *scratch, feats.data_ptr(), None,
