@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define MGS_ABI_VERSION 22
+#define MGS_ABI_VERSION 23
 #define MGS_TILE 16 /* tile edge in pixels; ranges are per 16x16 tile */
 
 /* GaussianRasterizationSettings, minus `prefiltered` / `debug` which are call flags
@@ -862,6 +862,57 @@ typedef struct MgsStereo {
 } MgsStereo;
 size_t mgs_stereo_scratch_bytes(int32_t width, int32_t height, int32_t num_disparities);
 int mgs_stereo_depth(const MgsStereo* params, void* stream);
+
+/* ---- TSDF fusion of depth images and indexed triangle-mesh extraction (ABI v23) ---------------------------------
+ * The specification is DESIGN.md, "TSDF fusion and mesh extraction" (tests/tsdf_mirror.py restates it in float64).
+ * VOLUME: a dense grid of nx x ny x nz voxels, nx ny nz < 2^31; origin = the centre of voxel (0,0,0) in world metres, voxel =
+ * the edge; centre of (i,j,k) = origin + voxel (i,j,k); linear index (k ny + j) nx + i.  Planes: float32 tsdf (initially 1),
+ * weight (initially 0) and, all three or none, r, g, b (initially 0).  The caller owns and initialises them.
+ * mgs_tsdf_integrate fuses one frame, one launch: per voxel centre p, in float32, pc = R p + t from `viewmatrix` (the device
+ * matrix of mgs_camera.viewmatrix; never read on the host); skip if pc.z <= depth_min; pixel ix = floor(fx pc.x / pc.z + cx
+ * - 0.5 + 0.5), iy likewise, skip outside the image; d = depth[iy][ix]; with `opacity`: skip if a < opacity_min, else d = d / a;
+ * skip unless depth_min < d <= depth_max (depth_max <= 0: no upper bound); sdf = d - pc.z, skip if sdf < -trunc; f = min(1,
+ * sdf / trunc); tsdf = (tsdf W + f) / (W + 1), colour likewise from rgb[:, iy, ix] when volume and frame both have colour,
+ * weight = min(W + 1, max_weight).  Planes are touched only by voxels that reach the update.  A wave owns 64 consecutive x of
+ * one row and leaves early when the row segment's bounding sphere lies behind depth_min, outside the image or beyond depth_max +
+ * trunc (conservative: the result is bit-identical with MGS_TSDF_NO_CULL, a test flag).  No atomics, no host
+ * synchronisation, capturable in a hipGraph; bitwise reproducible.
+ * EXTRACT: marching tetrahedra (six per cell around the diagonal 000 -> 111) over the cells whose 8 corners have weight >=
+ * min_weight; inside = tsdf < 0.  mgs_tsdf_extract_count (5 launches) fills `scratch` (mgs_tsdf_extract_scratch_bytes(nx, ny,
+ * nz) bytes, pure and monotone, 256 for sizes the entry points refuse; nothing assumed on entry) and writes counts[2] = {V, T}
+ * on the device (saturating at 2^32 - 1); the caller reads them back, allocates, and calls mgs_tsdf_extract_emit (2 launches)
+ * with the same volume and scratch: vertices [V,3] float32 ordered by (owner voxel index, edge bit 0..6 = +x, +y, +z, +x+y, +y+z,
+ * +x+z, +x+y+z), colors [V,3] or NULL, triangles [T,3] int32 ordered by (cell index, tetrahedron, triangle), normals towards
+ * positive tsdf.  No store lands beyond V vertices or T triangles.  Scans are the library's own kernels; no atomics.
+ * Refused with 1 and a message before any launch: NULL volume / frame / required plane or pointer, r, g, b not all-or-none,
+ * non-positive dimensions or image size, nx ny nz >= 2^31, voxel <= 0, trunc <= 0, max_weight < 1, fx or fy <= 0, V or T >= 2^31. */
+#define MGS_TSDF_NO_CULL 1
+typedef struct mgs_tsdf_volume {
+    int32_t nx, ny, nz;
+    float origin[3];
+    float voxel;
+    float* tsdf;                  /* [nz][ny][nx] */
+    float* weight;
+    float* r;                     /* all three or none */
+    float* g;
+    float* b;
+} mgs_tsdf_volume;
+typedef struct mgs_tsdf_frame {
+    int32_t width, height;
+    const float* depth;           /* [H][W] */
+    const float* opacity;         /* [H][W] or NULL */
+    const float* rgb;             /* [3][H][W] or NULL */
+    const float* viewmatrix;      /* device, 16 floats, transposed world->camera */
+    float fx, fy, cx, cy;
+    float trunc, depth_min, depth_max, opacity_min, max_weight;
+    int32_t flags;                /* 0, or MGS_TSDF_NO_CULL */
+} mgs_tsdf_frame;
+int mgs_tsdf_integrate(const mgs_tsdf_volume* volume, const mgs_tsdf_frame* frame, void* stream);
+size_t mgs_tsdf_extract_scratch_bytes(int32_t nx, int32_t ny, int32_t nz);
+int mgs_tsdf_extract_count(const mgs_tsdf_volume* volume, float min_weight, void* scratch, uint32_t* counts /* [2] device */,
+                           void* stream);
+int mgs_tsdf_extract_emit(const mgs_tsdf_volume* volume, const void* scratch, float* vertices /* [V,3] */,
+                          float* colors /* [V,3] or NULL */, int32_t* triangles /* [T,3] */, uint32_t V, uint32_t T, void* stream);
 
 #ifdef __cplusplus
 }

@@ -21,4 +21,8 @@ def __getattr__(name):
                 "ObjectLayerTrainer", "eval_segmentation", "render_labels"):
         from . import object_layer
         return getattr(object_layer, name)
+    # TSDF fusion and mesh extraction (monogs_amd.tsdf) likewise
+    if name in ("TSDFVolume", "TriangleMesh", "fuse_map", "mesh_stats", "mesh_from_map"):
+        from . import tsdf
+        return getattr(tsdf, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -11,7 +11,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MGS_LIB_PATH") or os.path.join(_HERE, "lib", "libmonogs_raster.so")   # (override: kernel experiments)
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 c_float_p = C.c_void_p   # device pointers travel as integers (tensor.data_ptr())
 
@@ -55,6 +55,17 @@ class MgsStereo(C.Structure):
                                          "disp12_max_diff", "pre_filter_cap")] + [("bf", C.c_double)] + [
         (n, C.c_void_p) for n in ("left_u8", "right_u8", "map_lx", "map_ly", "map_rx", "map_ry", "rgb_out", "disp16_out",
                                   "depth_out", "left_rect_out", "right_rect_out", "sum_out", "scratch")]
+
+
+class MgsTsdfVolume(C.Structure):
+    _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("origin", C.c_float * 3), ("voxel", C.c_float),
+                ("tsdf", C.c_void_p), ("weight", C.c_void_p), ("r", C.c_void_p), ("g", C.c_void_p), ("b", C.c_void_p)]
+
+
+class MgsTsdfFrame(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("depth", C.c_void_p), ("opacity", C.c_void_p), ("rgb", C.c_void_p),
+                ("viewmatrix", C.c_void_p)] + [(n, C.c_float) for n in (
+                    "fx", "fy", "cx", "cy", "trunc", "depth_min", "depth_max", "opacity_min", "max_weight")] + [("flags", C.c_int32)]
 
 
 class MgsPseudoDepthParams(C.Structure):
@@ -148,6 +159,10 @@ SIGNATURES = {
     "mgs_frame_prepare": (C.c_int, [C.POINTER(MgsFramePrepare), C.c_void_p]),
     "mgs_stereo_scratch_bytes": (C.c_size_t, [C.c_int32] * 3),
     "mgs_stereo_depth": (C.c_int, [C.POINTER(MgsStereo), C.c_void_p]),
+    "mgs_tsdf_integrate": (C.c_int, [C.POINTER(MgsTsdfVolume), C.POINTER(MgsTsdfFrame), C.c_void_p]),
+    "mgs_tsdf_extract_scratch_bytes": (C.c_size_t, [C.c_int32] * 3),
+    "mgs_tsdf_extract_count": (C.c_int, [C.POINTER(MgsTsdfVolume), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mgs_tsdf_extract_emit": (C.c_int, [C.POINTER(MgsTsdfVolume)] + [C.c_void_p] * 4 + [C.c_uint32, C.c_uint32, C.c_void_p]),
 }
 
 _lib = None

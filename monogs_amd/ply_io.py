@@ -109,3 +109,77 @@ def load_ply(path: str, device="cpu") -> Dict[str, torch.Tensor]:
     if any(k.startswith("obj_prob_") for k in v):
         out["obj_prob"] = stack("obj_prob_")
     return {k: torch.from_numpy(a).to(device) for k, a in out.items()}
+
+
+# ---- triangle meshes (monogs_amd.tsdf) ------------------------------------------------------------------------------------
+def save_mesh_ply(path: str, mesh) -> None:
+    """An indexed triangle mesh (``vertices`` [V,3], ``triangles`` [T,3], ``colors`` [V,3] in 0..1 or None) as a binary
+    little-endian PLY: ``vertex`` x y z (+ uchar red green blue) and ``face`` with ``list uchar int vertex_indices`` -- the layout
+    MeshLab and Open3D read.  An empty mesh writes a valid file with zero elements."""
+    v = mesh.vertices.detach().to("cpu", torch.float32).numpy().reshape(-1, 3)
+    f = mesh.triangles.detach().to("cpu", torch.int32).numpy().reshape(-1, 3)
+    col = None if mesh.colors is None else mesh.colors.detach().to("cpu", torch.float32).numpy().reshape(-1, 3)
+    vdt = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")] + ([("red", "u1"), ("green", "u1"), ("blue", "u1")] if col is not None else [])
+    vt = np.zeros(v.shape[0], dtype=vdt)
+    vt["x"], vt["y"], vt["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if col is not None:
+        u8 = np.floor(np.clip(col, 0.0, 1.0) * 255.0 + 0.5).astype(np.uint8)
+        vt["red"], vt["green"], vt["blue"] = u8[:, 0], u8[:, 1], u8[:, 2]
+    ft = np.zeros(f.shape[0], dtype=[("n", "u1"), ("i", "<i4", (3,))])
+    ft["n"], ft["i"] = 3, f
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    header = "ply\nformat binary_little_endian 1.0\nelement vertex %d\n" % v.shape[0]
+    header += "property float x\nproperty float y\nproperty float z\n"
+    if col is not None:
+        header += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+    header += "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % f.shape[0]
+    with open(path, "wb") as fh:
+        fh.write(header.encode("ascii"))
+        fh.write(vt.tobytes())
+        fh.write(ft.tobytes())
+
+
+def load_mesh_ply(path: str, device="cpu"):
+    """The ``TriangleMesh`` of a file ``save_mesh_ply`` wrote (colours come back as uchar / 255)."""
+    from .tsdf import TriangleMesh
+    with open(path, "rb") as f:
+        if f.readline().strip() != b"ply":
+            raise ValueError(f"{path}: not a PLY file")
+        nv = nf = 0
+        props, element = [], None
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError(f"{path}: truncated header")
+            tok = line.decode("ascii").split()
+            if not tok or tok[0] == "comment":
+                continue
+            if tok[0] == "format" and tok[1] != "binary_little_endian":
+                raise ValueError(f"{path}: only binary_little_endian mesh files are read")
+            if tok[0] == "element":
+                element = tok[1]
+                if element == "vertex":
+                    nv = int(tok[2])
+                elif element == "face":
+                    nf = int(tok[2])
+            elif tok[0] == "property" and element == "vertex":
+                props.append((tok[2], "<" + _PLY_TYPES[tok[1]]))
+            elif tok[0] == "property" and element == "face":
+                if tok[1:] != ["list", "uchar", "int", "vertex_indices"]:
+                    raise ValueError(f"{path}: face property {tok[1:]} is not 'list uchar int vertex_indices'")
+            elif tok[0] == "end_header":
+                break
+        vdt = np.dtype(props)
+        vt = np.frombuffer(f.read(nv * vdt.itemsize), dtype=vdt, count=nv)
+        fdt = np.dtype([("n", "u1"), ("i", "<i4", (3,))])
+        ft = np.frombuffer(f.read(nf * fdt.itemsize), dtype=fdt, count=nf)
+    if nf and not (ft["n"] == 3).all():
+        raise ValueError(f"{path}: only triangles are read")
+    v = np.stack([vt["x"], vt["y"], vt["z"]], axis=1).astype(np.float32).reshape(-1, 3)
+    col = None
+    if "red" in vt.dtype.names:
+        col = (np.stack([vt["red"], vt["green"], vt["blue"]], axis=1).astype(np.float32) / 255.0).reshape(-1, 3)
+    return TriangleMesh(torch.from_numpy(v).to(device), torch.from_numpy(np.array(ft["i"], dtype=np.int32).reshape(-1, 3)).to(device),
+                        None if col is None else torch.from_numpy(col).to(device))

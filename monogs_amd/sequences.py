@@ -115,6 +115,22 @@ def raycast_room(R, t, k, device, with_ids=False):
     return rgb.t().reshape(3, H, W).contiguous(), best.reshape(H, W).contiguous()
 
 
+def room_surface_distance(points: torch.Tensor) -> torch.Tensor:
+    """Unsigned distance [N] of ``points`` [N,3] (world metres) to the room's surfaces: the union of its six walls and the faces of
+    the four boxes, in closed form (distance to the boundary of an axis-aligned box: outside ``|max(q, 0)|``, inside ``-max(q)``
+    with ``q = |p - centre| - half``).  Plain torch; for evaluating a reconstructed mesh, nothing on a hot path."""
+    p = points.to(torch.float64)
+    boxes = [((-_ROOM_HALF[0], -_ROOM_HALF[1], -_ROOM_HALF[2]), _ROOM_HALF)] + list(_ROOM_BOXES)
+    best = None
+    for lo, hi in boxes:
+        lo, hi = torch.tensor(lo, dtype=p.dtype, device=p.device), torch.tensor(hi, dtype=p.dtype, device=p.device)
+        q = (p - 0.5 * (lo + hi)).abs() - 0.5 * (hi - lo)
+        out = q.clamp_min(0.0).norm(dim=1)
+        d = torch.where(out > 0, out, -q.max(dim=1).values)
+        best = d if best is None else torch.minimum(best, d)
+    return best.to(points.dtype)
+
+
 def make_room_sequence(n_frames: int, intrinsics="fr3_office", device="cuda:0", step_scale: float = 1.0,
                        with_segmentation: bool = False):
     """``n_frames`` RGB-D frames of the room along a smooth hand-held-like path (about 1 cm and 0.3 degrees per frame at

@@ -294,7 +294,10 @@ def _finish(s):
     and after the refinement) and ``ate`` over the keyframes, as the reference reports them.  ``refine_iters``: that many iterations
     of ``refinement.Refiner`` over all keyframes (``refinement``).  ``eager_probe``: that many iterations of
     ``eager_probe.eager_tracking_probe`` against the final map (``eager_tracking``).  ``learn_objects``: ``objects`` = the trainer's
-    iteration count, its first and last loss and ``object_layer.eval_segmentation`` over the run's frames."""
+    iteration count, its first and last loss and ``object_layer.eval_segmentation`` over the run's frames.  ``mesh_path``: ``mesh`` =
+    the final map fused from every keyframe into a TSDF volume of ``mesh_voxel`` metres over the map's bounds and written there as a
+    triangle-mesh PLY (``tsdf.mesh_from_map``): ``path, vertices, triangles, voxel, integrate_ms, extract_ms`` and, on the synthetic
+    room, ``accuracy_mean_m`` (mean distance of the vertices to the room's true surfaces)."""
     c, frames, gmap, intr, bg, mapper, kf_list = s.c, s.frames, s.gmap, s.intr, s.bg, s.mapper, s.kf_list
     _drop_tracking_graph(s)
     extra = {}
@@ -332,6 +335,14 @@ def _finish(s):
         gc.collect()
         torch.cuda.empty_cache()
         extra["eager_tracking"] = eager_tracking_probe(frames, intr, gmap, bg, int(c.eager_probe))
+    if c.mesh_path is not None:          # (only then: tests/golden/run_slam_contract.json pins the keys of the default flags)
+        from .tsdf import mesh_from_map
+        m = mesh_from_map(gmap, [frames[k] for k in kf_list], intr, bg, float(c.mesh_voxel), path=c.mesh_path)
+        mesh = m.pop("mesh")
+        if c.sequence is None and c.scene == "room" and m["vertices"]:
+            from .sequences import room_surface_distance
+            m["accuracy_mean_m"] = float(room_surface_distance(mesh.vertices).mean())
+        extra["mesh"] = m
     return extra
 
 
@@ -390,7 +401,7 @@ def run_slam(n_frames=12, intrinsics="fr3_office", tracking_itr_num=100, mapping
              scene="cloud", reference_densify=False, eager_probe=0, exclusive_device=False,
              kf_selection="interval", check_viewpoints_overlap=False, kf_trace=None, refine_iters=0, eval_render=False,
              sequence=None, nr_objects=None, sensor="depth", viewer_dir=None, viewer_modes=("rgb",), viewer_every=0,
-             learn_objects=0):
+             learn_objects=0, mesh_path=None, mesh_voxel=0.02):
     """Tracks and maps a sequence in one process; returns tracking / mapping rates, iterations and the trajectory error (``_report``).
     Every argument is described where it acts: ``_setup``, ``_track_frame``, ``_select_keyframe``, ``_map_keyframe``, ``_map_window``,
     ``_finish`` (what follows the last frame).  ``log``: a callable that gets a line per frame.  ``sensor="monocular"`` adds the result
@@ -398,7 +409,8 @@ def run_slam(n_frames=12, intrinsics="fr3_office", tracking_itr_num=100, mapping
     ``viewer_dir``: write headless-viewer frames there (``monogs_amd.viewer``), one per mode of ``viewer_modes``, after every
     ``viewer_every``-th keyframe (0: never) and at the end; only then does the result hold a ``viewer`` entry.
     ``learn_objects=N`` (with ``nr_objects``): learn the object rows, N trainer iterations over the window after each mapping call; only
-    then does the result hold an ``objects`` entry (iterations, first and last label loss, label accuracy and mIoU)."""
+    then does the result hold an ``objects`` entry (iterations, first and last label loss, label accuracy and mIoU).
+    ``mesh_path``: write the final map's triangle mesh there (``_finish``); only then does the result hold a ``mesh`` entry."""
     s = _setup(SimpleNamespace(**locals()))              # (every argument, by name: must stay the first statement)
     for i, vp in enumerate(s.frames):
         if i == 0:

@@ -11,6 +11,8 @@ stand-in; the TUM / Replica sequences are not available offline).  Prints one JS
       # files are not read (a YAML with Dataset.sensor_type: monocular selects this by itself).  Prints both ATEs to stderr.
   python tools/slam_bench.py --config tum --room --viewer frames/ --viewer-modes rgb depth elipsoids --viewer-every 2
       # PNGs of what the reference's viewer window would show, from a camera behind the current pose (monogs_amd.viewer)
+  python tools/slam_bench.py --config tum --room --graph --mesh room.ply [--mesh-voxel 0.02]
+      # the final map fused from every keyframe into a TSDF volume and written as a coloured triangle mesh (monogs_amd.tsdf)
 """
 import argparse
 import json
@@ -73,6 +75,10 @@ if __name__ == "__main__":
                     help="with --room: an object row per Gaussian (one score per room surface), learned from the frames' surface ids, "
                          "N trainer iterations over the window after each mapping call (monogs_amd.object_layer); the result gains "
                          "`objects`: label loss, pixel accuracy and mIoU on every fifth non-keyframe")
+    ap.add_argument("--mesh", default=None, metavar="PATH",
+                    help="after the run: fuse the final map from every keyframe into a TSDF volume over the map's bounds and write the "
+                         "triangle mesh to PATH (binary PLY); the result gains `mesh`")
+    ap.add_argument("--mesh-voxel", type=float, default=0.02, help="with --mesh: the voxel edge in metres")
     a = ap.parse_args()
     from monogs_amd.slam_harness import run_slam
     cfg = dict(CONFIGS[a.config])
@@ -106,7 +112,8 @@ if __name__ == "__main__":
                    reference_lrs=a.reference_lrs, scene="room" if a.room else "cloud", reference_densify=a.reference_densify,
                    eager_probe=a.eager_probe, kf_selection=a.kf_selection, check_viewpoints_overlap=a.check_overlap,
                    refine_iters=a.refine, eval_render=a.eval, sensor=sensor, viewer_dir=a.viewer,
-                   viewer_modes=tuple(a.viewer_modes), viewer_every=a.viewer_every, log=lambda s: print("[slam]", s, file=sys.stderr, flush=True), **objects, **cfg)
+                   viewer_modes=tuple(a.viewer_modes), viewer_every=a.viewer_every, log=lambda s: print("[slam]", s, file=sys.stderr, flush=True), **objects, **cfg,
+                   **(dict(mesh_path=a.mesh, mesh_voxel=a.mesh_voxel) if a.mesh else {}))
     what = f"{a.dataset}, every {a.stride}. frame" if a.dataset else f"synthetic {a.config}-like sequence"
     out["workload"] = f"{what}, {a.frames} frames" + (" (fork's hard-coded run configuration)" if a.fork else "")
     if sensor == "monocular":
