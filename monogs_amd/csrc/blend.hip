@@ -19,8 +19,11 @@
 // No barriers; a quadrant whose pixels are all saturated retires early.
 // Skipping an instance for a whole quadrant never changes a pixel: every skipped pair has
 // alpha < 1/255 and the per-pixel rule would have skipped it too.
+// What the walkers of other files share with these (the falloff and the activity rule, the quadrant of a wave, the cull, the mask
+// table's addressing, BlendArgs) is tile_walk.h; the counting diagnostics of these walks are blend_stats.hip.
 #include "common.h"
 #include "tile_sort.h"
+#include "tile_walk.h"
 
 #include <type_traits>
 
@@ -36,10 +39,6 @@ static unsigned long long g_trace_bwd_records = 0;      // 4-word records the ba
 #define BS_STAMP(v) asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) :: "memory")
 #endif
 
-__device__ __forceinline__ uint32_t bcast(uint32_t v, int lane) {
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, lane);
-}
-
 // One 256-thread workgroup per 16x16 tile, wave w = quadrant w.  (Round 5 measured one 64-thread workgroup per (tile, quadrant),
 // launched as one contiguous band of quadrants per XCD, so that wave slots refill one by one instead of four at a time: C5
 // backward 0.335 / 0.343 against 0.345 / 0.333 ms, forward 0.190 / 0.192 against 0.194 / 0.189 -- nothing)
@@ -47,79 +46,6 @@ constexpr int MGS_WG_WAVES = 4;
 #define MGS_TILE_WAVE(ntiles_, tile_, wave_, ws_)                                                   \
     const int tile_ = (int)blockIdx.x, wave_ = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), ws_ = wave_; \
     if (tile_ >= (ntiles_)) return;
-struct BlendArgs {
-#ifdef BS_TRACE
-    unsigned long long* trace;
-#endif
-    const float4* __restrict__ rec;            // [P][4]
-    const uint32_t* __restrict__ point_list;
-    const uint2* __restrict__ ranges;
-    const float* __restrict__ bg;
-    unsigned long long* fwd_masks;             // BinningState::fwd_masks: [row][quadrant], the forward's survivor masks
-    int W, H, gx;
-};
-// Row of the mask table that step b of `tile` takes, its list starting at range_x: range_x / 64 + tile + b.  No two tiles share
-// a row: a list [x, x + n), x = 64 a + r, n = 64 c + s, takes c + (s > 0) rows from a + tile, and the next tile that has a list
-// starts at a row >= a + c + (r + s) / 64 + tile + 1 (empty tiles in between only add to `tile`).
-__device__ __forceinline__ size_t fwd_mask_word(uint32_t range_x, int tile, int wave) {
-    return ((size_t)(range_x / WAVE) + (size_t)tile) * 4 + (size_t)wave;
-}
-
-// Does the alpha >= 1/255 ellipse of an instance reach the 8x8 pixel quadrant whose first pixel is (qx0, qy0)?
-// First the padded bounding box (rejects most), then the exact minimum of the ellipse's quadratic form over the
-// quadrant rectangle: the centre is inside, or the minimum lies on one of the four edges, where the quadratic is
-// one-dimensional and its clamped minimiser is closed-form.  Conservative: threshold 1.02 instead of 1 and the
-// rectangle grown by 0.05 px, so a skipped instance has alpha < 1/255 at every pixel of the quadrant under any
-// rounding.  Runs once per lane per 64 instances, so its ~40 instructions cost < 1 per instance.
-//
-// `alive` is the wave's 64-bit mask of pixels that can still use an instance of this step (forward: not yet
-// saturated; backward: the pixel's last contributor is not in front of the step).  An instance whose cull box covers
-// no alive pixel is skipped as well -- in a dense scene most of a tile's depth range is walked for the sake of a few
-// unsaturated pixels, and most instances of those steps sit over pixels that finished long ago.  Exact: a pixel
-// outside the box has alpha < 1/255, a dead pixel ignores every instance.
-__device__ __forceinline__ bool quadrant_hit(const float4 c /* px, py, ex, ey */, const float4 n /* na, nb, nc, . */,
-                                             float qx0, float qy0, unsigned long long alive) {
-    const float x0 = qx0 - 0.05f - c.x, x1 = qx0 + (float)(SUB - 1) + 0.05f - c.x;   // rectangle relative to the centre
-    const float y0 = qy0 - 0.05f - c.y, y1 = qy0 + (float)(SUB - 1) + 0.05f - c.y;
-    if (c.z < 0.f) return false;                      // opacity < 1/255 (or an empty slot): contributes nowhere
-    if (!((c.z >= x0) && (-c.z <= x1) && (c.w >= y0) && (-c.w <= y1))) return false;   // bounding boxes apart
-    {   // pixels (qx0 + i, qy0 + j) inside the box: i in [ix0, ix1], j in [iy0, iy1] (clamped; the box may be huge or NaN-wide)
-        const int ix0 = (int)fminf(8.f, fmaxf(0.f, ceilf(-x0 - c.z - 0.06f))), ix1 = (int)fminf(7.f, fmaxf(-1.f, floorf(-x0 + c.z + 0.06f)));
-        const int iy0 = (int)fminf(8.f, fmaxf(0.f, ceilf(-y0 - c.w - 0.06f))), iy1 = (int)fminf(7.f, fmaxf(-1.f, floorf(-y0 + c.w + 0.06f)));
-        if (ix0 > ix1 || iy0 > iy1) return false;
-        const unsigned long long cols = (unsigned long long)((0xFFu >> (7 - ix1)) & (0xFFu << ix0) & 0xFFu) * 0x0101010101010101ull;
-        const unsigned long long rows = (~0ull >> (8 * (7 - iy1))) & (~0ull << (8 * iy0));
-        if ((cols & rows & alive) == 0ull) return false;
-    }
-    if (x0 <= 0.f && x1 >= 0.f && y0 <= 0.f && y1 >= 0.f) return true;                 // centre inside
-    if (!(n.x > 0.f) || !(n.z > 0.f)) return true;                                     // no ellipse data: keep
-    // v_rcp_f32 (1 ulp) instead of two IEEE divide sequences: the 2 % threshold margin dwarfs the error
-    const float rby = -n.y * __builtin_amdgcn_rcpf(n.z), rbx = -n.y * __builtin_amdgcn_rcpf(n.x);
-    auto edge_x = [&](float xe) {          // x = xe, y in [y0, y1]
-        const float t = fminf(y1, fmaxf(y0, rby * xe));
-        return n.x * xe * xe + 2.f * n.y * xe * t + n.z * t * t;
-    };
-    auto edge_y = [&](float ye) {          // y = ye, x in [x0, x1]
-        const float t = fminf(x1, fmaxf(x0, rbx * ye));
-        return n.x * t * t + 2.f * n.y * t * ye + n.z * ye * ye;
-    };
-    const float qmin = fminf(fminf(edge_x(x0), edge_x(x1)), fminf(edge_y(y0), edge_y(y1)));
-    return qmin <= 1.02f;
-}
-
-// the survivor's record through the scalar cache (wave-uniform address -> s_load)
-struct Rec {
-    float px, py, ca, cb, cc, op, r, g, b, z;
-};
-// Read through the CONSTANT address space (common.h): the backend then always selects scalar loads for the wave-uniform
-// address (s_load_dwordx2 + s_load_dwordx8).  Through the generic pointer that choice hangs on a no-clobber analysis that
-// flips to per-lane vector loads with unrelated edits of the loop (an atomic moved, an LDS store added).  The records
-// are written by preprocess, an earlier kernel.
-__device__ __forceinline__ Rec fetch(const BlendArgs& a, uint32_t gid_uniform) {
-    const const_float_p p = MGS_CONST(reinterpret_cast<const float*>(a.rec)) + (size_t)gid_uniform * REC_FLOATS;
-    return Rec{p[R_X], p[R_Y], p[R_CA], p[R_CB], p[R_CC], p[R_OPAC], p[R_R], p[R_G], p[R_B], p[R_DEPTH]};
-}
-
 // One survivor against the 64 pixels of the quadrant.  Round 3: the per-pixel decisions narrow EXEC instead of building
 // lane masks on the scalar unit -- the kernel was bound by the compute unit's ONE scalar ALU (24 scalar instructions per
 // survivor from each of four SIMDs against 28 vector ones; r03 PMC: 86 M SALU + 124 M VALU per launch at C5):
@@ -163,7 +89,7 @@ __device__ __forceinline__ void blend_one(unsigned long long& live, unsigned lon
             "v_writelane_b32 %[tc], %[cnt], m0\n\t"
             : [live] "+s"(live), [mask] "+s"(mask), [T] "+v"(T), [last] "+v"(last), [C0] "+v"(C0), [C1] "+v"(C1), [C2] "+v"(C2), [D] "+v"(D),
               [w] "=&v"(w), [cnt] "=&s"(cnt), [tc] "+v"(touched_cnt)
-            : [power] "v"(power), [alpha] "v"(alpha), [tt] "v"(test_T), [amin] "s"(1.0f / 255.0f), [tmin] "s"(0.0001f),
+            : [power] "v"(power), [alpha] "v"(alpha), [tt] "v"(test_T), [amin] "s"(ALPHA_MIN), [tmin] "s"(T_MIN),
               [pos] "s"(pos), [cr] "v"(g.r), [cg] "v"(g.g), [cb] "v"(g.b), [cz] "v"(g.z), [j] "s"(j)
             : "vcc", "scc", "m0");
     } else {
@@ -185,7 +111,7 @@ __device__ __forceinline__ void blend_one(unsigned long long& live, unsigned lon
             "s_mov_b64 exec, -1\n\t"
             : [live] "+s"(live), [mask] "+s"(mask), [T] "+v"(T), [last] "+v"(last), [C0] "+v"(C0), [C1] "+v"(C1), [C2] "+v"(C2), [D] "+v"(D),
               [w] "=&v"(w)
-            : [power] "v"(power), [alpha] "v"(alpha), [tt] "v"(test_T), [amin] "s"(1.0f / 255.0f), [tmin] "s"(0.0001f),
+            : [power] "v"(power), [alpha] "v"(alpha), [tt] "v"(test_T), [amin] "s"(ALPHA_MIN), [tmin] "s"(T_MIN),
               [pos] "s"(pos), [cr] "v"(g.r), [cg] "v"(g.g), [cb] "v"(g.b), [cz] "v"(g.z)
             : "vcc", "scc");
     }
@@ -224,6 +150,8 @@ __global__ void __launch_bounds__(256) blend_forward_kernel(BlendArgs a, float* 
             for (int i = (int)threadIdx.x; i < n4; i += 256) base[i] = make_float4(0.f, 0.f, 0.f, 0.f);
         }
     }
+    // (the quadrant: MGS_QUADRANT_FILL's lines (tile_walk.h), written out -- through the macro <false> comes out with two
+    //  instructions of its set-up in the other order)
     const int tx = tile % a.gx, ty = tile / a.gx;
     const int lane = threadIdx.x & 63;
     const bool first_of_tile = wave == 0 && lane == 0;
@@ -325,8 +253,8 @@ __global__ void __launch_bounds__(256) blend_forward_kernel(BlendArgs a, float* 
             asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(e0));
             float dx = e0[0] - pxf, dy = e0[1] - pyf;
             asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(e1), "+v"(dx), "+v"(dy));      // (dx, dy tied in: formed BEFORE this wait)
-            const float power = dx * (e1[0] * dx + e1[1] * dy) + (e1[2] * dy) * dy;     // log2 of the Gaussian falloff
-            float alpha = fminf(0.99f, e1[3] * __builtin_amdgcn_exp2f(power));
+            const float power = falloff_power(dx, dy, e1[0], e1[1], e1[2]);
+            float alpha = falloff_alpha(e1[3], __builtin_amdgcn_exp2f(power));
             asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(e2), "+v"(alpha));             // (alpha formed BEFORE the colour is waited for)
             const Rec g{e0[0], e0[1], e1[0], e1[1], e1[2], e1[3], e2[0], e2[1], e2[2], e2[3]};
             // (also: mask = 0 once no pixel of the quadrant is live -- the walk's only exit test stays `mask != 0`)
@@ -379,23 +307,6 @@ __global__ void __launch_bounds__(256) blend_forward_kernel(BlendArgs a, float* 
         out_depth[pix] = D;
         out_opacity[pix] = 1.f - T;
     }
-}
-
-static BlendArgs make_args(const mgs_camera& cam, const GeometryState& g, const BinningState& b,
-                           const ImageState& img) {
-    BlendArgs a;
-#ifdef BS_TRACE
-    a.trace = nullptr;
-#endif
-    a.rec = reinterpret_cast<const float4*>(g.rec);
-    a.point_list = b.vals_sorted;
-    a.ranges = img.ranges;
-    a.bg = cam.bg;
-    a.fwd_masks = b.fwd_masks;
-    a.W = cam.image_width;
-    a.H = cam.image_height;
-    a.gx = tiles_x(a.W);
-    return a;
 }
 
 int launch_blend_forward(const mgs_camera& cam, const GeometryState& g, const BinningState& b,
@@ -501,12 +412,6 @@ __device__ __forceinline__ float reduce6(float a0, float a1, float a2, float a3,
     return (lane & 15) == 15 ? c0 : c1;
 }
 
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o, 64));
-    return v;
-}
-
 // POSE_ONLY: the caller wants no gradient for colours / opacities (pose tracking against a fixed map): the colour and
 //            opacity sums are neither formed nor reduced -- 6 values instead of 10 through the wave reduction.
 // (Round 2 measured a batched reduction staged through LDS -- permlane32 swap, one ds_write_b32 per register pair, a
@@ -526,24 +431,21 @@ __global__ void __launch_bounds__(256) blend_backward_kernel(BlendArgs a, int nt
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int tile = (int)blockIdx.x;
     if (tile >= ntiles) return;
-    const int tx = tile % a.gx, ty = tile / a.gx;
     const uint2 range = a.ranges[tile];
     if (range.y <= range.x) return;
     const size_t HW = (size_t)a.H * a.W;
     const float bg0 = a.bg[0], bg1 = a.bg[1], bg2 = a.bg[2];
 
     // per-pixel state
-    const int qx0i = tx * TILE + (wave & 1) * SUB, qy0i = ty * TILE + (wave >> 1) * SUB;
-    const int pxi = qx0i + (lane & 7), pyi = qy0i + (lane >> 3);
-    const bool inside = pxi < a.W && pyi < a.H;
-    const size_t pix = (size_t)pyi * a.W + pxi;
-    const float pxf = (float)pxi, pyf = (float)pyi, qx0 = (float)qx0i, qy0 = (float)qy0i;
-    const float T_final = inside ? final_T[pix] : 0.f;
-    const uint32_t last = inside ? n_contrib[pix] : 0u;
-    const float g0 = inside ? dL_dcolor[pix] : 0.f;
-    const float g1 = inside ? dL_dcolor[HW + pix] : 0.f;
-    const float g2 = inside ? dL_dcolor[2 * HW + pix] : 0.f;
-    const float gd = inside ? dL_ddepth[pix] : 0.f;
+    Quadrant quad;
+    MGS_QUADRANT_FILL(quad, a, tile, wave, lane);
+    const float qx0 = quad.qx0(), qy0 = quad.qy0();
+    const float T_final = quad.inside ? final_T[quad.pix] : 0.f;
+    const uint32_t last = quad.inside ? n_contrib[quad.pix] : 0u;
+    const float g0 = quad.inside ? dL_dcolor[quad.pix] : 0.f;
+    const float g1 = quad.inside ? dL_dcolor[HW + quad.pix] : 0.f;
+    const float g2 = quad.inside ? dL_dcolor[2 * HW + quad.pix] : 0.f;
+    const float gd = quad.inside ? dL_ddepth[quad.pix] : 0.f;
     const float bgT = -T_final * (bg0 * g0 + bg1 * g1 + bg2 * g2);   // background term, per pixel
     // T: transmittance in front of the instance being processed.  Bk: sum over channels of (colour blended BEHIND the
     // instance) * dL/dpixel -- the recursion  Bk <- alpha q + (1 - alpha) Bk  folded over the instances already
@@ -584,12 +486,12 @@ __global__ void __launch_bounds__(256) blend_backward_kernel(BlendArgs a, int nt
             const int j = 63 - __builtin_clzll(mask);
             mask &= ~(1ull << j);
             const uint32_t gid = bcast(gid_l, j);
-            const Rec g = fetch(a, gid);
-            const float dx = g.px - pxf, dy = g.py - pyf;
-            const float power = dx * (g.ca * dx + g.cb * dy) + (g.cc * dy) * dy;   // log2 of the Gaussian falloff
+            const Rec g = fetch(reinterpret_cast<const float*>(a.rec), gid);
+            const float dx = g.px - quad.pxf, dy = g.py - quad.pyf;
+            const float power = falloff_power(dx, dy, g.ca, g.cb, g.cc);
             const float G = __builtin_amdgcn_exp2f(power);
-            const float alpha = fminf(0.99f, g.op * G);
-            const bool act = (j <= rel_last) && !(power > 0.f) && !(alpha < 1.0f / 255.0f);
+            const float alpha = falloff_alpha(g.op, G);
+            const bool act = falloff_active(j <= rel_last, power, alpha);
             if (__builtin_amdgcn_ballot_w64(act) == 0ull) continue;
             // Everything below runs for all 64 lanes; an inactive lane has alpha = 0: it contributes exact zeros
             // (w = 0, h = 0) and its state passes through (T * rcp(1) = T, Bk + 0 * diff = Bk).
@@ -830,24 +732,22 @@ __global__ void __launch_bounds__(256) blend_backward_t_kernel(BlendArgs a, int 
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
     const int tile = (int)blockIdx.x;
     if (tile >= ntiles) return;
-    const int tx = tile % a.gx, ty = tile / a.gx;
     const uint2 range = a.ranges[tile];
     if (range.y <= range.x) return;
     const size_t HW = (size_t)a.H * a.W;
     const float bg0 = a.bg[0], bg1 = a.bg[1], bg2 = a.bg[2];
 
     // per-pixel state (lane = pixel of the 8x8 quadrant, as in blend_backward_kernel)
-    const int qx0i = tx * TILE + (wave & 1) * SUB, qy0i = ty * TILE + (wave >> 1) * SUB;
-    const int pxi = qx0i + (lane & 7), pyi = qy0i + (lane >> 3);
-    const bool inside = pxi < a.W && pyi < a.H;
-    const size_t pix = (size_t)pyi * a.W + pxi;
-    const float pxf = (float)pxi, pyf = (float)pyi, qx0 = (float)qx0i, qy0 = (float)qy0i;
-    const float T_final = inside ? final_T[pix] : 0.f;
-    const uint32_t last = inside ? n_contrib[pix] : 0u;
-    const float g0 = inside ? dL_dcolor[pix] : 0.f;
-    const float g1 = inside ? dL_dcolor[HW + pix] : 0.f;
-    const float g2 = inside ? dL_dcolor[2 * HW + pix] : 0.f;
-    const float gd = inside ? dL_ddepth[pix] : 0.f;
+    Quadrant quad;
+    MGS_QUADRANT_FILL(quad, a, tile, wave, lane);
+    const float qx0 = quad.qx0(), qy0 = quad.qy0();
+    const bool inside = quad.inside;         // (a copy: read from the struct each time, the six guarded loads below are merged otherwise)
+    const float T_final = inside ? final_T[quad.pix] : 0.f;
+    const uint32_t last = inside ? n_contrib[quad.pix] : 0u;
+    const float g0 = inside ? dL_dcolor[quad.pix] : 0.f;
+    const float g1 = inside ? dL_dcolor[HW + quad.pix] : 0.f;
+    const float g2 = inside ? dL_dcolor[2 * HW + quad.pix] : 0.f;
+    const float gd = inside ? dL_ddepth[quad.pix] : 0.f;
     const float bgT = -T_final * (bg0 * g0 + bg1 * g1 + bg2 * g2);
     float T = T_final, Bk = 0.f;
     const uint32_t maxc = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max_u32(last));   // wave-uniform, in an SGPR
@@ -856,7 +756,7 @@ __global__ void __launch_bounds__(256) blend_backward_t_kernel(BlendArgs a, int 
 
     // the turned-round view: row = slot of the batch, lane q of the row = pixels 4q .. 4q+3 of the quadrant
     const int q = lane & 15;
-    const int fxi = qx0i + 4 * (q & 1), fyi = qy0i + (q >> 1);
+    const int fxi = quad.qx0i + 4 * (q & 1), fyi = quad.qy0i + (q >> 1);
     // dL/dpixel of the lane's four pixels, constants of the launch, live in LDS, [channel][q][pixel] (pose-only: depth only)
     // -- in registers they pushed the kernel past 64 VGPRs -- and come back with four (one) broadcast ds_read_b128 per batch:
     // the four rows read the same addresses.
@@ -905,7 +805,7 @@ __global__ void __launch_bounds__(256) blend_backward_t_kernel(BlendArgs a, int 
         // one survivor: its two per-pixel factors into slot k of the batch (lane = pixel); whose they are -- centre and index
         // of the Gaussian -- is noted by lane j, which has held all three in registers since it loaded instance j's cull box
         auto apply = [&](const Rec& g, int j, float power, float G, float alpha) {
-            const bool act = (k_first + (uint32_t)j <= last) && !(power > 0.f) && !(alpha < 1.0f / 255.0f);
+            const bool act = falloff_active(k_first + (uint32_t)j <= last, power, alpha);
             if (__builtin_amdgcn_ballot_w64(act) == 0ull) return;
             const float a_eff = act ? alpha : 0.f;
             const float inv = __builtin_amdgcn_rcpf(1.f - a_eff);    // (an IEEE divide changes no gradient digit: tools/grad_accuracy.py)
@@ -928,11 +828,11 @@ __global__ void __launch_bounds__(256) blend_backward_t_kernel(BlendArgs a, int 
         while (mask) {
             const int j = 63 - __builtin_clzll(mask);
             mask &= ~(1ull << j);
-            const Rec g = fetch(a, bcast(gid_l, j));
-            const float dx = g.px - pxf, dy = g.py - pyf;
-            const float power = dx * (g.ca * dx + g.cb * dy) + (g.cc * dy) * dy;
+            const Rec g = fetch(reinterpret_cast<const float*>(a.rec), bcast(gid_l, j));
+            const float dx = g.px - quad.pxf, dy = g.py - quad.pyf;
+            const float power = falloff_power(dx, dy, g.ca, g.cb, g.cc);
             const float G = __builtin_amdgcn_exp2f(power);
-            apply(g, j, power, G, fminf(0.99f, g.op * G));
+            apply(g, j, power, G, falloff_alpha(g.op, G));
         }
     }
     if (k) bt_flush<POSE_ONLY>(bl, k);
@@ -1005,6 +905,8 @@ __device__ __forceinline__ void bs_walk(const BlendArgs& a, const int tile, cons
     if (range.y <= range.x) return;
     const size_t HW = (size_t)a.H * a.W;
 
+    // (the quadrant: MGS_QUADRANT_FILL's lines (tile_walk.h), written out -- through the macro the split instantiations schedule
+    //  the tile's division and the quadrant's origin differently)
     const int qx0i = tx * TILE + (wave & 1) * SUB, qy0i = ty * TILE + (wave >> 1) * SUB;
     const int pxi = qx0i + (lane & 7), pyi = qy0i + (lane >> 3);
     const bool inside = pxi < a.W && pyi < a.H;
@@ -1122,15 +1024,15 @@ __device__ __forceinline__ void bs_walk(const BlendArgs& a, const int tile, cons
                     "v_mul_f32_e32 %[t2], %[cc], %[dy]\n\t"
                     "v_fmac_f32_e32 %[t1], %[ca], %[dx]\n\t"
                     "v_mul_f32_e32 %[t2], %[dy], %[t2]\n\t"
-                    "v_fmac_f32_e32 %[t2], %[dx], %[t1]\n\t"               // power (log2 of the falloff), as the other kernels form it
+                    "v_fmac_f32_e32 %[t2], %[dx], %[t1]\n\t"               // falloff_power (tile_walk.h), in its order               
                     "v_exp_f32_e32 %[G], %[t2]\n\t"
                     "s_add_u32 %[tmp], %[wbase], %[koff]\n\t"               // the open slot
                     "v_lshl_add_u32 %[sa], %[lane], 2, %[tmp]\n\t"           // this lane's word of it
                     "ds_write2st64_b32 %[sa], %[zero], %[zero] offset1:5\n\t"   // the slot's h and w of every pixel <- 0 (full EXEC)
                     "v_cmpx_le_i32_e32 vcc, %[j], %[thr]\n\t"              // EXEC: pixels whose last contributor is not in front of j
-                    "v_cmpx_nlt_f32_e32 vcc, 0, %[t2]\n\t"                 //       and power <= 0
+                    "v_cmpx_nlt_f32_e32 vcc, 0, %[t2]\n\t"                 //       and falloff_active (tile_walk.h): power <= 0
                     "v_mul_f32_e32 %[al], %[op], %[G]\n\t"
-                    "v_min_f32_e32 %[al], 0x3f7d70a4, %[al]\n\t"           // min(0.99, opacity G)
+                    "v_min_f32_e32 %[al], 0x3f7d70a4, %[al]\n\t"           // falloff_alpha: min(ALPHA_MAX, opacity G)
                     "v_cmpx_ngt_f32_e32 vcc, %[amin], %[al]\n\t"           //       and alpha >= 1/255
                     "v_sub_f32_e32 %[t1], 1.0, %[al]\n\t"
                     "v_rcp_f32_e32 %[inv], %[t1]\n\t"
@@ -1156,7 +1058,7 @@ __device__ __forceinline__ void bs_walk(const BlendArgs& a, const int tile, cons
                     : [px] "s"(r0[0]), [py] "s"(r0[1]), [ca] "s"(r1[0]), [cb] "s"(r1[1]), [cc] "s"(r1[2]), [op] "s"(r1[3]),
                       [cr] "s"(r1[4]), [cg] "s"(r1[5]), [cb2] "s"(r1[6]), [cz] "s"(r1[7]), [pxf] "v"(pxf), [pyf] "v"(pyf), [thr] "v"(thr),
                       [j] "s"(j), [g0] "v"(g0), [g1] "v"(g1), [g2] "v"(g2), [gd] "v"(gd), [lane] "v"(lane), [zero] "v"(zero),
-                      [koff] "s"(koff), [wbase] "s"(wbase), [meta] "v"(meta), [amin] "s"(1.0f / 255.0f)
+                      [koff] "s"(koff), [wbase] "s"(wbase), [meta] "v"(meta), [amin] "s"(ALPHA_MIN)
                     : "vcc", "scc", "memory");
                 else
                 asm volatile(
@@ -1166,15 +1068,15 @@ __device__ __forceinline__ void bs_walk(const BlendArgs& a, const int tile, cons
                     "v_mul_f32_e32 %[t2], %[cc], %[dy]\n\t"
                     "v_fmac_f32_e32 %[t1], %[ca], %[dx]\n\t"
                     "v_mul_f32_e32 %[t2], %[dy], %[t2]\n\t"
-                    "v_fmac_f32_e32 %[t2], %[dx], %[t1]\n\t"               // power (log2 of the falloff), as the other kernels form it
+                    "v_fmac_f32_e32 %[t2], %[dx], %[t1]\n\t"               // falloff_power (tile_walk.h), in its order               
                     "v_exp_f32_e32 %[G], %[t2]\n\t"
                     "s_add_u32 %[tmp], %[wbase], %[koff]\n\t"               // the open slot
                     "v_lshl_add_u32 %[sa], %[lane], 2, %[tmp]\n\t"           // this lane's word of it
                     "ds_write2st64_b32 %[sa], %[zero], %[zero] offset1:5\n\t"   // the slot's h and w of every pixel <- 0 (full EXEC)
                     "v_cmpx_ge_i32_e32 vcc, %[j], %[thr]\n\t"              // EXEC: pixels whose last contributor is not in front of j
-                    "v_cmpx_nlt_f32_e32 vcc, 0, %[t2]\n\t"                 //       and power <= 0
+                    "v_cmpx_nlt_f32_e32 vcc, 0, %[t2]\n\t"                 //       and falloff_active (tile_walk.h): power <= 0
                     "v_mul_f32_e32 %[al], %[op], %[G]\n\t"
-                    "v_min_f32_e32 %[al], 0x3f7d70a4, %[al]\n\t"           // min(0.99, opacity G)
+                    "v_min_f32_e32 %[al], 0x3f7d70a4, %[al]\n\t"           // falloff_alpha: min(ALPHA_MAX, opacity G)
                     "v_cmpx_ngt_f32_e32 vcc, %[amin], %[al]\n\t"           //       and alpha >= 1/255
                     "v_sub_f32_e32 %[inv], 1.0, %[al]\n\t"
                     "v_rcp_f32_e32 %[inv], %[inv]\n\t"
@@ -1201,7 +1103,7 @@ __device__ __forceinline__ void bs_walk(const BlendArgs& a, const int tile, cons
                     : [px] "s"(r0[0]), [py] "s"(r0[1]), [ca] "s"(r1[0]), [cb] "s"(r1[1]), [cc] "s"(r1[2]), [op] "s"(r1[3]),
                       [cr] "s"(r1[4]), [cg] "s"(r1[5]), [cb2] "s"(r1[6]), [cz] "s"(r1[7]), [pxf] "v"(pxf), [pyf] "v"(pyf), [thr] "v"(thr),
                       [j] "s"(j), [g0] "v"(g0), [g1] "v"(g1), [g2] "v"(g2), [gd] "v"(gd), [bgT] "v"(bgT), [lane] "v"(lane), [zero] "v"(zero),
-                      [koff] "s"(koff), [wbase] "s"(wbase), [meta] "v"(meta), [amin] "s"(1.0f / 255.0f)
+                      [koff] "s"(koff), [wbase] "s"(wbase), [meta] "v"(meta), [amin] "s"(ALPHA_MIN)
                     : "vcc", "scc", "memory");
                 koff += adv;
             if (koff == BT_SLOTS * BS_STRIDE) {
@@ -1283,233 +1185,6 @@ __global__ void __launch_bounds__(256) blend_backward_s_kernel(BlendArgs a, int 
     }
 }
 
-// ---- diagnostic: what the backward walk does, counted (not on the hot path; mgs_debug_blend_stats) --------------
-// The same walk, cull and per-pixel activity test as blend_backward_kernel<1, *>, with counters instead of gradient
-// arithmetic: stats[0] steps of 64 instances, [1] instances that pass the quadrant cull and are fetched ("survivors"),
-// [2] survivors with at least one active pixel ("active survivors" = wave reductions = atomic instructions),
-// [3] active (pixel, instance) pairs, [4] inactive survivors whose cull box holds no pixel with k <= last (depth
-// order, not geometry), [5..7] active survivors with <= 2 / <= 4 / <= 8 active pixels.
-__global__ void __launch_bounds__(256) blend_backward_stats_kernel(BlendArgs a, int ntiles,
-                                                                   const uint32_t* __restrict__ n_contrib,
-                                                                   unsigned long long* __restrict__ stats) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int tile = (int)blockIdx.x;
-    if (tile >= ntiles) return;
-    const int tx = tile % a.gx, ty = tile / a.gx;
-    const uint2 range = a.ranges[tile];
-    if (range.y <= range.x) return;
-    const int qx0i = tx * TILE + (wave & 1) * SUB, qy0i = ty * TILE + (wave >> 1) * SUB;
-    const int pxi = qx0i + (lane & 7), pyi = qy0i + (lane >> 3);
-    const bool inside = pxi < a.W && pyi < a.H;
-    const float pxf = (float)pxi, pyf = (float)pyi, qx0 = (float)qx0i, qy0 = (float)qy0i;
-    const uint32_t last = inside ? n_contrib[(size_t)pyi * a.W + pxi] : 0u;
-    const uint32_t maxc = wave_max_u32(last);
-    if (maxc == 0) return;
-    const uint32_t end = range.x + maxc;
-    unsigned long long c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int b = (int)((maxc - 1) / WAVE); b >= 0; --b) {
-        const uint32_t i = range.x + (uint32_t)b * WAVE + lane;
-        uint32_t gid_l = 0;
-        float4 box = make_float4(0.f, 0.f, -1.f, -1.f), el = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (i < end) {
-            gid_l = a.point_list[i];
-            box = a.rec[(size_t)gid_l * 4];
-            el = a.rec[(size_t)gid_l * 4 + 3];
-        }
-        const unsigned long long alive = __builtin_amdgcn_ballot_w64(last >= (uint32_t)b * WAVE + 1u);
-        unsigned long long mask = __builtin_amdgcn_ballot_w64(quadrant_hit(box, el, qx0, qy0, alive));
-        c[0] += 1;
-        c[1] += __popcll(mask);
-        while (mask) {
-            const int j = 63 - __builtin_clzll(mask);
-            mask &= ~(1ull << j);
-            const uint32_t k = (uint32_t)b * WAVE + (uint32_t)j + 1u;
-            const Rec g = fetch(a, bcast(gid_l, j));
-            const float dx = g.px - pxf, dy = g.py - pyf;
-            const float power = dx * (g.ca * dx + g.cb * dy) + (g.cc * dy) * dy;
-            const float alpha = fminf(0.99f, g.op * __builtin_amdgcn_exp2f(power));
-            const bool geo = !(power > 0.f) && !(alpha < 1.0f / 255.0f);
-            const unsigned long long act = __builtin_amdgcn_ballot_w64(geo && k <= last);
-            const int n = __popcll(act);
-            if (n == 0) {
-                if (__builtin_amdgcn_ballot_w64(geo) != 0ull) c[4] += 1;
-                continue;
-            }
-            c[2] += 1;
-            c[3] += n;
-            c[5] += n <= 2;
-            c[6] += n <= 4;
-            c[7] += n <= 8;
-        }
-    }
-    if (lane < 8) {
-        unsigned long long v = c[0];
-#pragma unroll
-        for (int q = 1; q < 8; ++q) v = lane == q ? c[q] : v;
-        atomicAdd(stats + lane, v);
-    }
-}
-
-// ---- diagnostic, round 5: how many loop trips would the walk take if the wave ran SEVERAL survivor streams side by side,
-// one per group of pixels?  39 of a survivor's 64 lanes are active on average (stats[3] / stats[2]) and narrowing EXEC saves
-// no time on gfx950, so the only way to use the idle lanes is to give them another survivor.  For five ways of cutting the
-// 8x8 quadrant into groups (two 8x4 halves, two 4x8 halves, four 4x4 blocks, four 8x2 strips, eight 4x2 blocks) the cull is
-// run per group (the same box + ellipse test against the group's rectangle and its alive pixels) and three sums are kept:
-//   [8 + 3 d + 0]  sum over steps of max_g S_g      trips when the groups' lists are paired step by step
-//   [8 + 3 d + 1]  sum over steps of sum_g S_g      (group, survivor) rows: what the backward would have to flush
-//   [8 + 3 d + 2]  sum over walks of max_g sum_steps S_g   trips when every group runs down a list of its own
-// to be read against stats[1] (survivors of the whole-quadrant cull = trips now).
-__device__ __forceinline__ bool rect_hit(const float4 c, const float4 n, float qx0, float qy0, int ox, int oy, int w, int h,
-                                         unsigned long long alive) {
-    if (c.z < 0.f) return false;
-    const float x0q = qx0 - 0.05f - c.x, y0q = qy0 - 0.05f - c.y;                      // quadrant origin relative to the centre
-    const float x0 = x0q + (float)ox, x1 = qx0 + (float)(ox + w - 1) + 0.05f - c.x;   // the group's rectangle
-    const float y0 = y0q + (float)oy, y1 = qy0 + (float)(oy + h - 1) + 0.05f - c.y;
-    if (!((c.z >= x0) && (-c.z <= x1) && (c.w >= y0) && (-c.w <= y1))) return false;
-    {
-        const int ix0 = (int)fminf(8.f, fmaxf(0.f, ceilf(-x0q - c.z - 0.06f))), ix1 = (int)fminf(7.f, fmaxf(-1.f, floorf(-x0q + c.z + 0.06f)));
-        const int iy0 = (int)fminf(8.f, fmaxf(0.f, ceilf(-y0q - c.w - 0.06f))), iy1 = (int)fminf(7.f, fmaxf(-1.f, floorf(-y0q + c.w + 0.06f)));
-        if (ix0 > ix1 || iy0 > iy1) return false;
-        const unsigned long long cols = (unsigned long long)((0xFFu >> (7 - ix1)) & (0xFFu << ix0) & 0xFFu) * 0x0101010101010101ull;
-        const unsigned long long rows = (~0ull >> (8 * (7 - iy1))) & (~0ull << (8 * iy0));
-        const unsigned long long gcols = (unsigned long long)(((1u << w) - 1u) << ox) * 0x0101010101010101ull;
-        const unsigned long long grows = ((h >= 8 ? ~0ull : ((1ull << (8 * h)) - 1ull)) << (8 * oy));
-        if ((cols & rows & gcols & grows & alive) == 0ull) return false;
-    }
-    if (x0 <= 0.f && x1 >= 0.f && y0 <= 0.f && y1 >= 0.f) return true;
-    if (!(n.x > 0.f) || !(n.z > 0.f)) return true;
-    const float rby = -n.y * __builtin_amdgcn_rcpf(n.z), rbx = -n.y * __builtin_amdgcn_rcpf(n.x);
-    auto edge_x = [&](float xe) { const float t = fminf(y1, fmaxf(y0, rby * xe)); return n.x * xe * xe + 2.f * n.y * xe * t + n.z * t * t; };
-    auto edge_y = [&](float ye) { const float t = fminf(x1, fmaxf(x0, rbx * ye)); return n.x * t * t + 2.f * n.y * t * ye + n.z * ye * ye; };
-    return fminf(fminf(edge_x(x0), edge_x(x1)), fminf(edge_y(y0), edge_y(y1))) <= 1.02f;
-}
-__global__ void __launch_bounds__(256) blend_group_stats_kernel(BlendArgs a, int ntiles, const uint32_t* __restrict__ n_contrib,
-                                                                unsigned long long* __restrict__ stats) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int tile = (int)blockIdx.x;
-    if (tile >= ntiles) return;
-    const int tx = tile % a.gx, ty = tile / a.gx;
-    const uint2 range = a.ranges[tile];
-    if (range.y <= range.x) return;
-    const int qx0i = tx * TILE + (wave & 1) * SUB, qy0i = ty * TILE + (wave >> 1) * SUB;
-    const int pxi = qx0i + (lane & 7), pyi = qy0i + (lane >> 3);
-    const bool inside = pxi < a.W && pyi < a.H;
-    const float qx0 = (float)qx0i, qy0 = (float)qy0i;
-    const uint32_t last = inside ? n_contrib[(size_t)pyi * a.W + pxi] : 0u;
-    const uint32_t maxc = wave_max_u32(last);
-    if (maxc == 0) return;
-    const uint32_t end = range.x + maxc;
-    // decomposition d: NG[d] groups of GW[d] x GH[d] pixels, GX[d] groups per row of groups
-    constexpr int ND = 5;
-    constexpr int NG[ND] = {2, 2, 4, 4, 8}, GW[ND] = {8, 4, 4, 8, 4}, GH[ND] = {4, 8, 4, 2, 2}, GX[ND] = {1, 2, 2, 1, 2};
-    unsigned long long trips_step[ND] = {0, 0, 0, 0, 0}, rows[ND] = {0, 0, 0, 0, 0};
-    uint32_t walk[ND][8];
-#pragma unroll
-    for (int d = 0; d < ND; ++d)
-#pragma unroll
-        for (int g = 0; g < 8; ++g) walk[d][g] = 0;
-    for (int b = (int)((maxc - 1) / WAVE); b >= 0; --b) {
-        const uint32_t i = range.x + (uint32_t)b * WAVE + lane;
-        float4 box = make_float4(0.f, 0.f, -1.f, -1.f), el = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (i < end) {
-            const uint32_t gid_l = a.point_list[i];
-            box = a.rec[(size_t)gid_l * 4];
-            el = a.rec[(size_t)gid_l * 4 + 3];
-        }
-        const unsigned long long alive = __builtin_amdgcn_ballot_w64(last >= (uint32_t)b * WAVE + 1u);
-#pragma unroll
-        for (int d = 0; d < ND; ++d) {
-            int mx = 0, sum = 0;
-#pragma unroll
-            for (int g = 0; g < NG[d]; ++g) {
-                const int ox = (g % GX[d]) * GW[d], oy = (g / GX[d]) * GH[d];
-                const int n = __popcll(__builtin_amdgcn_ballot_w64(rect_hit(box, el, qx0, qy0, ox, oy, GW[d], GH[d], alive)));
-                mx = max(mx, n);
-                sum += n;
-                walk[d][g] += (uint32_t)n;
-            }
-            trips_step[d] += mx;
-            rows[d] += sum;
-        }
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int d = 0; d < ND; ++d) {
-            uint32_t mx = 0;
-#pragma unroll
-            for (int g = 0; g < NG[d]; ++g) mx = max(mx, walk[d][g]);
-            atomicAdd(stats + 8 + 3 * d + 0, trips_step[d]);
-            atomicAdd(stats + 8 + 3 * d + 1, rows[d]);
-            atomicAdd(stats + 8 + 3 * d + 2, (unsigned long long)mx);
-        }
-    }
-}
-
-int launch_blend_backward_stats(const mgs_camera& cam, const GeometryState& g, const BinningState& b,
-                                const ImageState& img, unsigned long long* stats, hipStream_t s) {
-    const BlendArgs a = make_args(cam, g, b, img);
-    const int ntiles = a.gx * tiles_y(a.H);
-    if (ntiles == 0) return 0;
-    hipLaunchKernelGGL(blend_backward_stats_kernel, dim3(ntiles), dim3(256), 0, s, a, ntiles, img.n_contrib, stats);
-    hipLaunchKernelGGL(blend_group_stats_kernel, dim3(ntiles), dim3(256), 0, s, a, ntiles, img.n_contrib, stats);
-    MGS_HIP(hipGetLastError());
-    return 0;
-}
-
-// ---- diagnostic: the forward's survivor masks against the backward's own cull (not on the hot path; mgs_debug_blend_mask_stats)
-// blend_backward_s_kernel walks the masks the forward left (BinningState::fwd_masks) instead of culling for itself.  This walks
-// every quadrant's list as the unsplit backward does and runs the cull the backward used to run -- the one blend_backward_stats_kernel
-// and the two older backward kernels still run -- beside the forward's word of the step, trimmed to the walk's range as bs_walk
-// trims it: stats[0] steps, [1] instances the own cull keeps, [2] set bits of the forward's masks, [3] instances the own cull
-// keeps and the mask lacks (0: the masks cover the cull).  [2] - [1] is what the backward now evaluates for nothing.
-__global__ void __launch_bounds__(256) blend_mask_stats_kernel(BlendArgs a, int ntiles, const uint32_t* __restrict__ n_contrib,
-                                                               unsigned long long* __restrict__ stats) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int tile = (int)blockIdx.x;
-    if (tile >= ntiles) return;
-    const int tx = tile % a.gx, ty = tile / a.gx;
-    const uint2 range = a.ranges[tile];
-    if (range.y <= range.x) return;
-    const int qx0i = tx * TILE + (wave & 1) * SUB, qy0i = ty * TILE + (wave >> 1) * SUB;
-    const int pxi = qx0i + (lane & 7), pyi = qy0i + (lane >> 3);
-    const bool inside = pxi < a.W && pyi < a.H;
-    const float qx0 = (float)qx0i, qy0 = (float)qy0i;
-    const uint32_t last = inside ? n_contrib[(size_t)pyi * a.W + pxi] : 0u;
-    const uint32_t maxc = wave_max_u32(last);
-    if (maxc == 0) return;
-    const uint32_t end = range.x + maxc;
-    const unsigned long long* const mask_row = a.fwd_masks + fwd_mask_word(range.x, tile, wave);
-    unsigned long long c0 = 0, c1 = 0, c2 = 0, c3 = 0;
-    const int b_first = (int)((maxc - 1) / WAVE);
-    for (int b = b_first; b >= 0; --b) {
-        const uint32_t i = range.x + (uint32_t)b * WAVE + lane;
-        float4 box = make_float4(0.f, 0.f, -1.f, -1.f), el = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (i < end) {
-            const uint32_t gid_l = a.point_list[i];
-            box = a.rec[(size_t)gid_l * 4];
-            el = a.rec[(size_t)gid_l * 4 + 3];
-        }
-        const unsigned long long alive = __builtin_amdgcn_ballot_w64(last >= (uint32_t)b * WAVE + 1u);
-        const unsigned long long own = __builtin_amdgcn_ballot_w64(quadrant_hit(box, el, qx0, qy0, alive));
-        unsigned long long fwd = mask_row[(size_t)b * 4];
-        if (b == b_first) fwd &= ~0ull >> (63u - ((maxc - 1u) & 63u));
-        c0 += 1;
-        c1 += __popcll(own);
-        c2 += __popcll(fwd);
-        c3 += __popcll(own & ~fwd);
-    }
-    if (lane < 4) atomicAdd(stats + lane, lane == 0 ? c0 : lane == 1 ? c1 : lane == 2 ? c2 : c3);
-}
-int launch_blend_mask_stats(const mgs_camera& cam, const GeometryState& g, const BinningState& b,
-                            const ImageState& img, unsigned long long* stats, hipStream_t s) {
-    const BlendArgs a = make_args(cam, g, b, img);
-    const int ntiles = a.gx * tiles_y(a.H);
-    if (ntiles == 0) return 0;
-    hipLaunchKernelGGL(blend_mask_stats_kernel, dim3(ntiles), dim3(256), 0, s, a, ntiles, img.n_contrib, stats);
-    MGS_HIP(hipGetLastError());
-    return 0;
-}
-
 // (The wave-per-tile and half-tile-per-wave variants of round 1 lost at every size and are gone; DESIGN.md section 4
 //  keeps their measurements.)
 int g_opt_blend_bwd_split = -1;         // mgs_debug_set_option("blend_bwd_split", 1 | 2 | 0 | -1): every quadrant's list walked from both ends by two waves (1: all back halves, then all front halves; 2: the halves of a tile in adjacent workgroups), 0 = unsplit, -1 = the default (see launch_blend_backward); needs blend_bwd_transposed = 2 and the forward's colour and depth images
@@ -1564,23 +1239,6 @@ int launch_blend_backward(const mgs_camera& cam, const GeometryState& g, const B
     else
         hipLaunchKernelGGL((blend_backward_kernel<false>), dim3(ntiles), dim3(256), 0, s, a, ntiles, img.final_T,
                            img.n_contrib, dL_dcolor, dL_ddepth, grad_acc);
-    MGS_HIP(hipGetLastError());
-    return 0;
-}
-
-// ---- diagnostic: the plain-FMA issue ceiling of this chip, measured by whoever asks (bench.py prints it next to the spec
-// VALU peak).  8 waves per SIMD, every CU busy, 8 independent v_fma_f32 per trip: tools/ubench/valu_rate.hip's first row.
-__global__ void __launch_bounds__(256) valu_ceiling_kernel(float* out, int iters, float seed) {
-    float a0 = seed + threadIdx.x, a1 = a0 + 1, a2 = a0 + 2, a3 = a0 + 3, a4 = a0 + 4, a5 = a0 + 5, a6 = a0 + 6, a7 = a0 + 7;
-    const float c = 1.0001f, d = 0.0001f;
-    for (int i = 0; i < iters; ++i) {
-        a0 = __builtin_fmaf(a0, c, d); a1 = __builtin_fmaf(a1, c, d); a2 = __builtin_fmaf(a2, c, d); a3 = __builtin_fmaf(a3, c, d);
-        a4 = __builtin_fmaf(a4, c, d); a5 = __builtin_fmaf(a5, c, d); a6 = __builtin_fmaf(a6, c, d); a7 = __builtin_fmaf(a7, c, d);
-    }
-    out[blockIdx.x * 256 + threadIdx.x] = ((a0 + a1) + (a2 + a3)) + ((a4 + a5) + (a6 + a7));
-}
-int launch_valu_ceiling(float* out, int iters, hipStream_t s) {
-    hipLaunchKernelGGL(valu_ceiling_kernel, dim3(MGS_VALU_CEILING_BLOCKS), dim3(256), 0, s, out, iters, 1.0f);
     MGS_HIP(hipGetLastError());
     return 0;
 }

@@ -10,16 +10,17 @@
 // forward left per (64-instance step, quadrant) (BinningState::fwd_masks) -- exactly what launch_blend_backward reads, so the
 // kernels are valid after an exact or a capacity-mode forward, on the global or the per-tile depth path.
 //
-// gfx950 mapping (that of blend.hip): a 16x16 tile is one 256-thread workgroup whose four waves never synchronise; wave w owns
+// gfx950 mapping (tile_walk.h): a 16x16 tile is one 256-thread workgroup whose four waves never synchronise; wave w owns
 // the 8x8 quadrant (w & 1, w >> 1), one pixel per lane, and walks the tile's list front to back, 64 instances per step:
 //   1. the step's survivor word comes through the scalar cache (the forward is an earlier kernel), lane l loads index l;
 //   2. the wave pops survivors off the word; the survivor's record (centre, conic, opacity) and its feature row arrive
 //      with scalar loads off the wave-uniform index (constant address space, common.h);
-//   3. all 64 lanes form alpha as blend_forward_kernel does; a pixel takes the instance iff its list position is <= the
+//   3. all 64 lanes form alpha with tile_walk.h's falloff; a pixel takes the instance iff its list position is <= the
 //      pixel's n_contrib, power <= 0 and alpha >= 1/255.  The forward decided where every pixel stops: no test of T here.
 // The channels are processed in chunks of C (compile time): C accumulators per lane in the forward, C upstream gradients per
 // lane in the backward; K > C walks the list ceil(K / C) times.  No LDS, no barriers.
 #include "common.h"
+#include "tile_walk.h"
 
 #include <math.h>
 
@@ -37,19 +38,10 @@ struct FeatArgs {
     int W, H, gx, K;
 };
 
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o, 64));
-    return v;
-}
-
 // what a wave knows about its quadrant before it walks
-struct FeatQuad {
+struct FeatQuad : Quadrant {
     uint2 range;            // wave-uniform
     uint32_t last, maxc;    // the pixel's n_contrib; its maximum over the quadrant (wave-uniform)
-    size_t pix;
-    float pxf, pyf;
-    bool inside;
     int tile, wave, lane;
 };
 
@@ -58,11 +50,7 @@ __device__ __forceinline__ FeatQuad feat_quadrant(const FeatArgs& a) {
     q.tile = (int)blockIdx.x;
     q.wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     q.lane = (int)(threadIdx.x & 63);
-    const int tx = q.tile % a.gx, ty = q.tile / a.gx;
-    const int pxi = tx * TILE + (q.wave & 1) * SUB + (q.lane & 7), pyi = ty * TILE + (q.wave >> 1) * SUB + (q.lane >> 3);
-    q.inside = pxi < a.W && pyi < a.H;                 // a pixel outside the image never blends: last = 0
-    q.pix = (size_t)pyi * a.W + pxi;
-    q.pxf = (float)pxi, q.pyf = (float)pyi;
+    MGS_QUADRANT_FILL(q, a, q.tile, q.wave, q.lane);   // (a pixel outside the image never blends: last = 0)
     const uint2 r = a.ranges[q.tile];
     q.range = make_uint2((uint32_t)__builtin_amdgcn_readfirstlane((int)r.x), (uint32_t)__builtin_amdgcn_readfirstlane((int)r.y));
     q.last = q.inside && q.range.y > q.range.x ? a.n_contrib[q.pix] : 0u;
@@ -76,8 +64,7 @@ __device__ __forceinline__ FeatQuad feat_quadrant(const FeatArgs& a) {
 template <class F>
 __device__ __forceinline__ void feat_walk(const FeatArgs& a, const FeatQuad& q, F&& use) {
     const const_float_p recs = MGS_CONST(a.rec);
-    // (fwd_mask_word of blend.hip: row = range.x / 64 + tile + step, four quadrant words per row)
-    const const_u64_p mask_row = MGS_CONST_U64(a.fwd_masks) + ((size_t)(q.range.x / WAVE) + (size_t)q.tile) * 4 + (size_t)q.wave;
+    const const_u64_p mask_row = MGS_CONST_U64(a.fwd_masks) + fwd_mask_word(q.range.x, q.tile, q.wave);
     const uint32_t end = q.range.x + q.maxc;
     const int b_last = (int)((q.maxc - 1u) / WAVE);
     float T = 1.f;
@@ -91,13 +78,12 @@ __device__ __forceinline__ void feat_walk(const FeatArgs& a, const FeatQuad& q, 
         while (mask) {
             const int j = __builtin_ctzll(mask);
             mask &= mask - 1ull;
-            const uint32_t gid = (uint32_t)__builtin_amdgcn_readlane((int)gid_l, j);
+            const uint32_t gid = bcast(gid_l, j);
             const const_float_p r = recs + (size_t)gid * REC_FLOATS;
-            // alpha exactly as blend_forward_kernel forms it
             const float dx = r[R_X] - q.pxf, dy = r[R_Y] - q.pyf;
-            const float power = dx * (r[R_CA] * dx + r[R_CB] * dy) + (r[R_CC] * dy) * dy;     // log2 of the Gaussian falloff
-            const float alpha = fminf(0.99f, r[R_OPAC] * __builtin_amdgcn_exp2f(power));
-            const bool act = (j <= rel_last) && !(power > 0.f) && !(alpha < 1.0f / 255.0f);
+            const float power = falloff_power(dx, dy, r[R_CA], r[R_CB], r[R_CC]);
+            const float alpha = falloff_alpha(r[R_OPAC], __builtin_amdgcn_exp2f(power));
+            const bool act = falloff_active(j <= rel_last, power, alpha);
             if (__builtin_amdgcn_ballot_w64(act) == 0ull) continue;
             const float a_eff = act ? alpha : 0.f;          // a pixel that passes: w = 0, T * (1 - 0) = T
             const float w = a_eff * T;

@@ -13,16 +13,17 @@
 // ---- ellipsoid walk ------------------------------------------------------------------------------------------------------
 // The reference's fragments have alpha 0 or 1 (alpha > 0.4 after the 0.99 cap) and are blended far to near: the NEAREST opaque
 // fragment wins.  So pixel p shows colour[g] exp(power) of the first entry g of its tile's list, in blend order, with
-// power <= 0 and min(0.99, opacity exp(power)) > threshold -- power and alpha formed with the expressions of
-// blend_forward_kernel -- and black (hit -1) where no entry qualifies.
+// power <= 0 and min(0.99, opacity exp(power)) > threshold -- power and alpha formed by tile_walk.h's
+// falloff, as the blend forward forms them -- and black (hit -1) where no entry qualifies.
 // What is read: the blend records, the point list in blend order, the canonical tile ranges.  NOT n_contrib (a pixel
 // saturated by many faint splats has its first opaque one behind the forward's stop) and NOT the forward's survivor masks
 // (the forward never entered the steps behind its stop): the walk culls for itself, lane l testing the alpha >= 1/255 box of
 // entry l of the step against the quadrant (threshold >= 1/255 is an argument check, so the box is conservative).
-// gfx950 mapping (that of features.hip): a 16x16 tile is one 256-thread workgroup whose four waves never synchronise; wave w
+// gfx950 mapping (tile_walk.h): a 16x16 tile is one 256-thread workgroup whose four waves never synchronise; wave w
 // owns the 8x8 quadrant (w & 1, w >> 1), one pixel per lane; a candidate's record arrives with scalar loads off the
 // wave-uniform index (constant address space, common.h).  A wave retires once all its pixels have hit or the range ends.
 #include "common.h"
+#include "tile_walk.h"
 
 #include <math.h>
 
@@ -42,20 +43,17 @@ __global__ void __launch_bounds__(256) viewer_ellipsoids_kernel(EllArgs a, float
     const int tile = (int)blockIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int lane = (int)(threadIdx.x & 63);
-    const int tx = tile % a.gx, ty = tile / a.gx;
-    const int qx0i = tx * TILE + (wave & 1) * SUB, qy0i = ty * TILE + (wave >> 1) * SUB;
-    const int pxi = qx0i + (lane & 7), pyi = qy0i + (lane >> 3);
-    const bool inside = pxi < a.W && pyi < a.H;
-    const float pxf = (float)pxi, pyf = (float)pyi;
-    // the quadrant's rectangle, grown by 0.05 px as the blend's cull has it
-    const float qx_lo = (float)qx0i - 0.05f, qx_hi = (float)(qx0i + SUB - 1) + 0.05f;
-    const float qy_lo = (float)qy0i - 0.05f, qy_hi = (float)(qy0i + SUB - 1) + 0.05f;
+    Quadrant q;
+    MGS_QUADRANT_FILL(q, a, tile, wave, lane);
+    // the quadrant's rectangle, grown by 0.05 px as the blend's cull has it (its own test, not quadrant_hit: the two round differently)
+    const float qx_lo = (float)q.qx0i - 0.05f, qx_hi = (float)(q.qx0i + SUB - 1) + 0.05f;
+    const float qy_lo = (float)q.qy0i - 0.05f, qy_hi = (float)(q.qy0i + SUB - 1) + 0.05f;
     const uint2 r = a.ranges[tile];
     const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane((int)r.x), end = (uint32_t)__builtin_amdgcn_readfirstlane((int)r.y);
     const const_float_p recs = MGS_CONST(a.rec);
     const float4* const rec4 = reinterpret_cast<const float4*>(a.rec);
 
-    bool open = inside;                             // the pixel has no hit yet (a pixel outside the image never takes one)
+    bool open = q.inside;                           // the pixel has no hit yet (a pixel outside the image never takes one)
     float c0 = 0.f, c1 = 0.f, c2 = 0.f;
     int32_t h = -1;
     for (uint32_t base = first; base < end && __builtin_amdgcn_ballot_w64(open) != 0ull; base += WAVE) {
@@ -72,13 +70,12 @@ __global__ void __launch_bounds__(256) viewer_ellipsoids_kernel(EllArgs a, float
         while (mask) {
             const int j = __builtin_ctzll(mask);
             mask &= mask - 1ull;
-            const uint32_t gid = (uint32_t)__builtin_amdgcn_readlane((int)gid_l, j);
+            const uint32_t gid = bcast(gid_l, j);
             const const_float_p g = recs + (size_t)gid * REC_FLOATS;
-            // power and alpha exactly as blend_forward_kernel forms them
-            const float dx = g[R_X] - pxf, dy = g[R_Y] - pyf;
-            const float power = dx * (g[R_CA] * dx + g[R_CB] * dy) + (g[R_CC] * dy) * dy;     // log2 of the Gaussian falloff
+            const float dx = g[R_X] - q.pxf, dy = g[R_Y] - q.pyf;
+            const float power = falloff_power(dx, dy, g[R_CA], g[R_CB], g[R_CC]);
             const float G = __builtin_amdgcn_exp2f(power);
-            const float alpha = fminf(0.99f, g[R_OPAC] * G);
+            const float alpha = falloff_alpha(g[R_OPAC], G);
             const bool take = open && !(power > 0.f) && alpha > a.threshold;
             if (__builtin_amdgcn_ballot_w64(take) == 0ull) continue;
             if (take) {
@@ -89,12 +86,12 @@ __global__ void __launch_bounds__(256) viewer_ellipsoids_kernel(EllArgs a, float
             if (__builtin_amdgcn_ballot_w64(open) == 0ull) break;
         }
     }
-    if (inside) {
-        const size_t pix = (size_t)pyi * a.W + pxi, HW = (size_t)a.H * a.W;
-        out[pix] = c0;
-        out[HW + pix] = c1;
-        out[2 * HW + pix] = c2;
-        if (hit) hit[pix] = h;
+    if (q.inside) {
+        const size_t HW = (size_t)a.H * a.W;
+        out[q.pix] = c0;
+        out[HW + q.pix] = c1;
+        out[2 * HW + q.pix] = c2;
+        if (hit) hit[q.pix] = h;
     }
 }
 

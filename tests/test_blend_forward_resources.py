@@ -1,37 +1,11 @@
 """The blend forward runs at eight waves per SIMD; the per-tile depth sort folded into it (blend_forward_kernel<true>) must
 not cost a wave.  The compiler's resource report for gfx950 (no GPU needed) holds every instantiation to occupancy 8,
 no scratch and at most 20 480 bytes of LDS per workgroup (eight workgroups in the compute unit's 160 KB)."""
-import os
-import re
-import subprocess
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "monogs_amd", "csrc")
-
-
-def _resource_report(tmp_path):
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    # the flags of blend.o in csrc/Makefile
-    cmd = [hipcc, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fno-gpu-rdc", "-Wno-unused-function", "-DNDEBUG",
-           "-fno-slp-vectorize", "-Wno-inline-asm", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
-           "-c", os.path.join(CSRC, "blend.hip"), "-o", str(tmp_path / "blend.o")]
-    r = subprocess.run(cmd, cwd=CSRC, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    kernels, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark:\s+Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            kernels[name] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z /\[\]]+?): (\S+) \[-Rpass-analysis", line)
-        if m and name:
-            kernels[name][m.group(1).strip()] = m.group(2)
-    return kernels
+from resource_report import resource_report
 
 
 def test_blend_forward_keeps_eight_waves_per_simd(tmp_path):
-    kernels = _resource_report(tmp_path)
+    kernels = resource_report("blend.hip", tmp_path)[0]
     fwd = {k: v for k, v in kernels.items() if "blend_forward_kernel" in k}
     assert len(fwd) == 2, sorted(kernels)                 # <false>: depth-ordered lists, <true>: sorts its tile first
     for name, res in fwd.items():

@@ -3,44 +3,11 @@ private-memory scratch -- the covisibility and the decision kernel index pointer
 must stay loads from the argument segment -- and the LDS of the median's kernels is what csrc/kfwindow.hip says: one histogram of
 2048 buckets (8192 bytes) per workgroup of the counting launch, the summed histogram plus 256 scan words (9216 bytes) in the
 selecting launch."""
-import os
-import re
-import subprocess
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "monogs_amd", "csrc")
-
-
-def _resource_report(tmp_path):
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    # the flags of kfwindow.o in csrc/Makefile
-    cmd = [hipcc, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",
-           "-DNDEBUG", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
-           "-c", os.path.join(CSRC, "kfwindow.hip"), "-o", str(tmp_path / "kfwindow.o")]
-    r = subprocess.run(cmd, cwd=CSRC, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    kernels, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark:\s+Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            kernels[name] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z /\[\]]+?): (\S+) \[-Rpass-analysis", line)
-        if m and name:
-            kernels[name][m.group(1).strip()] = m.group(2)
-    return kernels
-
-
-def test_makefile_builds_kfwindow_with_the_flags_used_here():
-    mk = open(os.path.join(CSRC, "Makefile")).read()
-    assert re.search(r"^SRCS\s*=.*\bkfwindow\.hip\b", mk, flags=re.M)
-    assert "-O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -fno-gpu-rdc -Wall -Wno-unused-function -DNDEBUG" in mk
-    assert not re.search(r"kfwindow\.o:\s*CXXFLAGS", mk)      # no per-file flags to mirror
+from resource_report import resource_report
 
 
 def test_kfwindow_kernels_use_no_scratch_and_the_recorded_lds(tmp_path):
-    kernels = _resource_report(tmp_path)
+    kernels = resource_report("kfwindow.hip", tmp_path)[0]
     pick = lambda s: {k: v for k, v in kernels.items() if s in k}  # noqa: E731
     hist, select = pick("median_hist_kernel"), pick("median_select_kernel")
     covis, decide = pick("covisibility_kernel"), pick("keyframe_decide_kernel")

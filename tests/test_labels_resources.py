@@ -2,45 +2,13 @@
 route.  The compiler's resource report for gfx950 (no GPU needed) must show no scratch for any kernel of the file: a spilled
 instantiation is a wrong choice of chunk, not something to accept.  The register, occupancy and LDS figures are printed; DESIGN.md
 section 3 ("Label kernels") quotes them."""
-import os
-import re
-import subprocess
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "monogs_amd", "csrc")
-
-
-def _resource_report(tmp_path):
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    # the flags of labels.o in csrc/Makefile (the common ones: the file has no line of its own there)
-    cmd = [hipcc, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",
-           "-DNDEBUG", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
-           "-c", os.path.join(CSRC, "labels.hip"), "-o", str(tmp_path / "labels.o")]
-    r = subprocess.run(cmd, cwd=CSRC, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    assert "warning:" not in r.stderr, r.stderr[-4000:]
-    kernels, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark:\s+Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            kernels[name] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z /\[\]]+?): (\S+) \[-Rpass-analysis", line)
-        if m and name:
-            kernels[name][m.group(1).strip()] = m.group(2)
-    return kernels
-
-
-def test_makefile_builds_labels_with_the_flags_used_here():
-    mk = open(os.path.join(CSRC, "Makefile")).read()
-    assert re.search(r"^SRCS\s*=.*\blabels\.hip\b", mk, flags=re.M)
-    assert "-O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -fno-gpu-rdc -Wall -Wno-unused-function -DNDEBUG" in mk
-    assert not re.search(r"^\$\(OUT\)/labels\.o:", mk, flags=re.M)                     # no flags of its own
+from resource_report import resource_report
 
 
 def test_label_kernels_do_not_spill(tmp_path):
-    kernels = {k: v for k, v in _resource_report(tmp_path).items() if "label_" in k}
+    report, stderr = resource_report("labels.hip", tmp_path)
+    assert "warning:" not in stderr, stderr[-4000:]
+    kernels = {k: v for k, v in report.items() if "label_" in k}
     loss = {k: v for k, v in kernels.items() if "label_loss_kernel" in k}
     count = {k: v for k, v in kernels.items() if "label_count_kernel" in k}
     conf = {k: v for k, v in kernels.items() if "label_confusion_kernel" in k}

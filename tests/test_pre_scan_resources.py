@@ -5,44 +5,19 @@ and to the occupancy the same report gave for the commit before the scan was fol
 preprocess_forward_kernel<COV, PRECOMP> (40-46 VGPRs, 20 480 bytes of LDS: exactly eight workgroups per compute unit, which is
 why the scan keeps its wave totals in the padding of the record hand-over rows) and 8 for duplicate_kernel (51 VGPRs,
 9 216 bytes of LDS)."""
-import os
-import re
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "monogs_amd", "csrc")
+from resource_report import resource_report
+
 PARENT_OCCUPANCY = 8          # every instantiation of both kernels, parent commit
 PARENT_PRE_LDS = 20480        # preprocess_forward_kernel
 PARENT_DUP_LDS = 9216         # duplicate_kernel
 
 
-def _resource_report(tmp_path, src, extra):
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    # the flags of the object in csrc/Makefile
-    cmd = [hipcc, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fno-gpu-rdc", "-Wno-unused-function", "-DNDEBUG",
-           *extra, "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
-           "-c", os.path.join(CSRC, src), "-o", str(tmp_path / (src + ".o"))]
-    r = subprocess.run(cmd, cwd=CSRC, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    kernels, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark:\s+Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            kernels[name] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z /\[\]]+?): (\S+) \[-Rpass-analysis", line)
-        if m and name:
-            kernels[name][m.group(1).strip()] = m.group(2)
-    return kernels
-
-
 @pytest.fixture(scope="module")
 def reports(tmp_path_factory):
     d = tmp_path_factory.mktemp("pre_scan_resources")
-    return dict(pre=_resource_report(d, "preprocess.hip", ["-ffp-contract=off"]), bin=_resource_report(d, "binning.hip", []))
+    return dict(pre=resource_report("preprocess.hip", d)[0], bin=resource_report("binning.hip", d)[0])
 
 
 def test_preprocess_forward_keeps_its_occupancy(reports):

@@ -2,44 +2,11 @@
 least 4 waves per SIMD and at most 40 960 bytes of LDS per 256-thread workgroup (four workgroups per compute unit) -- the
 floors -- and what csrc/ssim.hip actually reaches: forward 5 waves and 26 912 bytes (six workgroups by LDS), backward
 6 waves and 21 672 bytes (seven)."""
-import os
-import re
-import subprocess
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "monogs_amd", "csrc")
-
-
-def _resource_report(tmp_path):
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    # the flags of ssim.o in csrc/Makefile
-    cmd = [hipcc, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",
-           "-DNDEBUG", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
-           "-c", os.path.join(CSRC, "ssim.hip"), "-o", str(tmp_path / "ssim.o")]
-    r = subprocess.run(cmd, cwd=CSRC, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    kernels, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark:\s+Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            kernels[name] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z /\[\]]+?): (\S+) \[-Rpass-analysis", line)
-        if m and name:
-            kernels[name][m.group(1).strip()] = m.group(2)
-    return kernels
-
-
-def test_makefile_builds_ssim_with_the_flags_used_here():
-    mk = open(os.path.join(CSRC, "Makefile")).read()
-    assert re.search(r"^SRCS\s*=.*\bssim\.hip\b", mk, flags=re.M)
-    assert "-O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -fno-gpu-rdc -Wall -Wno-unused-function -DNDEBUG" in mk
-    assert not re.search(r"ssim\.o:\s*CXXFLAGS", mk)          # no per-file flags to mirror
+from resource_report import resource_report
 
 
 def test_ssim_kernels_stream(tmp_path):
-    kernels = _resource_report(tmp_path)
+    kernels = resource_report("ssim.hip", tmp_path)[0]
     fwd = {k: v for k, v in kernels.items() if "ssim_forward_kernel" in k}
     bwd = {k: v for k, v in kernels.items() if "ssim_backward_kernel" in k}
     fin = {k: v for k, v in kernels.items() if "ssim_finalize_kernel" in k}
