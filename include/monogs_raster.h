@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define MGS_ABI_VERSION 23
+#define MGS_ABI_VERSION 24
 #define MGS_TILE 16 /* tile edge in pixels; ranges are per 16x16 tile */
 
 /* GaussianRasterizationSettings, minus `prefiltered` / `debug` which are call flags
@@ -913,6 +913,57 @@ int mgs_tsdf_extract_count(const mgs_tsdf_volume* volume, float min_weight, void
                            void* stream);
 int mgs_tsdf_extract_emit(const mgs_tsdf_volume* volume, const void* scratch, float* vertices /* [V,3] */,
                           float* colors /* [V,3] or NULL */, int32_t* triangles /* [T,3] */, uint32_t V, uint32_t T, void* stream);
+
+/* ---- Reconstruction evaluation against a ground-truth mesh (ABI v24) ------------------------------------------------
+ * The specification is DESIGN.md, "Reconstruction evaluation" (tests/mesh_eval_mirror.py restates it in float64).  Every entry
+ * point takes a stream, keeps no state between calls, uses no float atomics and no library kernels (sorts and scans are the
+ * library's own) and is bitwise reproducible from call to call.
+ *
+ * mgs_nn_dist2: d2[q] = min over targets p of fma(dz, dz, fma(dy, dy, dx dx)), d = target - query in float32 (the pair formula of
+ * mgs_dist2_knn); index[q] (or NULL) = the SMALLEST target index that attains it.  P == 0: d2 = +inf, index = -1; Q == 0: nothing
+ * is done.  Two paths, bit-identical in both outputs: below mgs_nn_grid_min() (6144) targets an LDS-tiled all-pairs sweep,
+ * from there on boxes of 64 along the Morton curve of the joint bounding box (mgs_dist2_knn's index, built for both sets; one
+ * wave answers 64 neighbouring queries and prunes boxes wave-uniformly); flags force one of them for THIS call.  `scratch`:
+ * mgs_nn_scratch_bytes(Q, P) bytes (pure; sized for either path; may be NULL on the all-pairs path).
+ *
+ * mgs_mesh_sample: N points on the triangles with keep[t] != 0 (keep NULL: all), area-weighted and stratified.  Area of a
+ * triangle in float32, 0.5 |(b - a) x (c - a)|, quantised to uint64 by a power of two chosen from the vertices' bounding box
+ * so that the sum of T areas stays below 2^60; inclusive integer scan (exact: the chosen triangle does not depend on scan order).
+ * Sample s draws r0, r1, r2 in [0, 1) (24 bits each) from the counter hash mix(mix(seed ^ 0x9E3779B9) + 3 s + k), takes the
+ * first triangle whose inclusive sum exceeds floor((s + r0) / N * total) (float64), and lies at a + sqrt(r1) (1 - r2) (b - a) +
+ * sqrt(r1) r2 (c - a).  Zero-area and masked triangles are never chosen.  tri_index [N] or NULL; *area (device double, or NULL)
+ * = the kept area.  A vertex index outside [0, V) is an argument error found on the device: bit 0 of *status (device word, zeroed
+ * by the caller) is raised, the triangle counts as area 0 and nothing is read through it.  With no kept area the points are 0
+ * and tri_index -1 (the caller reads *area).  `scratch`: mgs_mesh_sample_scratch_bytes(T) bytes.
+ *
+ * mgs_mesh_mark_seen: one launch per view, one lane per vertex; seen[v] (bytes, zeroed by the caller before the first view) is set
+ * to 1 when pc = R p + t (`viewmatrix`: the device matrix of mgs_camera.viewmatrix) has max(depth_min, 0+) <= pc.z <= depth_max
+ * (depth_max <= 0: no upper bound), its pixel -- exactly the projection and pixel rule of mgs_tsdf_integrate -- lies inside the image
+ * and, with `depth` ([H][W] or NULL), depth > 0 there and pc.z <= depth + occlusion_eps.  A lane stores only its own byte.
+ *
+ * mgs_recon_metrics: out[0] = sum of sqrt(d2) over the finite entries (float64), out[1] = their number, out[2 + k] = how many have
+ * sqrt(d2) < thresholds[k] (host array, K <= MGS_RECON_MAX_THRESHOLDS, compared in float64); all as doubles, the counts exact.
+ * Per-block partial sums in a fixed order and one finishing block.  `scratch`: mgs_recon_metrics_scratch_bytes() bytes.
+ * Refused with 1 and a message before any launch: negative sizes, sizes beyond 2^30, NULL required pointers, unknown or
+ * contradictory flags, a mesh without vertices or triangles, non-positive image size or focal lengths, K out of range. */
+#define MGS_NN_FORCE_ALL_PAIRS 1
+#define MGS_NN_FORCE_MORTON 2
+#define MGS_RECON_MAX_THRESHOLDS 8
+int32_t mgs_nn_grid_min(void);
+size_t mgs_nn_scratch_bytes(int32_t Q, int32_t P);
+int mgs_nn_dist2(int32_t Q, int32_t P, const float* queries /* [Q,3] */, const float* targets /* [P,3] */, int32_t flags,
+                 float* d2 /* [Q] */, int32_t* index /* [Q] or NULL */, void* scratch, void* stream);
+size_t mgs_mesh_sample_scratch_bytes(int32_t T);
+int mgs_mesh_sample(int32_t V, int32_t T, const float* vertices /* [V,3] */, const int32_t* triangles /* [T,3] */,
+                    const uint8_t* keep /* [T] or NULL */, int32_t N, uint32_t seed, float* points /* [N,3] */,
+                    int32_t* tri_index /* [N] or NULL */, double* area /* device, or NULL */, uint32_t* status /* device */,
+                    void* scratch, void* stream);
+int mgs_mesh_mark_seen(int32_t V, const float* vertices /* [V,3] */, const float* viewmatrix /* device, 16 floats */, int32_t W,
+                       int32_t H, float fx, float fy, float cx, float cy, const float* depth /* [H][W] or NULL */, float depth_min,
+                       float depth_max, float occlusion_eps, uint8_t* seen /* [V] */, void* stream);
+size_t mgs_recon_metrics_scratch_bytes(void);
+int mgs_recon_metrics(int32_t Q, const float* d2 /* [Q] */, int32_t K, const float* thresholds /* host [K] */,
+                      double* out /* device [2 + K] */, void* scratch, void* stream);
 
 #ifdef __cplusplus
 }

@@ -25,4 +25,8 @@ def __getattr__(name):
     if name in ("TSDFVolume", "TriangleMesh", "fuse_map", "mesh_stats", "mesh_from_map"):
         from . import tsdf
         return getattr(tsdf, name)
+    # reconstruction evaluation against a ground-truth mesh (monogs_amd.mesh_eval) likewise
+    if name in ("nearest_distance", "sample_mesh", "seen_vertices", "cull_mesh", "eval_reconstruction", "recon_metrics"):
+        from . import mesh_eval
+        return getattr(mesh_eval, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -11,7 +11,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MGS_LIB_PATH") or os.path.join(_HERE, "lib", "libmonogs_raster.so")   # (override: kernel experiments)
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 c_float_p = C.c_void_p   # device pointers travel as integers (tensor.data_ptr())
 
@@ -163,6 +163,15 @@ SIGNATURES = {
     "mgs_tsdf_extract_scratch_bytes": (C.c_size_t, [C.c_int32] * 3),
     "mgs_tsdf_extract_count": (C.c_int, [C.POINTER(MgsTsdfVolume), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mgs_tsdf_extract_emit": (C.c_int, [C.POINTER(MgsTsdfVolume)] + [C.c_void_p] * 4 + [C.c_uint32, C.c_uint32, C.c_void_p]),
+    "mgs_nn_grid_min": (C.c_int32, []),
+    "mgs_nn_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "mgs_nn_dist2": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 4),
+    "mgs_mesh_sample_scratch_bytes": (C.c_size_t, [C.c_int32]),
+    "mgs_mesh_sample": (C.c_int, [C.c_int32, C.c_int32] + [C.c_void_p] * 3 + [C.c_int32, C.c_uint32] + [C.c_void_p] * 6),
+    "mgs_mesh_mark_seen": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_float] * 4 + [C.c_void_p]
+                           + [C.c_float] * 3 + [C.c_void_p, C.c_void_p]),
+    "mgs_recon_metrics_scratch_bytes": (C.c_size_t, []),
+    "mgs_recon_metrics": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

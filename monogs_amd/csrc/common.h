@@ -349,4 +349,27 @@ int launch_mark_visible(int P, const float* means3D, const float* viewmatrix, ui
 size_t knn_scratch_bytes(int P);
 int launch_knn(int P, const float* points, float* out, void* scratch, hipStream_t s);
 
+// ---- the Morton-box index of a point set (knn.hip), built for mgs_dist2_knn and for mgs_nn_dist2 (mesheval.hip) ----
+// the ONE pair formula of every nearest-neighbour path (explicit fma chain so that all of them compile to the same three instructions)
+__device__ __forceinline__ float pair_d2(float cx, float cy, float cz, float qx, float qy, float qz) {
+    const float dx = cx - qx, dy = cy - qy, dz = cz - qz;
+    return fmaf(dz, dz, fmaf(dy, dy, dx * dx));
+}
+struct MortonIndex {
+    int32_t* bbox;            // [8] ordered-int min xyz (0..2), max xyz (4..6)
+    uint32_t *code_a, *code_b, *idx_a, *idx_b;
+    float4* sorted;           // [P] x, y, z, bits(original index), Morton order
+    float4* box_lo;           // [ceil(P / 64)] bounds of 64 consecutive sorted points
+    float4* box_hi;
+    void* sort_temp;
+    size_t bytes;
+};
+MortonIndex morton_carve(void* base, int P);
+void morton_bbox_reset(int32_t* bbox, hipStream_t s);                               // an empty box
+void morton_bbox_extend(int P, const float* points, int32_t* bbox, hipStream_t s);  // bbox |= points (integer atomics: exact)
+// 30-bit codes inside `bbox` (any device box that holds the points), the radix sort, `sorted` + box bounds.  `codes_sorted`: where
+// the sorted codes lie (one of k.code_a / k.code_b)
+int morton_build(int P, const float* points, const int32_t* bbox, const MortonIndex& k, hipStream_t s,
+                 const uint32_t** codes_sorted = nullptr);
+
 }  // namespace mgs

@@ -30,11 +30,7 @@ constexpr int KNN_GRID_MIN = 6144;          // below this the all-pairs sweep wi
                                             // 4 k points 0.147 vs 0.207 ms, 8 k 0.291 vs 0.246, 16 k 0.58 vs 0.33, 32 k 1.17 vs 0.36 ms
 constexpr float KNN_FLT_MAX = 3.402823466e+38f;
 
-// the ONE pair formula both paths use (explicit fma chain so both compile to the same three instructions)
-__device__ __forceinline__ float pair_d2(float cx, float cy, float cz, float qx, float qy, float qz) {
-    const float dx = cx - qx, dy = cy - qy, dz = cz - qz;
-    return fmaf(dz, dz, fmaf(dy, dy, dx * dx));
-}
+// the ONE pair formula both paths use: pair_d2 (common.h; mesheval.hip's nearest neighbour uses it too)
 // insert d into the sorted triple (b0 <= b1 <= b2)
 __device__ __forceinline__ void insert3(float d, float& b0, float& b1, float& b2) {
     const float m2 = fminf(b2, d);
@@ -71,17 +67,10 @@ __global__ void __launch_bounds__(KNN_THREADS) knn_kernel(int P, const float* __
 // ------------------------------------------------------------------------------------------------
 // Morton-box path
 // ------------------------------------------------------------------------------------------------
-struct KnnScratch {
-    int32_t* bbox;            // [8] ordered-int min xyz (0..2), max xyz (4..6)
-    uint32_t *code_a, *code_b, *idx_a, *idx_b;
-    float4* sorted;           // [P] x, y, z, bits(original index), Morton order
-    float4* box_lo;           // [nb]
-    float4* box_hi;           // [nb]
-    void* sort_temp;
-    size_t bytes;
-};
-static KnnScratch knn_carve(void* base, int P) {
-    KnnScratch k;
+// the index (MortonIndex, common.h): bbox [8] ordered-int min xyz (0..2), max xyz (4..6); sorted [P] x, y, z, bits(original
+// index) in Morton order; box_lo / box_hi [nb]
+MortonIndex morton_carve(void* base, int P) {
+    MortonIndex k;
     const size_t n = (size_t)P, nb = (n + KNN_BOX - 1) / KNN_BOX;
     char* p = (char*)align_up((size_t)base, 256);
     char* p0 = p;
@@ -261,7 +250,7 @@ static int knn_grid_min() { return g_opt_knn_grid_min >= 0 ? g_opt_knn_grid_min 
 
 size_t knn_scratch_bytes(int P) {
     if (P < 4) return 256;
-    return knn_carve(nullptr, P).bytes;              // sized for either path, whatever the environment says later
+    return morton_carve(nullptr, P).bytes;              // sized for either path, whatever the environment says later
 }
 
 int launch_knn(int P, const float* points, float* out, void* scratch, hipStream_t s) {
@@ -272,17 +261,29 @@ int launch_knn(int P, const float* points, float* out, void* scratch, hipStream_
         return 0;
     }
     if (!scratch) { set_error("mgs_dist2_knn: scratch is NULL"); return 1; }
-    const KnnScratch k = knn_carve(scratch, P);
+    const MortonIndex k = morton_carve(scratch, P);
     const int nb = (P + KNN_BOX - 1) / KNN_BOX;
-    const int blocks = (P + KNN_THREADS - 1) / KNN_THREADS;
-    hipLaunchKernelGGL(knn_bbox_init_kernel, dim3(1), dim3(64), 0, s, k.bbox);
-    hipLaunchKernelGGL(knn_bbox_kernel, dim3(min(blocks, 1024)), dim3(KNN_THREADS), 0, s, P, points, k.bbox);
-    hipLaunchKernelGGL(knn_morton_kernel, dim3(blocks), dim3(KNN_THREADS), 0, s, P, points, k.bbox, k.code_a, k.idx_a);
-    if (int rc = radix_sort_pairs(k.code_a, k.idx_a, k.code_b, k.idx_b, (uint64_t)P, 32, k.sort_temp, s, nullptr)) return rc;
-    const uint32_t* idx_sorted = radix_result_in_b(32) ? k.idx_b : k.idx_a;
-    hipLaunchKernelGGL(knn_gather_kernel, dim3(blocks), dim3(KNN_THREADS), 0, s, P, points, idx_sorted, k.sorted, k.box_lo, k.box_hi);
+    morton_bbox_reset(k.bbox, s);
+    morton_bbox_extend(P, points, k.bbox, s);
+    if (int rc = morton_build(P, points, k.bbox, k, s)) return rc;
     hipLaunchKernelGGL(knn_query_kernel, dim3((nb + 3) / 4), dim3(KNN_THREADS), 0, s, P, nb, k.sorted, k.box_lo, k.box_hi, out);
     MGS_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---- the index build, shared with the cross-set nearest neighbour of mesheval.hip -------------------------------------------
+void morton_bbox_reset(int32_t* bbox, hipStream_t s) { hipLaunchKernelGGL(knn_bbox_init_kernel, dim3(1), dim3(64), 0, s, bbox); }
+void morton_bbox_extend(int P, const float* points, int32_t* bbox, hipStream_t s) {
+    const int blocks = (P + KNN_THREADS - 1) / KNN_THREADS;
+    hipLaunchKernelGGL(knn_bbox_kernel, dim3(min(blocks, 1024)), dim3(KNN_THREADS), 0, s, P, points, bbox);
+}
+int morton_build(int P, const float* points, const int32_t* bbox, const MortonIndex& k, hipStream_t s, const uint32_t** codes_sorted) {
+    const int blocks = (P + KNN_THREADS - 1) / KNN_THREADS;
+    hipLaunchKernelGGL(knn_morton_kernel, dim3(blocks), dim3(KNN_THREADS), 0, s, P, points, bbox, k.code_a, k.idx_a);
+    if (int rc = radix_sort_pairs(k.code_a, k.idx_a, k.code_b, k.idx_b, (uint64_t)P, 32, k.sort_temp, s, nullptr)) return rc;
+    const uint32_t* idx_sorted = radix_result_in_b(32) ? k.idx_b : k.idx_a;
+    if (codes_sorted) *codes_sorted = radix_result_in_b(32) ? k.code_b : k.code_a;
+    hipLaunchKernelGGL(knn_gather_kernel, dim3(blocks), dim3(KNN_THREADS), 0, s, P, points, idx_sorted, k.sorted, k.box_lo, k.box_hi);
     return 0;
 }
 

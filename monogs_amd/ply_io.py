@@ -141,14 +141,53 @@ def save_mesh_ply(path: str, mesh) -> None:
         fh.write(ft.tobytes())
 
 
+_PLY_INDEX_TYPES = {"int": "<i4", "int32": "<i4", "uint": "<u4", "uint32": "<u4"}
+
+
+def _read_faces(path, raw, nf, index_type):
+    """int32 [T,3] from the face records ``uchar n, n indices``: all triangles (one strided view), all quads (each split (0,1,2),
+    (0,2,3)), or a mix of the two (walked record by record).  Indices beyond 2^31 - 1 are refused."""
+    out = None
+    for n in (3, 4):
+        fdt = np.dtype([("n", "u1"), ("i", index_type, (n,))])
+        if len(raw) >= nf * fdt.itemsize:
+            ft = np.frombuffer(raw, dtype=fdt, count=nf)
+            if (ft["n"] == n).all():
+                out = ft["i"].astype(np.int64).reshape(-1, n)
+                break
+    if out is None:
+        rows, at = [], 0
+        for _ in range(nf):
+            if at >= len(raw):
+                raise ValueError(f"{path}: truncated face list")
+            n = raw[at]
+            if n not in (3, 4) or at + 1 + 4 * n > len(raw):
+                raise ValueError(f"{path}: only faces of three or four vertices are read")
+            rows.append(np.frombuffer(raw, dtype=index_type, count=n, offset=at + 1).astype(np.int64))
+            at += 1 + 4 * n
+        out_rows = []
+        for r in rows:
+            out_rows.append(r[[0, 1, 2]])
+            if len(r) == 4:
+                out_rows.append(r[[0, 2, 3]])
+        out = np.stack(out_rows) if out_rows else np.zeros((0, 3), np.int64)
+    elif out.shape[1] == 4:
+        out = np.stack([out[:, [0, 1, 2]], out[:, [0, 2, 3]]], axis=1).reshape(-1, 3)
+    if out.size and (out.max() > 0x7FFFFFFF or out.min() < 0):
+        raise ValueError(f"{path}: vertex index outside int32")
+    return np.ascontiguousarray(out.astype(np.int32)).reshape(-1, 3)
+
+
 def load_mesh_ply(path: str, device="cpu"):
-    """The ``TriangleMesh`` of a file ``save_mesh_ply`` wrote (colours come back as uchar / 255)."""
+    """The ``TriangleMesh`` of a binary little-endian PLY: a file ``save_mesh_ply`` wrote (colours come back as uchar / 255), or one
+    whose faces are ``list uchar int|uint vertex_indices`` of three or four vertices (a quad is split (0,1,2), (0,2,3): how Replica's
+    ``mesh.ply`` comes)."""
     from .tsdf import TriangleMesh
     with open(path, "rb") as f:
         if f.readline().strip() != b"ply":
             raise ValueError(f"{path}: not a PLY file")
         nv = nf = 0
-        props, element = [], None
+        props, element, index_type = [], None, "<i4"
         while True:
             line = f.readline()
             if not line:
@@ -167,19 +206,19 @@ def load_mesh_ply(path: str, device="cpu"):
             elif tok[0] == "property" and element == "vertex":
                 props.append((tok[2], "<" + _PLY_TYPES[tok[1]]))
             elif tok[0] == "property" and element == "face":
-                if tok[1:] != ["list", "uchar", "int", "vertex_indices"]:
-                    raise ValueError(f"{path}: face property {tok[1:]} is not 'list uchar int vertex_indices'")
+                if (len(tok) != 5 or tok[1] != "list" or tok[2] not in ("uchar", "uint8") or tok[3] not in _PLY_INDEX_TYPES
+                        or tok[4] not in ("vertex_indices", "vertex_index")):
+                    raise ValueError(f"{path}: face property {tok[1:]} is not 'list uchar int|uint vertex_indices'")
+                index_type = _PLY_INDEX_TYPES[tok[3]]
             elif tok[0] == "end_header":
                 break
         vdt = np.dtype(props)
         vt = np.frombuffer(f.read(nv * vdt.itemsize), dtype=vdt, count=nv)
-        fdt = np.dtype([("n", "u1"), ("i", "<i4", (3,))])
-        ft = np.frombuffer(f.read(nf * fdt.itemsize), dtype=fdt, count=nf)
-    if nf and not (ft["n"] == 3).all():
-        raise ValueError(f"{path}: only triangles are read")
+        raw = f.read()
+    faces = _read_faces(path, raw, nf, index_type)
     v = np.stack([vt["x"], vt["y"], vt["z"]], axis=1).astype(np.float32).reshape(-1, 3)
     col = None
     if "red" in vt.dtype.names:
         col = (np.stack([vt["red"], vt["green"], vt["blue"]], axis=1).astype(np.float32) / 255.0).reshape(-1, 3)
-    return TriangleMesh(torch.from_numpy(v).to(device), torch.from_numpy(np.array(ft["i"], dtype=np.int32).reshape(-1, 3)).to(device),
+    return TriangleMesh(torch.from_numpy(v).to(device), torch.from_numpy(faces).to(device),
                         None if col is None else torch.from_numpy(col).to(device))

@@ -131,6 +131,43 @@ def room_surface_distance(points: torch.Tensor) -> torch.Tensor:
     return best.to(points.dtype)
 
 
+def room_rectangles():
+    """The room's true surfaces as axis-aligned rectangles ``(axis, side, (a, a_lo, a_hi), (b, b_lo, b_hi))``: the plane ``x[axis] =
+    side`` over ``[a_lo, a_hi] x [b_lo, b_hi]`` of the other two axes -- the six walls and the six faces of every box, from the tables
+    ``room_surface_distance`` uses (a box standing on the floor or against a wall keeps that face: it is part of the union's distance)."""
+    out = []
+    for lo, hi in [((-_ROOM_HALF[0], -_ROOM_HALF[1], -_ROOM_HALF[2]), _ROOM_HALF)] + list(_ROOM_BOXES):
+        for ax in range(3):
+            a, b = [i for i in range(3) if i != ax]
+            for side in (lo[ax], hi[ax]):
+                out.append((ax, float(side), (a, float(lo[a]), float(hi[a])), (b, float(lo[b]), float(hi[b]))))
+    return out
+
+
+def room_mesh(device, max_edge: float = 0.1, dtype=torch.float32):
+    """The room's true surfaces (``room_rectangles``) as a ``TriangleMesh`` without colours, every rectangle diced into a grid of cells
+    split along one diagonal so that no edge -- the diagonals included -- exceeds ``max_edge``: the visibility cull of
+    ``mesh_eval.seen_vertices`` is per vertex.  Vertices are computed in float64 and stored as ``dtype``."""
+    import numpy as np
+    from .tsdf import TriangleMesh
+    verts, tris, base = [], [], 0
+    cell = float(max_edge) / math.sqrt(2.0)
+    for ax, side, (a, a_lo, a_hi), (b, b_lo, b_hi) in room_rectangles():
+        na, nb = max(1, int(math.ceil((a_hi - a_lo) / cell - 1e-9))), max(1, int(math.ceil((b_hi - b_lo) / cell - 1e-9)))
+        A, B = np.meshgrid(np.linspace(a_lo, a_hi, na + 1), np.linspace(b_lo, b_hi, nb + 1), indexing="ij")
+        p = np.zeros(A.shape + (3,))
+        p[..., a], p[..., b], p[..., ax] = A, B, side
+        verts.append(p.reshape(-1, 3))
+        i, j = np.meshgrid(np.arange(na), np.arange(nb), indexing="ij")
+        v00 = (base + i * (nb + 1) + j).reshape(-1)
+        v10, v01, v11 = v00 + (nb + 1), v00 + 1, v00 + (nb + 1) + 1
+        tris.append(np.stack([np.stack([v00, v10, v11], 1), np.stack([v00, v11, v01], 1)], 1).reshape(-1, 3))
+        base += (na + 1) * (nb + 1)
+    v = torch.from_numpy(np.concatenate(verts)).to(dtype).to(device)
+    t = torch.from_numpy(np.concatenate(tris).astype(np.int32)).to(device)
+    return TriangleMesh(v, t, None)
+
+
 def make_room_sequence(n_frames: int, intrinsics="fr3_office", device="cuda:0", step_scale: float = 1.0,
                        with_segmentation: bool = False):
     """``n_frames`` RGB-D frames of the room along a smooth hand-held-like path (about 1 cm and 0.3 degrees per frame at

@@ -297,7 +297,9 @@ def _finish(s):
     iteration count, its first and last loss and ``object_layer.eval_segmentation`` over the run's frames.  ``mesh_path``: ``mesh`` =
     the final map fused from every keyframe into a TSDF volume of ``mesh_voxel`` metres over the map's bounds and written there as a
     triangle-mesh PLY (``tsdf.mesh_from_map``): ``path, vertices, triangles, voxel, integrate_ms, extract_ms`` and, on the synthetic
-    room, ``accuracy_mean_m`` (mean distance of the vertices to the room's true surfaces)."""
+    room, ``accuracy_mean_m`` (mean distance of the vertices to the room's true surfaces).  ``mesh_gt`` (a mesh PLY in the sequence's
+    world frame, or ``"room"`` for ``sequences.room_mesh``): ``mesh["reconstruction"]`` = ``mesh_eval.eval_reconstruction`` of the written
+    mesh against it, ``mesh_samples`` samples each, both culled by the keyframes (their estimated poses) and their depth images."""
     c, frames, gmap, intr, bg, mapper, kf_list = s.c, s.frames, s.gmap, s.intr, s.bg, s.mapper, s.kf_list
     _drop_tracking_graph(s)
     extra = {}
@@ -342,6 +344,17 @@ def _finish(s):
         if c.sequence is None and c.scene == "room" and m["vertices"]:
             from .sequences import room_surface_distance
             m["accuracy_mean_m"] = float(room_surface_distance(mesh.vertices).mean())
+        if c.mesh_gt is not None:        # (only then: the `mesh` entry of a run without it keeps exactly its keys)
+            from .mesh_eval import eval_reconstruction
+            if c.mesh_gt == "room":
+                from .sequences import room_mesh
+                gt = room_mesh(gmap._xyz.device)
+            else:
+                from .ply_io import load_mesh_ply
+                gt = load_mesh_ply(str(c.mesh_gt), device=gmap._xyz.device)
+            kfs = [frames[k] for k in kf_list]
+            depths = [f.depth for f in kfs] if c.sensor == "depth" else None     # (a monocular frame's depth is the all-zero image)
+            m["reconstruction"] = eval_reconstruction(mesh, gt, n_samples=int(c.mesh_samples), viewpoints=kfs, intr=intr, depths=depths)
         extra["mesh"] = m
     return extra
 
@@ -401,7 +414,7 @@ def run_slam(n_frames=12, intrinsics="fr3_office", tracking_itr_num=100, mapping
              scene="cloud", reference_densify=False, eager_probe=0, exclusive_device=False,
              kf_selection="interval", check_viewpoints_overlap=False, kf_trace=None, refine_iters=0, eval_render=False,
              sequence=None, nr_objects=None, sensor="depth", viewer_dir=None, viewer_modes=("rgb",), viewer_every=0,
-             learn_objects=0, mesh_path=None, mesh_voxel=0.02):
+             learn_objects=0, mesh_path=None, mesh_voxel=0.02, mesh_gt=None, mesh_samples=200_000):
     """Tracks and maps a sequence in one process; returns tracking / mapping rates, iterations and the trajectory error (``_report``).
     Every argument is described where it acts: ``_setup``, ``_track_frame``, ``_select_keyframe``, ``_map_keyframe``, ``_map_window``,
     ``_finish`` (what follows the last frame).  ``log``: a callable that gets a line per frame.  ``sensor="monocular"`` adds the result
@@ -410,7 +423,8 @@ def run_slam(n_frames=12, intrinsics="fr3_office", tracking_itr_num=100, mapping
     ``viewer_every``-th keyframe (0: never) and at the end; only then does the result hold a ``viewer`` entry.
     ``learn_objects=N`` (with ``nr_objects``): learn the object rows, N trainer iterations over the window after each mapping call; only
     then does the result hold an ``objects`` entry (iterations, first and last label loss, label accuracy and mIoU).
-    ``mesh_path``: write the final map's triangle mesh there (``_finish``); only then does the result hold a ``mesh`` entry."""
+    ``mesh_path``: write the final map's triangle mesh there (``_finish``); only then does the result hold a ``mesh`` entry;
+    with ``mesh_gt`` that entry gains ``reconstruction`` (``_finish``)."""
     s = _setup(SimpleNamespace(**locals()))              # (every argument, by name: must stay the first statement)
     for i, vp in enumerate(s.frames):
         if i == 0:

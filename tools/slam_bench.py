@@ -13,6 +13,8 @@ stand-in; the TUM / Replica sequences are not available offline).  Prints one JS
       # PNGs of what the reference's viewer window would show, from a camera behind the current pose (monogs_amd.viewer)
   python tools/slam_bench.py --config tum --room --graph --mesh room.ply [--mesh-voxel 0.02]
       # the final map fused from every keyframe into a TSDF volume and written as a coloured triangle mesh (monogs_amd.tsdf)
+  python tools/slam_bench.py --config tum --room --graph --mesh room.ply --mesh-gt room
+      # ... and scored against the ground-truth mesh: accuracy, completion, completion ratio, Chamfer-L1, F-score (monogs_amd.mesh_eval)
 """
 import argparse
 import json
@@ -79,7 +81,14 @@ if __name__ == "__main__":
                     help="after the run: fuse the final map from every keyframe into a TSDF volume over the map's bounds and write the "
                          "triangle mesh to PATH (binary PLY); the result gains `mesh`")
     ap.add_argument("--mesh-voxel", type=float, default=0.02, help="with --mesh: the voxel edge in metres")
+    ap.add_argument("--mesh-gt", default=None, metavar="PATH|room",
+                    help="with --mesh: the ground-truth mesh (a PLY in the sequence's world frame, e.g. Replica's mesh.ply; `room`: the "
+                         "--room scene's true surfaces); `mesh` gains `reconstruction`: accuracy, completion, completion ratio, Chamfer-L1, "
+                         "precision / recall / F-score between samples of both meshes, culled by the keyframes (monogs_amd.mesh_eval)")
+    ap.add_argument("--mesh-samples", type=int, default=200000, help="with --mesh-gt: samples per mesh")
     a = ap.parse_args()
+    if a.mesh_gt and not a.mesh:
+        ap.error("--mesh-gt evaluates the mesh --mesh writes")
     from monogs_amd.slam_harness import run_slam
     cfg = dict(CONFIGS[a.config])
     init_iters = a.init_iters
@@ -113,7 +122,8 @@ if __name__ == "__main__":
                    eager_probe=a.eager_probe, kf_selection=a.kf_selection, check_viewpoints_overlap=a.check_overlap,
                    refine_iters=a.refine, eval_render=a.eval, sensor=sensor, viewer_dir=a.viewer,
                    viewer_modes=tuple(a.viewer_modes), viewer_every=a.viewer_every, log=lambda s: print("[slam]", s, file=sys.stderr, flush=True), **objects, **cfg,
-                   **(dict(mesh_path=a.mesh, mesh_voxel=a.mesh_voxel) if a.mesh else {}))
+                   **(dict(mesh_path=a.mesh, mesh_voxel=a.mesh_voxel) if a.mesh else {}),
+                   **(dict(mesh_gt=a.mesh_gt, mesh_samples=a.mesh_samples) if a.mesh_gt else {}))
     what = f"{a.dataset}, every {a.stride}. frame" if a.dataset else f"synthetic {a.config}-like sequence"
     out["workload"] = f"{what}, {a.frames} frames" + (" (fork's hard-coded run configuration)" if a.fork else "")
     if sensor == "monocular":
