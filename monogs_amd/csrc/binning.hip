@@ -163,8 +163,7 @@ __global__ void __launch_bounds__(SCAN_THREADS) scan_small_kernel(const uint2* _
             }
             before = (uint32_t)w;
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) before += __shfl_xor(before, o, 64);
+        MGS_WAVE_REDUCE(before, MGS_WAVE_ADD);
         if (threadIdx.x == 0) s_prefix = before;
     }
     __syncthreads();
@@ -405,8 +404,7 @@ __global__ void __launch_bounds__(256) duplicate_kernel(int P, const uint2* __re
             }
             const uint32_t exc = inc - ntg;                                    // first slot of the Gaussian
             uint32_t Eg = valid ? inc : 0u;                                    // end of the group's slots = the largest inclusive sum
-#pragma unroll
-            for (int o2 = 32; o2 > 0; o2 >>= 1) Eg = max(Eg, (uint32_t)__shfl_xor((int)Eg, o2, 64));
+            MGS_WAVE_REDUCE(Eg, max);
             __builtin_amdgcn_wave_barrier();
             s_ent[wv][lane] = dup_entry(exc, gx0, gy0, gw, gx, idg); s_kf[wv][lane] = kfg;
             const uint32_t e = min(s1, Eg);

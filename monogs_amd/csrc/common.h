@@ -6,6 +6,7 @@
 #include <stddef.h>
 
 #include "../../include/monogs_raster.h"
+#include "wave_ops.h"          // wave reductions and scans, the reproducible workgroup sums
 
 namespace mgs {
 
@@ -40,6 +41,17 @@ enum : int {
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// Host: a bump allocator over one scratch buffer, every sub-buffer 256-byte aligned (the feature units' scratch; the forward's
+// named layout is api.hip's Carver).  The base is rounded up first; used() counts from the rounded base.
+struct ScratchCursor {
+    static constexpr size_t ALIGN = 256;
+    char *p0, *p;
+    explicit ScratchCursor(void* base) : p0((char*)align_up((size_t)base, ALIGN)), p(p0) {}
+    template <typename T>
+    T* take(size_t bytes) { char* r = p; p += align_up(bytes, ALIGN); return (T*)r; }
+    size_t used() const { return (size_t)(p - p0); }
+};
+
 // Wave-uniform read-only inputs (camera matrices, background colour): read through the CONSTANT address space, so the
 // backend always selects scalar loads (s_load_dwordx8/x16, all issued at once) for them.  Through a generic pointer
 // it falls back to per-lane vector loads with a vmcnt(0) wait after each group as soon as the kernel also stores to
@@ -58,18 +70,28 @@ typedef const unsigned long long* const_u64_p;
 #define MGS_CONST_U64(p) (p)
 #endif
 
-// ---- 64-lane inclusive scan (u32 add) on the DPP data path: 4 row shifts + 2 row broadcasts, ~60 cycles, instead of
-// six __shfl_up round trips through ds_bpermute (the LDS crossbar, >100 cycles each).
-__device__ __forceinline__ uint32_t wave_incl_scan_dpp(uint32_t v) {
-#define MGS_DPP_ADD(ctrl, row_mask) v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, ctrl, row_mask, 0xf, false)
-    MGS_DPP_ADD(0x111, 0xf);      // row_shr:1
-    MGS_DPP_ADD(0x112, 0xf);      // row_shr:2
-    MGS_DPP_ADD(0x114, 0xf);      // row_shr:4
-    MGS_DPP_ADD(0x118, 0xf);      // row_shr:8   -> inclusive within each row of 16
-    MGS_DPP_ADD(0x142, 0xa);      // row_bcast:15 into rows 1, 3
-    MGS_DPP_ADD(0x143, 0xc);      // row_bcast:31 into rows 2, 3
-#undef MGS_DPP_ADD
-    return v;
+// ---- a world point to its pixel: the ONE rule of TSDF integration (tsdf.hip) and the mesh visibility cull (mesheval.hip) ----
+// the rows of the world->camera transform, loaded from the transposed matrix of mgs_camera.viewmatrix
+struct ViewRows {
+    const float r00, r01, r02, tx, r10, r11, r12, ty, r20, r21, r22, tz;
+    __device__ __forceinline__ explicit ViewRows(const_float_p vm)
+        : r00(vm[0]), r01(vm[4]), r02(vm[8]), tx(vm[12]), r10(vm[1]), r11(vm[5]), r12(vm[9]), ty(vm[13]),
+          r20(vm[2]), r21(vm[6]), r22(vm[10]), tz(vm[14]) {}
+};
+// declares x, y, z: the camera-space point of the world point (px, py, pz).  (A statement: as an inlined function it came out with
+// the operands of two packed multiplies of tsdf_integrate_kernel exchanged.)
+#define MGS_TO_CAMERA(cam, px, py, pz, x, y, z)                              \
+    const float x = cam.r00 * px + cam.r01 * py + cam.r02 * pz + cam.tx,     \
+                y = cam.r10 * px + cam.r11 * py + cam.r12 * pz + cam.ty,     \
+                z = cam.r20 * px + cam.r21 * py + cam.r22 * pz + cam.tz
+// the pixel whose centre is nearest to the projection of the camera-space point (x, y, z), z > 0; false: outside the image
+__device__ __forceinline__ bool camera_pixel(float fx, float fy, float cx, float cy, int W, int H, float x, float y, float z,
+                                             size_t& pix) {
+    const float u = fx * x / z + cx - 0.5f, v = fy * y / z + cy - 0.5f;
+    const float fu = floorf(u + 0.5f), fv = floorf(v + 0.5f);
+    if (!(fu >= 0.f && fu < (float)W && fv >= 0.f && fv < (float)H)) return false;
+    pix = (size_t)(int)fv * W + (int)fu;
+    return true;
 }
 
 // ---- zero fill as a plain kernel ------------------------------------------------------------
@@ -371,5 +393,69 @@ void morton_bbox_extend(int P, const float* points, int32_t* bbox, hipStream_t s
 // the sorted codes lie (one of k.code_a / k.code_b)
 int morton_build(int P, const float* points, const int32_t* bbox, const MortonIndex& k, hipStream_t s,
                  const uint32_t** codes_sorted = nullptr);
+constexpr int KNN_BOX = 64;                 // points per Morton box = one wave of queries
+constexpr int KNN_GRID_MIN = 6144;          // below this many points the all-pairs sweep wins (no sort, no index).  Measured, round 2:
+                                            // 4 k points 0.147 vs 0.207 ms, 8 k 0.291 vs 0.246, 16 k 0.58 vs 0.33, 32 k 1.17 vs 0.36 ms
+constexpr float KNN_FLT_MAX = 3.402823466e+38f;
+// float <-> int whose signed order is the float order (for atomicMin / atomicMax)
+__device__ __forceinline__ int32_t f2ord(float f) { const int32_t i = __float_as_int(f); return i >= 0 ? i : i ^ 0x7FFFFFFF; }
+__device__ __forceinline__ float ord2f(int32_t i) { return __int_as_float(i >= 0 ? i : i ^ 0x7FFFFFFF); }
+__device__ __forceinline__ float gap(float lo, float hi, float qlo, float qhi) {   // distance between [lo,hi] and [qlo,qhi]
+    return fmaxf(0.f, fmaxf(lo - qhi, qlo - hi));
+}
+
+// The walk over the boxes of a Morton index by ONE WAVE for its 64 queries (lane: query q, `live` or a copy of the last one; the
+// wave's own bounds qlo / qhi; `cand[wv]`: the 64 float4 of LDS that belong to the wave).  A box is staged there between two wave
+// barriers and swept by all lanes as broadcasts.  The boxes are pruned 64 at a time (lane l: box base + l) against the wave's
+// bounds and the largest bound of its lanes, each survivor is re-checked per lane, swept if any lane needs it, and the wave's
+// maximum refreshed.  The lower bound of a box is the pair formula applied to coordinate gaps that rounding can only shrink
+// (c >= lo => fl(c - q) >= fl(lo - q), squares and fmas are monotone); the 0.99999 is an extra margin.  What differs between
+// the users is the policy:
+//   void take(const float4& c, const float4& q, int i, int b)    candidate i of box b against the lane's running result
+//   float bound() const                             the distance beyond which the lane has no use for a candidate
+//   static bool keep(float lower, float bound)      may a box (or lane) with this lower bound still matter?
+//   int seed(sweep)                                 sweeps a box and its two neighbours along the curve, returns the middle one
+//   void store(const float4& q) const               writes a live lane's result (inside the walk: behind it, the compiler lays the
+//                                                   loop's exit out differently from the kernels this was lifted from)
+template <typename Policy>
+__device__ __forceinline__ void morton_box_walk(Policy& pol, int P, int nb, const float4* sorted, const float4* box_lo,
+                                                const float4* box_hi, const float4& q, const float4& qlo, const float4& qhi,
+                                                bool live, int lane, float4 (*cand)[KNN_BOX], int wv) {
+    auto sweep = [&](int b) {                   // all 64 lanes against the (<= 64) points of box b
+        const int ci = b * KNN_BOX + lane;
+        __builtin_amdgcn_wave_barrier();
+        cand[wv][lane] = ci < P ? sorted[ci] : make_float4(KNN_FLT_MAX, KNN_FLT_MAX, KNN_FLT_MAX, 0.f);
+        __builtin_amdgcn_wave_barrier();
+        const int n = min(KNN_BOX, P - b * KNN_BOX);
+        for (int i = 0; i < n; ++i) {
+            const float4 c = cand[wv][i];
+            pol.take(c, q, i, b);
+        }
+    };
+    const int sb = pol.seed(sweep);
+    float wmax = wave_max(live ? pol.bound() : 0.f);     // no lane of the wave can still use a box farther than this
+    for (int base = 0; base < nb; base += 64) {
+        const int bi = base + lane;
+        bool want = bi < nb && (bi < sb - 1 || bi > sb + 1);
+        if (want) {
+            const float4 lo = box_lo[bi], hi = box_hi[bi];
+            const float gx = gap(lo.x, hi.x, qlo.x, qhi.x), gy = gap(lo.y, hi.y, qlo.y, qhi.y), gz = gap(lo.z, hi.z, qlo.z, qhi.z);
+            want = Policy::keep(fmaf(gz, gz, fmaf(gy, gy, gx * gx)) * 0.99999f, wmax);
+        }
+        unsigned long long mask = __builtin_amdgcn_ballot_w64(want);
+        while (mask) {
+            const int j = __builtin_ctzll(mask);
+            mask &= mask - 1;
+            const int b = base + j;                                  // wave-uniform
+            const float4 lo = box_lo[b], hi = box_hi[b];
+            const float gx = gap(lo.x, hi.x, q.x, q.x), gy = gap(lo.y, hi.y, q.y, q.y), gz = gap(lo.z, hi.z, q.z, q.z);
+            const bool need = live && Policy::keep(fmaf(gz, gz, fmaf(gy, gy, gx * gx)) * 0.99999f, pol.bound());
+            if (__builtin_amdgcn_ballot_w64(need) == 0ull) continue;
+            sweep(b);
+            wmax = wave_max(live ? pol.bound() : 0.f);
+        }
+    }
+    if (live) pol.store(q);
+}
 
 }  // namespace mgs

@@ -25,10 +25,7 @@ namespace mgs {
 
 constexpr int KNN_THREADS = 256;
 constexpr int KNN_TILE = 1024;
-constexpr int KNN_BOX = 64;                 // points per Morton box = one wave of queries
-constexpr int KNN_GRID_MIN = 6144;          // below this the all-pairs sweep wins (no sort, no index).  Measured, round 2:
-                                            // 4 k points 0.147 vs 0.207 ms, 8 k 0.291 vs 0.246, 16 k 0.58 vs 0.33, 32 k 1.17 vs 0.36 ms
-constexpr float KNN_FLT_MAX = 3.402823466e+38f;
+// (KNN_BOX, KNN_GRID_MIN, KNN_FLT_MAX: common.h, beside the index)
 
 // the ONE pair formula both paths use: pair_d2 (common.h; mesheval.hip's nearest neighbour uses it too)
 // insert d into the sorted triple (b0 <= b1 <= b2)
@@ -72,22 +69,16 @@ __global__ void __launch_bounds__(KNN_THREADS) knn_kernel(int P, const float* __
 MortonIndex morton_carve(void* base, int P) {
     MortonIndex k;
     const size_t n = (size_t)P, nb = (n + KNN_BOX - 1) / KNN_BOX;
-    char* p = (char*)align_up((size_t)base, 256);
-    char* p0 = p;
-    auto take = [&](size_t bytes) { char* r = p; p += align_up(bytes, 256); return r; };
-    k.bbox = (int32_t*)take(8 * sizeof(int32_t));
-    k.code_a = (uint32_t*)take(n * 4); k.code_b = (uint32_t*)take(n * 4);
-    k.idx_a = (uint32_t*)take(n * 4); k.idx_b = (uint32_t*)take(n * 4);
-    k.sorted = (float4*)take(n * 16);
-    k.box_lo = (float4*)take(nb * 16); k.box_hi = (float4*)take(nb * 16);
-    k.sort_temp = take(radix_temp_bytes(n, 32));
-    k.bytes = (size_t)(p - p0) + 256;
+    ScratchCursor c(base);
+    k.bbox = c.take<int32_t>(8 * sizeof(int32_t));
+    k.code_a = c.take<uint32_t>(n * 4); k.code_b = c.take<uint32_t>(n * 4);
+    k.idx_a = c.take<uint32_t>(n * 4); k.idx_b = c.take<uint32_t>(n * 4);
+    k.sorted = c.take<float4>(n * 16);
+    k.box_lo = c.take<float4>(nb * 16); k.box_hi = c.take<float4>(nb * 16);
+    k.sort_temp = c.take<void>(radix_temp_bytes(n, 32));
+    k.bytes = c.used() + ScratchCursor::ALIGN;
     return k;
 }
-
-// float <-> int whose signed order is the float order (for atomicMin / atomicMax)
-__device__ __forceinline__ int32_t f2ord(float f) { const int32_t i = __float_as_int(f); return i >= 0 ? i : i ^ 0x7FFFFFFF; }
-__device__ __forceinline__ float ord2f(int32_t i) { return __int_as_float(i >= 0 ? i : i ^ 0x7FFFFFFF); }
 
 __global__ void knn_bbox_init_kernel(int32_t* bbox) {
     if (threadIdx.x < 8) bbox[threadIdx.x] = threadIdx.x < 4 ? 0x7FFFFFFF : (int32_t)0x80000000;
@@ -104,13 +95,7 @@ __global__ void __launch_bounds__(KNN_THREADS) knn_bbox_kernel(int P, const floa
         }
     }
 #pragma unroll
-    for (int a = 0; a < 3; ++a) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            lo[a] = fminf(lo[a], __shfl_xor(lo[a], o, 64));
-            hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], o, 64));
-        }
-    }
+    for (int a = 0; a < 3; ++a) MGS_WAVE_REDUCE2(lo[a], fminf, hi[a], fmaxf);
     if ((threadIdx.x & 63) == 0) {
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
@@ -164,11 +149,7 @@ __global__ void __launch_bounds__(KNN_THREADS) knn_gather_kernel(int P, const fl
     for (int a = 0; a < 3; ++a) {
         lo[a] = live ? v[a] : KNN_FLT_MAX;
         hi[a] = live ? v[a] : -KNN_FLT_MAX;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            lo[a] = fminf(lo[a], __shfl_xor(lo[a], o, 64));
-            hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], o, 64));
-        }
+        MGS_WAVE_REDUCE2(lo[a], fminf, hi[a], fmaxf);
     }
     const int first = i & ~63;
     if ((threadIdx.x & 63) == 0 && first < P) {
@@ -177,14 +158,28 @@ __global__ void __launch_bounds__(KNN_THREADS) knn_gather_kernel(int P, const fl
     }
 }
 
-__device__ __forceinline__ float wave_max_f32(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ float gap(float lo, float hi, float qlo, float qhi) {   // distance between [lo,hi] and [qlo,qhi]
-    return fmaxf(0.f, fmaxf(lo - qhi, qlo - hi));
-}
+// the self-query's policy of the walk (morton_box_walk, common.h): the three best, the query itself excluded by position; a box
+// can only matter if its lower bound is below a third-best, and the strict < drops boxes that could at best tie
+struct KnnBest3 {
+    int qb, nb, lane;
+    float* out;
+    float b0, b1, b2;
+    __device__ __forceinline__ void take(const float4& c, const float4& q, int i, int b) {
+        float d = pair_d2(c.x, c.y, c.z, q.x, q.y, q.z);
+        d = (b == qb && i == lane) ? KNN_FLT_MAX : d;
+        insert3(d, b0, b1, b2);
+    }
+    __device__ __forceinline__ float bound() const { return b2; }
+    __device__ __forceinline__ void store(const float4& q) const { out[__float_as_uint(q.w)] = (b0 + b1 + b2) / 3.f; }
+    static __device__ __forceinline__ bool keep(float lower, float bound) { return lower < bound; }
+    template <typename Sweep>
+    __device__ __forceinline__ int seed(Sweep&& sweep) {             // the neighbourhood along the curve
+        sweep(qb);
+        if (qb > 0) sweep(qb - 1);
+        if (qb + 1 < nb) sweep(qb + 1);
+        return qb;
+    }
+};
 
 __global__ void __launch_bounds__(KNN_THREADS) knn_query_kernel(int P, int nb, const float4* __restrict__ sorted,
                                                                 const float4* __restrict__ box_lo,
@@ -197,52 +192,8 @@ __global__ void __launch_bounds__(KNN_THREADS) knn_query_kernel(int P, int nb, c
     const bool live = qi < P;
     const float4 q = sorted[live ? qi : P - 1];
     const float4 qlo = box_lo[qb], qhi = box_hi[qb];
-    float b0 = KNN_FLT_MAX, b1 = b0, b2 = b0;
-
-    auto sweep = [&](int b) {                   // all 64 lanes against the (<= 64) points of box b
-        const int ci = b * KNN_BOX + lane;
-        __builtin_amdgcn_wave_barrier();
-        cand[wv][lane] = ci < P ? sorted[ci] : make_float4(KNN_FLT_MAX, KNN_FLT_MAX, KNN_FLT_MAX, 0.f);
-        __builtin_amdgcn_wave_barrier();
-        const int n = min(KNN_BOX, P - b * KNN_BOX);
-        const int self = b == qb ? lane : -1;
-        for (int i = 0; i < n; ++i) {
-            const float4 c = cand[wv][i];
-            float d = pair_d2(c.x, c.y, c.z, q.x, q.y, q.z);
-            d = (i == self) ? KNN_FLT_MAX : d;
-            insert3(d, b0, b1, b2);
-        }
-    };
-    // seed from the neighbourhood along the curve
-    sweep(qb);
-    if (qb > 0) sweep(qb - 1);
-    if (qb + 1 < nb) sweep(qb + 1);
-    float wmax = wave_max_f32(live ? b2 : 0.f);     // no lane of the wave can still use a box farther than this
-
-    // A box can only matter if (a lower bound of) its distance is below a third-best; the 0.99999 absorbs the
-    // rounding difference between the bound and the pair formula, and the strict < drops boxes that could at best tie.
-    for (int base = 0; base < nb; base += 64) {
-        const int bi = base + lane;
-        bool want = bi < nb && (bi < qb - 1 || bi > qb + 1);
-        if (want) {
-            const float4 lo = box_lo[bi], hi = box_hi[bi];
-            const float gx = gap(lo.x, hi.x, qlo.x, qhi.x), gy = gap(lo.y, hi.y, qlo.y, qhi.y), gz = gap(lo.z, hi.z, qlo.z, qhi.z);
-            want = fmaf(gz, gz, fmaf(gy, gy, gx * gx)) * 0.99999f < wmax;
-        }
-        unsigned long long mask = __builtin_amdgcn_ballot_w64(want);
-        while (mask) {
-            const int j = __builtin_ctzll(mask);
-            mask &= mask - 1;
-            const int b = base + j;                                  // wave-uniform
-            const float4 lo = box_lo[b], hi = box_hi[b];
-            const float gx = gap(lo.x, hi.x, q.x, q.x), gy = gap(lo.y, hi.y, q.y, q.y), gz = gap(lo.z, hi.z, q.z, q.z);
-            const bool need = live && (fmaf(gz, gz, fmaf(gy, gy, gx * gx)) * 0.99999f < b2);
-            if (__builtin_amdgcn_ballot_w64(need) == 0ull) continue;
-            sweep(b);
-            wmax = wave_max_f32(live ? b2 : 0.f);
-        }
-    }
-    if (live) out[__float_as_uint(q.w)] = (b0 + b1 + b2) / 3.f;
+    KnnBest3 best{qb, nb, lane, out, KNN_FLT_MAX, KNN_FLT_MAX, KNN_FLT_MAX};
+    morton_box_walk(best, P, nb, sorted, box_lo, box_hi, q, qlo, qhi, live, lane, cand, wv);
 }
 
 int g_opt_knn_grid_min = -1;         // mgs_debug_set_option("knn_grid_min", n): tests force either path at any size

@@ -85,22 +85,6 @@ __device__ __forceinline__ void lb_store(float* __restrict__ plane, size_t q, co
     else plane[q] = g[0];
 }
 
-// sum over the workgroup, valid in thread 0 (fixed order: shuffles, then ((w0 + w1) + (w2 + w3)))
-__device__ __forceinline__ double lb_block_sum(double a, double* s_a) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
-    if ((threadIdx.x & 63) == 0) s_a[threadIdx.x >> 6] = a;
-    __syncthreads();
-    return (s_a[0] + s_a[1]) + (s_a[2] + s_a[3]);
-}
-__device__ __forceinline__ uint32_t lb_block_sum(uint32_t a, uint32_t* s_a) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) a += (uint32_t)__shfl_xor((int)a, o, 64);
-    if ((threadIdx.x & 63) == 0) s_a[threadIdx.x >> 6] = a;
-    __syncthreads();
-    return (s_a[0] + s_a[1]) + (s_a[2] + s_a[3]);
-}
-
 // ---- prepare: N ------------------------------------------------------------------------------------------------------
 template <bool VEC>
 __global__ void __launch_bounds__(LB_THREADS) label_count_kernel(const uint8_t* __restrict__ labels,
@@ -117,7 +101,7 @@ __global__ void __launch_bounds__(LB_THREADS) label_count_kernel(const uint8_t* 
 #pragma unroll
         for (int j = 0; j < PIX; ++j) n += on[j] ? 1u : 0u;
     }
-    n = lb_block_sum(n, s_n);
+    n = block_sum(n, s_n);
     if (threadIdx.x == 0) part[blockIdx.x] = n;
 }
 
@@ -126,7 +110,7 @@ __global__ void __launch_bounds__(LB_THREADS) label_count_finalize_kernel(const 
     __shared__ uint32_t s_n[4];
     uint32_t n = 0;
     for (int b = threadIdx.x; b < nb; b += LB_THREADS) n += part[b];
-    n = lb_block_sum(n, s_n);
+    n = block_sum(n, s_n);
     if (threadIdx.x == 0) { count_out[0] = n; count_out[1] = HW - n; }
 }
 
@@ -247,7 +231,7 @@ __global__ void __launch_bounds__(LB_THREADS) label_loss_kernel(const LabelArgs 
             }
         }
     }
-    acc = lb_block_sum(acc, s_a);
+    acc = block_sum(acc, s_a);
     if (threadIdx.x == 0) part[blockIdx.x] = acc;
 }
 
@@ -256,7 +240,7 @@ __global__ void __launch_bounds__(LB_THREADS) label_finalize_kernel(const double
     __shared__ double s_a[4];
     double a = 0.0;
     for (int b = threadIdx.x; b < nb; b += LB_THREADS) a += part[b];
-    a = lb_block_sum(a, s_a);
+    a = block_sum(a, s_a);
     if (threadIdx.x == 0) loss[0] = count[0] ? (float)(a / (double)count[0]) : 0.f;
 }
 
@@ -294,9 +278,9 @@ __global__ void __launch_bounds__(LB_THREADS) label_confusion_kernel(const int32
             if (c) atomicAdd(&counts[i], c);
         }
     }
-    unseen = lb_block_sum(unseen, s_n);
+    unseen = block_sum(unseen, s_n);
     __syncthreads();
-    skipped = lb_block_sum(skipped, s_n);
+    skipped = block_sum(skipped, s_n);
     if (threadIdx.x == 0) {
         if (unseen) atomicAdd(&side[0], unseen);
         if (skipped) atomicAdd(&side[1], skipped);

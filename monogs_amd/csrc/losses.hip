@@ -111,9 +111,7 @@ __global__ void __launch_bounds__(LS_THREADS) loss_forward_kernel(LossArgs a, fl
     // in the order ((w0 + w1) + (w2 + w3)) by seven threads)
     float v7[LP_SUMS] = {acc.s_rgb, acc.c_rgb, acc.s_d, acc.c_d, acc.s_op, acc.u_a, acc.u_b};
 #pragma unroll
-    for (int k = 0; k < LP_SUMS; ++k)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v7[k] += __shfl_xor(v7[k], o, 64);
+    for (int k = 0; k < LP_SUMS; ++k) MGS_WAVE_REDUCE(v7[k], MGS_WAVE_ADD);
     __shared__ float s_w[4][LP_SUMS];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     if (lane == 0) {
@@ -157,25 +155,10 @@ __device__ __forceinline__ LossScalars loss_scalars(const LossArgs& a, const flo
     return r;
 }
 
-// one wave: sum the per-workgroup partials in a fixed order (lane l adds blocks l, l+64, ...: bitwise reproducible)
-__device__ __forceinline__ void sum_partials(const float* __restrict__ part, int nblocks, int lane, float v[LP_SUMS]) {
-#pragma unroll
-    for (int k = 0; k < LP_SUMS; ++k) v[k] = 0.f;
-    for (int b = lane; b < nblocks; b += WAVE) {
-        const float* o = part + LP_N + (size_t)b * LP_PART;
-#pragma unroll
-        for (int k = 0; k < LP_SUMS; ++k) v[k] += o[k];
-    }
-#pragma unroll
-    for (int k = 0; k < LP_SUMS; ++k)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o, 64);
-}
-
 __global__ void loss_finalize_kernel(LossArgs a, int nblocks, float* __restrict__ part, float* __restrict__ loss_out) {
     const int lane = threadIdx.x;
     float v[LP_SUMS];
-    sum_partials(part, nblocks, lane, v);
+    wave_sum_rows(part + LP_N, LP_PART, nblocks, lane, v);
     if (lane == 0) {
         const LossScalars r = loss_scalars(a, v);
         part[LP_L1_RGB] = r.l1_rgb;
@@ -204,7 +187,7 @@ __global__ void __launch_bounds__(LS_THREADS) loss_backward_kernel(LossArgs a, f
     if (fwd_blocks > 0) {
         if (threadIdx.x < WAVE) {
             float v[LP_SUMS];
-            sum_partials(part, fwd_blocks, (int)threadIdx.x, v);
+            wave_sum_rows(part + LP_N, LP_PART, fwd_blocks, (int)threadIdx.x, v);
             if (threadIdx.x == 0) {
                 const LossScalars r = loss_scalars(a, v);
                 s_scale[0] = r.scale_rgb; s_scale[1] = r.scale_d;

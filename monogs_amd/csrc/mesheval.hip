@@ -6,7 +6,7 @@
 // reproducible from call to call: minima and integer sums do not depend on order, the double sums are taken in a fixed order.
 //
 // mgs_nn_dist2, two paths, bit-identical in d2 and index (a minimum of the same float32 numbers, ties to the smaller index):
-//   * P < NN_GRID_MIN targets: an LDS-tiled all-pairs sweep, one query per lane, tiles of 1024 targets read back as broadcasts
+//   * P < KNN_GRID_MIN targets: an LDS-tiled all-pairs sweep, one query per lane, tiles of 1024 targets read back as broadcasts
 //     (knn_kernel's shape).  The threshold is the one knn.hip measured for its own two paths (6144): per query both pairs of
 //     paths trade the same P pair tests against the same sort + index build.
 //   * more targets: the Morton-box index of knn.hip over the JOINT bounding box of queries and targets, built once for the targets
@@ -21,9 +21,6 @@ namespace mgs {
 
 constexpr int NN_THREADS = 256;
 constexpr int NN_TILE = 1024;
-constexpr int NN_BOX = 64;                  // = KNN_BOX: the boxes morton_build cuts
-constexpr int NN_GRID_MIN = 6144;           // = KNN_GRID_MIN (see above)
-constexpr float NN_FLT_MAX = 3.402823466e+38f;
 
 // one candidate against the running (best, index): smaller distance, or the same distance at a smaller index
 __device__ __forceinline__ void nn_take(float d, int ti, float& best, int& bi) {
@@ -59,15 +56,6 @@ __global__ void __launch_bounds__(NN_THREADS) nn_all_pairs_kernel(int Q, int P, 
     }
 }
 
-__device__ __forceinline__ float nn_wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ float nn_gap(float lo, float hi, float qlo, float qhi) {   // distance between [lo,hi] and [qlo,qhi]
-    return fmaxf(0.f, fmaxf(lo - qhi, qlo - hi));
-}
-
 struct NnQueryArgs {
     int Q, P, nbq, nbt;
     const float4 *qsorted, *qlo, *qhi;         // the queries' index: sorted points, bounds of each run of 64
@@ -78,71 +66,52 @@ struct NnQueryArgs {
     int32_t* index;
 };
 
-__global__ void __launch_bounds__(NN_THREADS) nn_query_kernel(const NnQueryArgs a) {
-    __shared__ float4 cand[NN_THREADS / 64][NN_BOX];
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int qb = blockIdx.x * (NN_THREADS / 64) + wv;             // this wave's run of 64 queries
-    if (qb >= a.nbq) return;                                        // whole wave; no block-level barrier below
-    const int qi = qb * NN_BOX + lane;
-    const bool live = qi < a.Q;
-    const float4 q = a.qsorted[live ? qi : a.Q - 1];
-    const float4 qlo = a.qlo[qb], qhi = a.qhi[qb];
-    float best = __int_as_float(0x7f800000);
-    int bi = -1;
-
-    auto sweep = [&](int b) {                   // all 64 lanes against the (<= 64) points of target box b
-        const int ci = b * NN_BOX + lane;
-        __builtin_amdgcn_wave_barrier();
-        cand[wv][lane] = ci < a.P ? a.tsorted[ci] : make_float4(NN_FLT_MAX, NN_FLT_MAX, NN_FLT_MAX, 0.f);
-        __builtin_amdgcn_wave_barrier();
-        const int n = min(NN_BOX, a.P - b * NN_BOX);
-        for (int i = 0; i < n; ++i) {
-            const float4 c = cand[wv][i];
-            nn_take(pair_d2(c.x, c.y, c.z, q.x, q.y, q.z), (int)__float_as_uint(c.w), best, bi);
-        }
-    };
-    // seed: the target box where the wave's first query falls along the curve (first sorted target code >= its code)
-    const uint32_t code0 = a.qcode[qb * NN_BOX];
-    int lo = 0, hi = a.P;
-    while (lo < hi) {
-        const int mid = (int)(((unsigned)lo + (unsigned)hi) >> 1);
-        if (a.tcode[mid] < code0) lo = mid + 1;
-        else hi = mid;
+// the cross-set policy of the walk (morton_box_walk, common.h): one best with the smaller index; a box is dropped only when its
+// lower bound EXCEEDS the best (<= keeps it), since a box that could tie may hold the smaller index
+struct NnBest1 {
+    const NnQueryArgs& a;
+    int qb;
+    float best;
+    int bi;
+    __device__ __forceinline__ void take(const float4& c, const float4& q, int, int) {
+        nn_take(pair_d2(c.x, c.y, c.z, q.x, q.y, q.z), (int)__float_as_uint(c.w), best, bi);
     }
-    const int sb = __builtin_amdgcn_readfirstlane(min(lo, a.P - 1) / NN_BOX);
-    sweep(sb);
-    if (sb + 1 < a.nbt) sweep(sb + 1);
-    if (sb > 0) sweep(sb - 1);
-    float wmax = nn_wave_max(live ? best : 0.f);    // no lane of the wave can still use a box farther than this
-
-    // The bound is the pair formula applied to coordinate gaps that rounding can only shrink (c >= lo => fl(c - q) >= fl(lo - q),
-    // squares and fmas are monotone), so bound <= every distance into the box; the 0.99999 is knn.hip's extra margin.
-    for (int base = 0; base < a.nbt; base += 64) {
-        const int bx = base + lane;
-        bool want = bx < a.nbt && (bx < sb - 1 || bx > sb + 1);
-        if (want) {
-            const float4 l = a.tlo[bx], h = a.thi[bx];
-            const float gx = nn_gap(l.x, h.x, qlo.x, qhi.x), gy = nn_gap(l.y, h.y, qlo.y, qhi.y), gz = nn_gap(l.z, h.z, qlo.z, qhi.z);
-            want = fmaf(gz, gz, fmaf(gy, gy, gx * gx)) * 0.99999f <= wmax;
-        }
-        unsigned long long mask = __builtin_amdgcn_ballot_w64(want);
-        while (mask) {
-            const int j = __builtin_ctzll(mask);
-            mask &= mask - 1;
-            const int b = base + j;                                  // wave-uniform
-            const float4 l = a.tlo[b], h = a.thi[b];
-            const float gx = nn_gap(l.x, h.x, q.x, q.x), gy = nn_gap(l.y, h.y, q.y, q.y), gz = nn_gap(l.z, h.z, q.z, q.z);
-            const bool need = live && (fmaf(gz, gz, fmaf(gy, gy, gx * gx)) * 0.99999f <= best);
-            if (__builtin_amdgcn_ballot_w64(need) == 0ull) continue;
-            sweep(b);
-            wmax = nn_wave_max(live ? best : 0.f);
-        }
-    }
-    if (live) {
+    __device__ __forceinline__ float bound() const { return best; }
+    __device__ __forceinline__ void store(const float4& q) const {
         const uint32_t o = __float_as_uint(q.w);                     // back in the caller's order
         a.d2[o] = best;
         if (a.index) a.index[o] = bi;
     }
+    static __device__ __forceinline__ bool keep(float lower, float bound) { return lower <= bound; }
+    // the target box where the wave's first query falls along the curve (first sorted target code >= its code), and its neighbours
+    template <typename Sweep>
+    __device__ __forceinline__ int seed(Sweep&& sweep) {
+        const uint32_t code0 = a.qcode[qb * KNN_BOX];
+        int hi = a.P, lo = 0;                    // (hi first: the other order exchanges the operands of the midpoint's add)
+        while (lo < hi) {
+            const int mid = (int)(((unsigned)lo + (unsigned)hi) >> 1);
+            if (a.tcode[mid] < code0) lo = mid + 1;
+            else hi = mid;
+        }
+        const int sb = __builtin_amdgcn_readfirstlane(min(lo, a.P - 1) / KNN_BOX);
+        sweep(sb);
+        if (sb + 1 < a.nbt) sweep(sb + 1);
+        if (sb > 0) sweep(sb - 1);
+        return sb;
+    }
+};
+
+__global__ void __launch_bounds__(NN_THREADS) nn_query_kernel(const NnQueryArgs a) {
+    __shared__ float4 cand[NN_THREADS / 64][KNN_BOX];
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int qb = blockIdx.x * (NN_THREADS / 64) + wv;             // this wave's run of 64 queries
+    if (qb >= a.nbq) return;                                        // whole wave; no block-level barrier below
+    const int qi = qb * KNN_BOX + lane;
+    const bool live = qi < a.Q;
+    const float4 q = a.qsorted[live ? qi : a.Q - 1];
+    const float4 qlo = a.qlo[qb], qhi = a.qhi[qb];
+    NnBest1 r{a, qb, __int_as_float(0x7f800000), -1};
+    morton_box_walk(r, a.P, a.nbt, a.tsorted, a.tlo, a.thi, q, qlo, qhi, live, lane, cand, wv);
 }
 
 __global__ void __launch_bounds__(NN_THREADS) nn_empty_kernel(int Q, float* __restrict__ d2, int32_t* __restrict__ index) {
@@ -155,9 +124,9 @@ __global__ void __launch_bounds__(NN_THREADS) nn_empty_kernel(int Q, float* __re
 struct NnScratch { MortonIndex t, q; size_t bytes; };
 static NnScratch nn_carve(void* base, int Q, int P) {
     NnScratch s;
-    char* p = (char*)align_up((size_t)base, 256);
-    s.t = morton_carve(p, P);
-    s.q = morton_carve(p + s.t.bytes, Q);
+    ScratchCursor c(base);
+    s.t = morton_carve(c.p0, P);
+    s.q = morton_carve(c.p0 + s.t.bytes, Q);
     s.bytes = s.t.bytes + s.q.bytes + 256;
     return s;
 }
@@ -177,19 +146,15 @@ struct MeshSampleScratch {
 };
 static MeshSampleScratch ms_carve(void* base, size_t T) {
     const size_t Tp = align_up(T ? T : 1, MS_SCAN_ITEMS), nb = Tp / MS_SCAN_ITEMS;
-    char* p = (char*)align_up((size_t)base, 256);
-    char* p0 = p;
+    ScratchCursor c(base);
     MeshSampleScratch s;
-    auto take = [&](size_t n) { char* q = p; p += align_up(n, 256); return q; };
-    s.bbox = (int32_t*)take(8 * sizeof(int32_t));
-    s.incl = (uint64_t*)take(Tp * 8);
-    s.blk = (uint64_t*)take(nb * 8);
-    s.total = (uint64_t*)take(8);
-    s.bytes = (size_t)(p - p0) + 256;
+    s.bbox = c.take<int32_t>(8 * sizeof(int32_t));
+    s.incl = c.take<uint64_t>(Tp * 8);
+    s.blk = c.take<uint64_t>(nb * 8);
+    s.total = c.take<uint64_t>(8);
+    s.bytes = c.used() + ScratchCursor::ALIGN;
     return s;
 }
-
-__device__ __forceinline__ float ms_ord2f(int32_t i) { return __int_as_float(i >= 0 ? i : i ^ 0x7FFFFFFF); }
 
 // The fixed-point scale of the areas, a power of two: with D2 the squared diagonal of the vertices' bounding box no triangle is
 // larger than D2 / 2 < 2^(eD - 1) and T <= 2^eT, so every sum of areas stays below 2^(eT + eD - 1); the scale 2^(61 - eT - eD)
@@ -199,7 +164,7 @@ __device__ __forceinline__ double ms_scale(const int32_t* __restrict__ bbox, int
     double d2 = 0.0;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        const double e = (double)ms_ord2f(bbox[4 + a]) - (double)ms_ord2f(bbox[a]);
+        const double e = (double)ord2f(bbox[4 + a]) - (double)ord2f(bbox[a]);
         d2 += e * e;
     }
     int eD = 0, eT = 0;
@@ -233,15 +198,6 @@ __global__ void __launch_bounds__(MS_THREADS) mesh_area_kernel(int V, int T, con
     area_q[t] = q;
 }
 
-__device__ __forceinline__ uint64_t ms_wave_incl_scan(uint64_t v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint64_t u = (uint64_t)__shfl_up((unsigned long long)v, o, 64);
-        v += lane >= o ? u : 0ull;
-    }
-    return v;
-}
-
 // block-local inclusive scan in place; a thread owns 8 consecutive items, items at index >= T count as 0
 __global__ void __launch_bounds__(MS_THREADS) mesh_scan_local_kernel(uint64_t* __restrict__ incl, uint64_t* __restrict__ blk, int T) {
     __shared__ uint64_t s_w[MS_THREADS / WAVE];
@@ -253,7 +209,7 @@ __global__ void __launch_bounds__(MS_THREADS) mesh_scan_local_kernel(uint64_t* _
         x[n] = sum;
     }
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const uint64_t in = ms_wave_incl_scan(sum, lane);
+    const uint64_t in = wave_incl_scan_u64(sum, lane);
     if (lane == 63) s_w[wv] = in;
     __syncthreads();
     uint64_t before = in - sum, total = 0ull;
@@ -276,7 +232,7 @@ __global__ void __launch_bounds__(MS_SCANB_THREADS) mesh_scan_blocks_kernel(uint
     for (uint32_t b0 = 0; b0 < nb; b0 += MS_SCANB_THREADS) {
         const uint32_t b = b0 + threadIdx.x;
         const uint64_t x = b < nb ? blk[b] : 0ull;
-        const uint64_t in = ms_wave_incl_scan(x, lane);
+        const uint64_t in = wave_incl_scan_u64(x, lane);
         if (lane == 63) s_w[wv] = in;
         __syncthreads();
         uint64_t before = carry, total = 0ull;
@@ -348,21 +304,15 @@ struct MarkSeenArgs {
 __global__ void __launch_bounds__(256) mesh_mark_seen_kernel(const MarkSeenArgs a) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= a.V) return;
-    const_float_p vm = MGS_CONST(a.view);
-    const float r00 = vm[0], r01 = vm[4], r02 = vm[8], tx = vm[12];
-    const float r10 = vm[1], r11 = vm[5], r12 = vm[9], ty = vm[13];
-    const float r20 = vm[2], r21 = vm[6], r22 = vm[10], tz = vm[14];
+    const ViewRows cam(MGS_CONST(a.view));
     const float px = a.vert[3 * (size_t)i], py = a.vert[3 * (size_t)i + 1], pz = a.vert[3 * (size_t)i + 2];
-    // the transform, projection and pixel rule of tsdf_integrate_kernel (tsdf.hip), expression for expression
-    const float x = r00 * px + r01 * py + r02 * pz + tx;
-    const float y = r10 * px + r11 * py + r12 * pz + ty;
-    const float z = r20 * px + r21 * py + r22 * pz + tz;
+    // the transform, projection and pixel rule of tsdf_integrate_kernel (tsdf.hip): the same two statements
+    MGS_TO_CAMERA(cam, px, py, pz, x, y, z);
     if (!(z > 0.f && z >= a.depth_min) || (a.depth_max > 0.f && z > a.depth_max)) return;
-    const float u = a.fx * x / z + a.cx - 0.5f, v = a.fy * y / z + a.cy - 0.5f;
-    const float fu = floorf(u + 0.5f), fv = floorf(v + 0.5f);
-    if (!(fu >= 0.f && fu < (float)a.W && fv >= 0.f && fv < (float)a.H)) return;
+    size_t pix;
+    if (!camera_pixel(a.fx, a.fy, a.cx, a.cy, a.W, a.H, x, y, z, pix)) return;
     if (a.depth) {
-        const float d = a.depth[(size_t)(int)fv * a.W + (int)fu];
+        const float d = a.depth[pix];
         if (!(d > 0.f) || !(z <= d + a.eps)) return;
     }
     a.seen[i] = 1;                                                    // the lane owns its byte: a plain store, earlier views stay
@@ -380,17 +330,12 @@ struct ReconArgs {
     double* out;              // [2 + K]
 };
 
-__device__ __forceinline__ double rm_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 // sums of the block's RM_SLOTS values in a fixed order (wave butterfly, then waves 0..3): thread 0 holds them
 __device__ __forceinline__ void rm_block_sum(double (&v)[RM_SLOTS], double (*s_w)[RM_SLOTS]) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #pragma unroll
     for (int k = 0; k < RM_SLOTS; ++k) {
-        v[k] = rm_wave_sum(v[k]);
+        v[k] = wave_sum(v[k]);
         if (lane == 0) s_w[wv][k] = v[k];
     }
     __syncthreads();
@@ -448,7 +393,7 @@ using namespace mgs;
 
 extern "C" {
 
-int32_t mgs_nn_grid_min(void) { return NN_GRID_MIN; }
+int32_t mgs_nn_grid_min(void) { return KNN_GRID_MIN; }
 
 size_t mgs_nn_scratch_bytes(int32_t Q, int32_t P) {
     if (Q <= 0 || P <= 0) return 256;
@@ -471,7 +416,7 @@ int mgs_nn_dist2(int32_t Q, int32_t P, const float* queries, const float* target
         MGS_HIP(hipGetLastError());
         return 0;
     }
-    const bool morton = (flags & MGS_NN_FORCE_MORTON) || (!(flags & MGS_NN_FORCE_ALL_PAIRS) && P >= NN_GRID_MIN);
+    const bool morton = (flags & MGS_NN_FORCE_MORTON) || (!(flags & MGS_NN_FORCE_ALL_PAIRS) && P >= KNN_GRID_MIN);
     if (!morton) {
         hipLaunchKernelGGL(nn_all_pairs_kernel, dim3(qblocks), dim3(NN_THREADS), 0, s, Q, P, queries, targets, d2, index);
         MGS_HIP(hipGetLastError());
@@ -486,7 +431,7 @@ int mgs_nn_dist2(int32_t Q, int32_t P, const float* queries, const float* target
     NnQueryArgs a;
     if (int rc = morton_build(P, targets, bbox, k.t, s, &a.tcode)) return rc;
     if (int rc = morton_build(Q, queries, bbox, k.q, s, &a.qcode)) return rc;
-    a.Q = Q; a.P = P; a.nbq = (Q + NN_BOX - 1) / NN_BOX; a.nbt = (P + NN_BOX - 1) / NN_BOX;
+    a.Q = Q; a.P = P; a.nbq = (Q + KNN_BOX - 1) / KNN_BOX; a.nbt = (P + KNN_BOX - 1) / KNN_BOX;
     a.qsorted = k.q.sorted; a.qlo = k.q.box_lo; a.qhi = k.q.box_hi;
     a.tsorted = k.t.sorted; a.tlo = k.t.box_lo; a.thi = k.t.box_hi;
     a.d2 = d2; a.index = index;

@@ -11,7 +11,7 @@
 // inside a buffer) takes the scalar path, one pixel of three planes per thread.
 //
 // Sums: per-workgroup partials + a finalize that adds them in a fixed order (thread t: partials t, t + 256, ...; then the
-// fixed tree of mt_block_sum).  No atomics, no clear launch: bitwise reproducible.
+// fixed tree of block_sum, wave_ops.h).  No atomics, no clear launch: bitwise reproducible.
 // Error: the partials are carried in DOUBLE (full rate on this part, and the kernel is bound by memory).  c - gt of two floats
 // is exact in double, its square and every add round at 2^-53, so sum / count carries <= (n + 2) 2^-53 relative
 // (n < 2^31 terms, all of one sign: no cancellation) ~ 2.4e-7 at the very worst, 1e-10 at SLAM sizes; the stored float mse adds
@@ -34,17 +34,6 @@ __device__ __forceinline__ void mt_term(float c, float g, double& acc, uint32_t&
 }
 
 __device__ __forceinline__ uint32_t mt_u8(float c) { return (uint32_t)(uint8_t)(c * 255.0f); }
-
-// sum over the workgroup; valid in every thread (fixed order: shuffles, then ((w0 + w1) + (w2 + w3)))
-__device__ __forceinline__ void mt_block_sum(double& a, uint32_t& n, double* s_a, uint32_t* s_n) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); n += __shfl_xor(n, o, 64); }
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (lane == 0) { s_a[wv] = a; s_n[wv] = n; }
-    __syncthreads();
-    a = (s_a[0] + s_a[1]) + (s_a[2] + s_a[3]);
-    n = (s_n[0] + s_n[1]) + (s_n[2] + s_n[3]);
-}
 
 template <bool VEC>
 __global__ void __launch_bounds__(MT_THREADS) metrics_kernel(const float* render, const float* gt, float* clamped, uint8_t* u8,
@@ -86,7 +75,7 @@ __global__ void __launch_bounds__(MT_THREADS) metrics_kernel(const float* render
             mt_term(c0, g0, acc, cnt); mt_term(c1, g1, acc, cnt); mt_term(c2, g2, acc, cnt);
         }
     }
-    mt_block_sum(acc, cnt, s_a, s_n);
+    block_sum(acc, cnt, s_a, s_n);
     if (threadIdx.x == 0) { part_sum[blockIdx.x] = acc; part_cnt[blockIdx.x] = cnt; }
 }
 
@@ -99,7 +88,7 @@ __global__ void __launch_bounds__(MT_THREADS) metrics_finalize_kernel(const doub
     double a = 0.0;
     uint32_t n = 0;
     for (int b = threadIdx.x; b < nb; b += MT_THREADS) { a += part_sum[b]; n += part_cnt[b]; }
-    mt_block_sum(a, n, s_a, s_n);
+    block_sum(a, n, s_a, s_n);
     if (threadIdx.x == 0) {
         const double nan = __longlong_as_double(0x7ff8000000000000ll);
         const double mse = n ? a / (double)n : nan;

@@ -51,19 +51,14 @@ struct PseudoDepthArgs {
 // the workgroup's sum to its row of partials: wave sums by shuffles, the four waves' sums through LDS, ((w0 + w1) + (w2 + w3))
 __device__ __forceinline__ void pd_store_partial(double v, double* __restrict__ row) {
     __shared__ double s_w[PD_THREADS / 64];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) row[blockIdx.x] = (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
+    v = block_sum(v, s_w);
+    if (threadIdx.x == 0) row[blockIdx.x] = v;
 }
-// one wave adds the G partials in a fixed order (lane l: rows l, l + 64, ...), every lane gets the total
+// one wave adds the G partials in a fixed order, every lane gets the total
 __device__ __forceinline__ double pd_sum_partials(const double* __restrict__ part, int G, int lane) {
-    double v = 0.0;
-    for (int b = lane; b < G; b += 64) v += part[b];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
+    double v[1];
+    wave_sum_rows(part, 1, G, lane, v);
+    return v[0];
 }
 
 __device__ __forceinline__ float pd_select(const PseudoDepthArgs& a, float d, float op, bool rgb_ok) {

@@ -449,12 +449,6 @@ struct BwdArgs {
     int rot_aligned16, drot_aligned16;     // rotations / dL_drotations may be accessed 16 bytes at a time
 };
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // SH = false: colours are precomputed (MonoGS's path) -- the spherical-harmonics backward is compiled out,
 // which takes the kernel from 168 to far fewer VGPRs (occupancy) on the path that matters.
 template <bool SH, bool COV>

@@ -59,17 +59,6 @@ __device__ __forceinline__ float ssim_outside(int p, int n) {
     return q;
 }
 
-// sum over the workgroup of two values; the result is valid in thread 0 (fixed order: shuffles, then ((w0 + w1) + (w2 + w3)))
-__device__ __forceinline__ void ssim_block_sum2(float& a, float& b, float (*s_red)[4]) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); }
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (lane == 0) { s_red[0][wv] = a; s_red[1][wv] = b; }
-    __syncthreads();
-    a = (s_red[0][0] + s_red[0][1]) + (s_red[0][2] + s_red[0][3]);
-    b = (s_red[1][0] + s_red[1][1]) + (s_red[1][2] + s_red[1][3]);
-}
-
 // one pixel of the map from its five shifted statistics (a1, a2, g*x'^2, g*y'^2, g*x'y'); returns its share of the sum and,
 // with TRAIN, stores the three derivatives (zero where the pixel is not averaged).  BORDER = false: q = 0, nothing to correct.
 // Reciprocals are v_rcp_f32 (1 ulp): the map's error stays ~1e-7, three orders under the bar, for a third of the
@@ -222,7 +211,7 @@ __global__ void __launch_bounds__(SS_THREADS) ssim_forward_kernel(SsimArgs a, fl
             }
         }
     }
-    ssim_block_sum2(sum, l1, s_red);
+    block_sum(sum, l1, s_red[0], s_red[1]);
     if (tid == 0) {
         const size_t wg = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
         part[2 * wg] = sum;
@@ -230,14 +219,14 @@ __global__ void __launch_bounds__(SS_THREADS) ssim_forward_kernel(SsimArgs a, fl
     }
 }
 
-// one workgroup: thread t adds partials t, t + 256, ... in order, then the fixed tree of ssim_block_sum2
+// one workgroup: thread t adds partials t, t + 256, ... in order, then the fixed tree of block_sum (wave_ops.h)
 __global__ void __launch_bounds__(SS_THREADS) ssim_finalize_kernel(const float* __restrict__ part, int nwg, float count,
                                                                    float count_l1, float lambda, int refine,
                                                                    float* __restrict__ hdr, float* __restrict__ value_out) {
     __shared__ float s_red[2][4];
     float s = 0.f, l = 0.f;
     for (int b = threadIdx.x; b < nwg; b += SS_THREADS) { s += part[2 * (size_t)b]; l += part[2 * (size_t)b + 1]; }
-    ssim_block_sum2(s, l, s_red);
+    block_sum(s, l, s_red[0], s_red[1]);
     if (threadIdx.x == 0) {
         const float ssim = s / count, l1 = l / count_l1;
         const float loss = (1.f - lambda) * l1 + lambda * (1.f - ssim);

@@ -172,19 +172,6 @@ __global__ void __launch_bounds__(ST_THREADS) stereo_vsum_kernel(const uint16_t*
 }
 
 // ---- path aggregation (step 4) -----------------------------------------------------------------------------------------------
-// minimum over the 64 lanes, returned to every lane: four row shifts, two row broadcasts, one lane read
-__device__ __forceinline__ uint32_t st_wave_min(uint32_t v) {
-#define MGS_DPP_MIN(ctrl, row_mask) v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, ctrl, row_mask, 0xf, false))
-    MGS_DPP_MIN(0x111, 0xf);      // row_shr:1
-    MGS_DPP_MIN(0x112, 0xf);      // row_shr:2
-    MGS_DPP_MIN(0x114, 0xf);      // row_shr:4
-    MGS_DPP_MIN(0x118, 0xf);      // row_shr:8   -> lane 15 of each row holds the row's minimum
-    MGS_DPP_MIN(0x142, 0xa);      // row_bcast:15 into rows 1, 3
-    MGS_DPP_MIN(0x143, 0xc);      // row_bcast:31 into rows 2, 3 -> lane 63 holds the wave's
-#undef MGS_DPP_MIN
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
-}
-
 // Directions: 0 from the left, 1 from up-left, 2 from above, 3 from up-right, 4 from the right.  A path is the maximal run of
 // valid pixels along its direction; path k < W1 (directions 1..3) starts in the top row at column k, the others on the side
 // edge the direction enters through, at row k - W1 + 1.
@@ -235,7 +222,7 @@ __global__ void __launch_bounds__(ST_THREADS) stereo_path_kernel(const uint32_t*
             if (i + u < len) {                       // (wave-uniform)
                 const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp((int)ST_INF, (int)L, 0x138, 0xf, 0xf, false);   // wave_shr:1: L(q, d-1)
                 const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp((int)ST_INF, (int)L, 0x130, 0xf, 0xf, false);   // wave_shl:1: L(q, d+1)
-                const uint32_t m = st_wave_min(L);
+                const uint32_t m = wave_min_dpp(L);
                 const uint32_t best = min(min(L, m + P2), min(lo, hi) + P1);
                 L = live ? c[u] + best - m : ST_INF;
                 if (live) sp[(long long)(i + u) * step] = sv[u] + L;
@@ -253,7 +240,7 @@ __global__ void __launch_bounds__(ST_THREADS) stereo_winner_kernel(const uint32_
     if (p >= n_pix) return;                          // (wave-uniform)
     const bool live = lane < dm.D;
     const uint32_t s = live ? sum[p * dm.D + lane] : 0u;
-    const uint32_t kmin = st_wave_min(live ? (s << 6) | (uint32_t)lane : 0xffffffffu);
+    const uint32_t kmin = wave_min_dpp(live ? (s << 6) | (uint32_t)lane : 0xffffffffu);
     const int best = (int)(kmin & 63u);
     const int ms = (int)(kmin >> 6);
     const bool bad = live && (int)s * (100 - uniq) < ms * 100 && abs(best - lane) > 1;
@@ -352,17 +339,16 @@ struct StereoScratch {
 static StereoScratch st_carve(void* base, int W, int H, int D) {
     const size_t HW = (size_t)W * H, HW1 = (size_t)(W - D) * H, vol = HW1 * D;
     StereoScratch s;
-    size_t o = 0;
-    auto take = [&](size_t n) { char* p = (char*)base + o; o += align_up(n, 256); return p; };
-    s.rect_l = (uint8_t*)take(HW); s.rect_r = (uint8_t*)take(HW);
-    s.trip_l = (uint2*)take(HW * sizeof(uint2)); s.trip_r = (uint2*)take(HW * sizeof(uint2));
-    s.cost = (uint32_t*)take(vol * sizeof(uint32_t));
-    s.sum = (uint32_t*)take(vol * sizeof(uint32_t));
-    s.min_s = (int32_t*)take(HW1 * sizeof(int32_t));
-    s.best_d = (int16_t*)take(HW1 * sizeof(int16_t));
-    s.d16 = (int16_t*)take(HW1 * sizeof(int16_t));
-    s.disp2 = (int16_t*)take(HW * sizeof(int16_t));
-    s.bytes = o;
+    ScratchCursor c(base);
+    s.rect_l = c.take<uint8_t>(HW); s.rect_r = c.take<uint8_t>(HW);
+    s.trip_l = c.take<uint2>(HW * sizeof(uint2)); s.trip_r = c.take<uint2>(HW * sizeof(uint2));
+    s.cost = c.take<uint32_t>(vol * sizeof(uint32_t));
+    s.sum = c.take<uint32_t>(vol * sizeof(uint32_t));
+    s.min_s = c.take<int32_t>(HW1 * sizeof(int32_t));
+    s.best_d = c.take<int16_t>(HW1 * sizeof(int16_t));
+    s.d16 = c.take<int16_t>(HW1 * sizeof(int16_t));
+    s.disp2 = c.take<int16_t>(HW * sizeof(int16_t));
+    s.bytes = c.used();
     return s;
 }
 
@@ -416,7 +402,7 @@ int mgs_stereo_depth(const MgsStereo* p, void* stream) {
 
     hipStream_t st = (hipStream_t)stream;
     const StereoDims dm{p->width, p->height, D, p->width - D};
-    StereoScratch sc = st_carve((void*)align_up((size_t)p->scratch, 256), dm.W, dm.H, D);
+    StereoScratch sc = st_carve(p->scratch, dm.W, dm.H, D);
     const size_t HW = (size_t)dm.W * dm.H, HW1 = (size_t)dm.W1 * dm.H;
     const dim3 block256(ST_THREADS);
 

@@ -36,11 +36,7 @@ struct TdsLds {
 __device__ __forceinline__ void tds_minmax(uint32_t lo, uint32_t hi, uint32_t* s_red /* >= 2 * TDS_WAVES */, uint32_t& mn,
                                            uint32_t& mx) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        lo = min(lo, (uint32_t)__shfl_xor((int)lo, o, 64));
-        hi = max(hi, (uint32_t)__shfl_xor((int)hi, o, 64));
-    }
+    MGS_WAVE_REDUCE2(lo, min, hi, max);
     if (lane == 0) { s_red[wv] = lo; s_red[TDS_WAVES + wv] = hi; }
     __syncthreads();
     mn = s_red[0]; mx = s_red[TDS_WAVES];
@@ -215,8 +211,7 @@ __device__ __forceinline__ uint32_t tile_depth_sort(const TileSortArgs& ts, uint
             const uint32_t e = (uint32_t)(wv * (TDS_ITEMS * WAVE) + i * WAVE + lane);
             c += (e < n && d[i] == DEPTH_KEY_NARROW) ? 1u : 0u;
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) c += (uint32_t)__shfl_xor((int)c, o, 64);
+        MGS_WAVE_REDUCE(c, MGS_WAVE_ADD);
         if (lane == 0) lds.red[wv] = c;
         __syncthreads();
         uint32_t m = 0;

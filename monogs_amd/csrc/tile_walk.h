@@ -29,16 +29,6 @@ __device__ __forceinline__ bool falloff_active(bool in_walk, float power, float 
     return in_walk && !(power > 0.f) && !(alpha < ALPHA_MIN);
 }
 
-// ---- wave plumbing ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t bcast(uint32_t v, int lane) {
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, lane);
-}
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o, 64));
-    return v;
-}
-
 // ---- the quadrant of a wave ------------------------------------------------------------------------------------------------
 struct Quadrant {
     int qx0i, qy0i;         // first pixel of the quadrant (wave-uniform when `wave` is)

@@ -29,7 +29,6 @@ constexpr int TS_THREADS = 256;                 // 4 waves: 4 bricks
 constexpr int TS_SCAN_ITEMS = 2048;             // per scan block: 256 threads x 8 consecutive bytes
 constexpr int TS_SCAN_SHIFT = 11;
 constexpr int TS_SCANB_THREADS = 1024;
-constexpr size_t TS_ALIGN = 256;
 
 // ---- scratch of the extraction ------------------------------------------------------------------------------------------
 struct TsdfScratch {
@@ -46,18 +45,17 @@ struct TsdfScratch {
 // Np = N rounded up to whole scan blocks: the scans read and write whole blocks (the pad is masked by index, never trusted)
 static TsdfScratch tsdf_carve(void* base, size_t N) {
     const size_t Np = align_up(N, TS_SCAN_ITEMS), nb = Np / TS_SCAN_ITEMS;
-    char* p = (char*)align_up((size_t)base, TS_ALIGN);
+    ScratchCursor c(base);
     TsdfScratch s;
-    auto take = [&](size_t n) { char* q = p; p += align_up(n, TS_ALIGN); return q; };
-    s.cls = (uint8_t*)take(Np);
-    s.valid = (uint8_t*)take(Np);
-    s.tcnt = (uint8_t*)take(Np);
-    s.emask = (uint8_t*)take(Np);
-    s.vloc = (uint32_t*)take(Np * 4);
-    s.tloc = (uint32_t*)take(Np * 4);
-    s.vblk = (uint32_t*)take(nb * 4);
-    s.tblk = (uint32_t*)take(nb * 4);
-    s.bytes = (size_t)(p - (char*)base) + TS_ALIGN;
+    s.cls = c.take<uint8_t>(Np);
+    s.valid = c.take<uint8_t>(Np);
+    s.tcnt = c.take<uint8_t>(Np);
+    s.emask = c.take<uint8_t>(Np);
+    s.vloc = c.take<uint32_t>(Np * 4);
+    s.tloc = c.take<uint32_t>(Np * 4);
+    s.vblk = c.take<uint32_t>(nb * 4);
+    s.tblk = c.take<uint32_t>(nb * 4);
+    s.bytes = c.used() + ScratchCursor::ALIGN;      // (read only from a sizing call, whose base is NULL: the slack of rounding the base up)
     return s;
 }
 
@@ -95,10 +93,7 @@ struct TsdfIntegrateArgs {
 __global__ void __launch_bounds__(TS_THREADS) tsdf_integrate_kernel(const TsdfIntegrateArgs a) {
     int i0, j, k;
     if (!tsdf_brick(a.g, i0, j, k)) return;
-    const_float_p vm = MGS_CONST(a.view);
-    const float r00 = vm[0], r01 = vm[4], r02 = vm[8], tx = vm[12];
-    const float r10 = vm[1], r11 = vm[5], r12 = vm[9], ty = vm[13];
-    const float r20 = vm[2], r21 = vm[6], r22 = vm[10], tz = vm[14];
+    const ViewRows cam(MGS_CONST(a.view));
     const float s = a.g.s;
     const float py = a.g.oy + s * (float)j, pz = a.g.oz + s * (float)k;
     if (a.cull) {
@@ -107,9 +102,7 @@ __global__ void __launch_bounds__(TS_THREADS) tsdf_integrate_kernel(const TsdfIn
         const int n = min(WAVE, a.g.nx - i0);
         const float half = 0.5f * s * (float)(n - 1);
         const float mx = a.g.ox + s * (float)i0 + half;
-        const float X = r00 * mx + r01 * py + r02 * pz + tx;
-        const float Y = r10 * mx + r11 * py + r12 * pz + ty;
-        const float Z = r20 * mx + r21 * py + r22 * pz + tz;
+        MGS_TO_CAMERA(cam, mx, py, pz, X, Y, Z);
         const float rad = half * 1.001f + 0.01f * s + 1e-4f * (fabsf(X) + fabsf(Y) + fabsf(Z) + 1.f);
         if (Z + rad < a.depth_min) return;                                       // step 1 fails for every voxel
         if (a.depth_max > 0.f && Z - rad > a.depth_max + a.trunc) return;        // d <= depth_max: sdf < -trunc for every voxel
@@ -127,14 +120,10 @@ __global__ void __launch_bounds__(TS_THREADS) tsdf_integrate_kernel(const TsdfIn
     const int i = i0 + (int)(threadIdx.x & 63);
     if (i >= a.g.nx) return;
     const float px = a.g.ox + s * (float)i;
-    const float x = r00 * px + r01 * py + r02 * pz + tx;
-    const float y = r10 * px + r11 * py + r12 * pz + ty;
-    const float z = r20 * px + r21 * py + r22 * pz + tz;
+    MGS_TO_CAMERA(cam, px, py, pz, x, y, z);
     if (!(z > a.depth_min)) return;                                              // 1
-    const float u = a.fx * x / z + a.cx - 0.5f, v = a.fy * y / z + a.cy - 0.5f;  // 2
-    const float fu = floorf(u + 0.5f), fv = floorf(v + 0.5f);
-    if (!(fu >= 0.f && fu < (float)a.W && fv >= 0.f && fv < (float)a.H)) return;
-    const size_t pix = (size_t)(int)fv * a.W + (int)fu;
+    size_t pix;
+    if (!camera_pixel(a.fx, a.fy, a.cx, a.cy, a.W, a.H, x, y, z, pix)) return;   // 2
     float d = a.depth[pix];                                                      // 3
     if (a.opacity) {
         const float al = a.opacity[pix];

@@ -157,8 +157,7 @@ __global__ void __launch_bounds__(256) viewer_max_kernel(const float* __restrict
         const float v = src[i];
         m = max(m, v > 0.f ? __float_as_uint(v) : 0u);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, 64));
+    m = wave_max_u32(m);
     if ((threadIdx.x & 63) == 0 && m != 0u) atomicMax(word, m);
 }
 
