@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define MGS_ABI_VERSION 24
+#define MGS_ABI_VERSION 25
 #define MGS_TILE 16 /* tile edge in pixels; ranges are per 16x16 tile */
 
 /* GaussianRasterizationSettings, minus `prefiltered` / `debug` which are call flags
@@ -964,6 +964,54 @@ int mgs_mesh_mark_seen(int32_t V, const float* vertices /* [V,3] */, const float
 size_t mgs_recon_metrics_scratch_bytes(void);
 int mgs_recon_metrics(int32_t Q, const float* d2 /* [Q] */, int32_t K, const float* thresholds /* host [K] */,
                       double* out /* device [2 + K] */, void* scratch, void* stream);
+
+/* ---- Triangle-mesh rendering and the Depth L1 metric (ABI v25) ---------------------------------------------------------
+ * The specification is DESIGN.md, "Mesh rendering" (tests/mesh_render_mirror.py restates it in float64).
+ * mgs_mesh_render: an indexed triangle mesh seen by a pinhole camera.  A world vertex goes to camera space with `viewmatrix` (the
+ * device matrix of mgs_camera.viewmatrix; never read on the host); pixel (px, py) looks along d = ((px + 0.5 - cx) / fx,
+ * (py + 0.5 - cy) / fy, 1).  For camera-space vertices v0, v1, v2: w0 = d . (v1 x v2), w1 = d . (v2 x v0), w2 = d . (v0 x v1),
+ * S = w0 + w1 + w2; the ray hits iff S != 0 and all w >= 0 or all w <= 0 (with MGS_MESH_ONE_SIDED: only S < 0); z = (w0 z0 + w1 z1
+ * + w2 z2) / S, accepted iff z >= near (a near <= 0 counts as the smallest positive float) and (far <= 0 or z <= far).  Projective:
+ * no clipping.  An edge's cross product is formed from its endpoints in ascending vertex-index order and then given the sign of
+ * the direction of travel, so triangles that share an edge by index leave no gap.  Per pixel the accepted hit with the smallest
+ * float32 z wins, on equal bits the smallest triangle index (the minimum of bits(z) << 32 | triangle: independent of the order of
+ * execution and of the triangles, bitwise reproducible).  Outputs: depth [H][W] (0: no hit), tri_id [H][W] (-1), rgb [3][H][W]
+ * (sum wi ci / S of the vertex colours; bg), label [H][W] (face_labels[tri_id]; -1); each but depth may be NULL.  A triangle that
+ * names a vertex outside [0, V) is skipped before any vertex is loaded and raises bit 0 of *status (device word, zeroed by the
+ * caller).  Six launches (T == 0: two, the empty image), no host synchronisation, capturable in a hipGraph.  `scratch`:
+ * mgs_mesh_render_scratch_bytes(T, W, H) bytes, a pure function (256 for sizes the entry point refuses).
+ * mgs_depth_l1: row[0] = sum of |a - b| over the pixels where both images are > 0 (and, with max_depth > 0, both <= max_depth),
+ * row[1] = their number, row[2] = the number of pixels with b > 0; device doubles, sums in a fixed order, counts exact.
+ * `scratch`: mgs_depth_l1_scratch_bytes() bytes.
+ * Refused with 1 and a message before any launch: negative sizes, V or T beyond 2^30, an image size of zero or above
+ * MGS_MESH_RENDER_MAX_IMAGE, non-positive fx or fy, a NULL required pointer, rgb wanted without colors, label wanted without
+ * face_labels, unknown flags. */
+#define MGS_MESH_ONE_SIDED 1
+#define MGS_MESH_NO_SMALL 2       /* test flag: no triangle is rasterised by the setup kernel (the image is bit-identical) */
+#define MGS_MESH_RENDER_MAX_IMAGE 16384
+typedef struct mgs_mesh_render_params {
+    int32_t V, T;
+    const float* vertices;        /* [V,3] world */
+    const int32_t* triangles;     /* [T,3] */
+    const float* colors;          /* [V,3] or NULL */
+    const int32_t* face_labels;   /* [T] or NULL */
+    const float* viewmatrix;      /* device, 16 floats, transposed world->camera */
+    int32_t W, H;
+    float fx, fy, cx, cy;
+    float near, far;
+    int32_t flags;                /* 0, or MGS_MESH_ONE_SIDED | MGS_MESH_NO_SMALL */
+    float bg[3];
+    float* depth;                 /* [H][W] */
+    int32_t* tri_id;              /* [H][W] or NULL */
+    float* rgb;                   /* [3][H][W] or NULL */
+    int32_t* label;               /* [H][W] or NULL */
+    uint32_t* status;             /* device word */
+} MgsMeshRender;
+size_t mgs_mesh_render_scratch_bytes(int32_t T, int32_t W, int32_t H);
+int mgs_mesh_render(const MgsMeshRender* params, void* scratch, void* stream);
+size_t mgs_depth_l1_scratch_bytes(void);
+int mgs_depth_l1(int32_t W, int32_t H, const float* a /* [H][W] */, const float* b /* [H][W] */, float max_depth,
+                 double* row /* device [3] */, void* scratch, void* stream);
 
 #ifdef __cplusplus
 }

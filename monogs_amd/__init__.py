@@ -29,4 +29,8 @@ def __getattr__(name):
     if name in ("nearest_distance", "sample_mesh", "seen_vertices", "cull_mesh", "eval_reconstruction", "recon_metrics"):
         from . import mesh_eval
         return getattr(mesh_eval, name)
+    # mesh rendering and Depth L1 (monogs_amd.mesh_render) likewise
+    if name in ("MeshRenderer", "render_mesh", "eval_depth_l1", "depth_l1_row"):
+        from . import mesh_render
+        return getattr(mesh_render, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -11,7 +11,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MGS_LIB_PATH") or os.path.join(_HERE, "lib", "libmonogs_raster.so")   # (override: kernel experiments)
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 c_float_p = C.c_void_p   # device pointers travel as integers (tensor.data_ptr())
 
@@ -66,6 +66,13 @@ class MgsTsdfFrame(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("depth", C.c_void_p), ("opacity", C.c_void_p), ("rgb", C.c_void_p),
                 ("viewmatrix", C.c_void_p)] + [(n, C.c_float) for n in (
                     "fx", "fy", "cx", "cy", "trunc", "depth_min", "depth_max", "opacity_min", "max_weight")] + [("flags", C.c_int32)]
+
+
+class MgsMeshRender(C.Structure):
+    _fields_ = [("V", C.c_int32), ("T", C.c_int32)] + [(n, C.c_void_p) for n in (
+        "vertices", "triangles", "colors", "face_labels", "viewmatrix")] + [("W", C.c_int32), ("H", C.c_int32)] + [
+            (n, C.c_float) for n in ("fx", "fy", "cx", "cy", "near", "far")] + [("flags", C.c_int32), ("bg", C.c_float * 3)] + [
+                (n, C.c_void_p) for n in ("depth", "tri_id", "rgb", "label", "status")]
 
 
 class MgsPseudoDepthParams(C.Structure):
@@ -172,6 +179,10 @@ SIGNATURES = {
                            + [C.c_float] * 3 + [C.c_void_p, C.c_void_p]),
     "mgs_recon_metrics_scratch_bytes": (C.c_size_t, []),
     "mgs_recon_metrics": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mgs_mesh_render_scratch_bytes": (C.c_size_t, [C.c_int32] * 3),
+    "mgs_mesh_render": (C.c_int, [C.POINTER(MgsMeshRender), C.c_void_p, C.c_void_p]),
+    "mgs_depth_l1_scratch_bytes": (C.c_size_t, []),
+    "mgs_depth_l1": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -18,6 +18,7 @@
 // one rounding of 2^-24 = 6e-8.  The psnr is formed from the double mse, then rounded once.  The count is an exact integer
 // (uint32; stored as float in the row: exact up to 2^24 elements, 5.5 megapixels).
 #include "common.h"
+#include "mesh_render.h"     // mesh rendering: what the Depth L1 below compares (kernels, launcher, entry points)
 
 namespace mgs {
 
@@ -104,6 +105,44 @@ static int metrics_blocks(size_t HW) {       // four pixels (twelve elements) pe
 }
 static size_t metrics_cnt_offset(int nb) { return (size_t)nb * sizeof(double); }
 
+// ---- Depth L1 between two depth images (eval_depth_l1): per-workgroup partials, one finishing workgroup -----------------------
+// |a - b| of two floats is exact in double; the sums run in a fixed order (block_sum), the counts are integers.
+__global__ void __launch_bounds__(MT_THREADS) depth_l1_partial_kernel(const float* __restrict__ a, const float* __restrict__ b,
+                                                                      size_t HW, float max_depth, double* __restrict__ part_sum,
+                                                                      uint32_t* __restrict__ part_cnt) {
+    __shared__ double s_a[4];
+    __shared__ uint32_t s_n[4], s_m[4];
+    double acc = 0.0;
+    uint32_t both = 0, in_b = 0;
+    for (size_t p = (size_t)blockIdx.x * MT_THREADS + threadIdx.x; p < HW; p += (size_t)gridDim.x * MT_THREADS) {
+        const float x = a[p], y = b[p];
+        const bool on = x > 0.f && y > 0.f && (!(max_depth > 0.f) || (x <= max_depth && y <= max_depth));
+        acc += on ? fabs((double)x - (double)y) : 0.0;
+        both += on ? 1u : 0u;
+        in_b += y > 0.f ? 1u : 0u;
+    }
+    block_sum(acc, both, s_a, s_n);
+    in_b = block_sum(in_b, s_m);
+    if (threadIdx.x == 0) { part_sum[blockIdx.x] = acc; part_cnt[2 * blockIdx.x] = both; part_cnt[2 * blockIdx.x + 1] = in_b; }
+}
+
+__global__ void __launch_bounds__(MT_THREADS) depth_l1_finish_kernel(const double* __restrict__ part_sum,
+                                                                     const uint32_t* __restrict__ part_cnt, int nb,
+                                                                     double* __restrict__ row) {
+    __shared__ double s_a[4];
+    __shared__ uint32_t s_n[4], s_m[4];
+    double acc = 0.0;
+    uint32_t both = 0, in_b = 0;                 // (an image holds at most 2^28 pixels)
+    for (int i = threadIdx.x; i < nb; i += MT_THREADS) { acc += part_sum[i]; both += part_cnt[2 * i]; in_b += part_cnt[2 * i + 1]; }
+    block_sum(acc, both, s_a, s_n);
+    in_b = block_sum(in_b, s_m);
+    if (threadIdx.x == 0) { row[0] = acc; row[1] = (double)both; row[2] = (double)in_b; }
+}
+static int depth_l1_blocks(size_t HW) {
+    const size_t nb = (HW + MT_THREADS * 4 - 1) / (MT_THREADS * 4);
+    return (int)(nb < 1 ? 1 : (nb > MT_MAX_BLOCKS ? MT_MAX_BLOCKS : nb));
+}
+
 }  // namespace mgs
 
 using namespace mgs;
@@ -135,6 +174,27 @@ int mgs_image_metrics(int32_t width, int32_t height, const float* render, const 
     else
         hipLaunchKernelGGL(metrics_kernel<false>, dim3(nb), dim3(MT_THREADS), 0, s, render, gt, clamped_out, u8_out, HW, part_sum, part_cnt);
     hipLaunchKernelGGL(metrics_finalize_kernel, dim3(1), dim3(MT_THREADS), 0, s, part_sum, part_cnt, nb, row_out);
+    MGS_HIP(hipGetLastError());
+    return 0;
+}
+
+size_t mgs_depth_l1_scratch_bytes(void) { return (size_t)MT_MAX_BLOCKS * (sizeof(double) + 2 * sizeof(uint32_t)) + 256; }
+
+int mgs_depth_l1(int32_t W, int32_t H, const float* a, const float* b, float max_depth, double* row, void* scratch, void* stream) {
+    const char* who = "mgs_depth_l1";
+    if (W < 1 || H < 1 || W > MGS_MESH_RENDER_MAX_IMAGE || H > MGS_MESH_RENDER_MAX_IMAGE) {
+        set_error("%s: the image must be 1 .. %d pixels wide and high", who, MGS_MESH_RENDER_MAX_IMAGE);
+        return 1;
+    }
+    if (!a || !b || !row || !scratch) { set_error("%s: a, b, row and scratch must be non-NULL", who); return 1; }
+    const size_t HW = (size_t)W * H;
+    const int nb = depth_l1_blocks(HW);
+    ScratchCursor c(scratch);
+    double* part_sum = c.take<double>((size_t)MT_MAX_BLOCKS * sizeof(double));
+    uint32_t* part_cnt = c.take<uint32_t>((size_t)MT_MAX_BLOCKS * 2 * sizeof(uint32_t));
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(depth_l1_partial_kernel, dim3(nb), dim3(MT_THREADS), 0, s, a, b, HW, max_depth, part_sum, part_cnt);
+    hipLaunchKernelGGL(depth_l1_finish_kernel, dim3(1), dim3(MT_THREADS), 0, s, part_sum, part_cnt, nb, row);
     MGS_HIP(hipGetLastError());
     return 0;
 }

@@ -114,15 +114,35 @@ def _view_of(vp, intr):
     return cached_camera_tensors(vp, vp.R, vp.T, intr.projection_matrix)[0]
 
 
-def seen_vertices(mesh, viewpoints, intr, depths=None, depth_min: float = 0.01, depth_max: float = 0.0, occlusion_eps: float = 0.03):
+def render_depths(mesh, viewpoints, intr):
+    """One depth image [H,W] per view of ``mesh`` rendered from it (``mesh_render.MeshRenderer``): the occlusion test of
+    ``depths="render"``.  ``viewpoints`` as in ``seen_vertices``."""
+    from .mesh_render import MeshRenderer
+    renderer = MeshRenderer(intr, mesh.vertices.device)
+    out = []
+    for vp in viewpoints:
+        R, T = (vp[0], vp[1]) if isinstance(vp, (tuple, list)) else (vp, None)
+        out.append(renderer.render(mesh, R, T)["depth"].clone())
+    return out
+
+
+def seen_vertices(mesh, viewpoints, intr, depths=None, depth_min: float = 0.01, depth_max: float = 0.0, occlusion_eps: float = 0.03,
+                  occluder=None):
     """bool [V]: the vertices some view sees -- camera-space ``z`` in ``[depth_min, depth_max]`` (``depth_max <= 0``: no far limit), the
     pixel of ``TSDFVolume.integrate`` inside the image and, with ``depths`` (one [H,W] image per view), ``depth > 0`` there and
-    ``z <= depth + occlusion_eps``.  ``viewpoints``: objects with ``.R``, ``.T`` (world->camera) or ``(R, T)`` pairs.  One launch per view."""
+    ``z <= depth + occlusion_eps``.  ``depths="render"``: the images are the mesh ``occluder`` rendered from every view
+    (``render_depths``).  ``viewpoints``: objects with ``.R``, ``.T`` (world->camera) or ``(R, T)`` pairs.  One launch per view."""
     lib = _lib.load()
     v = _points(mesh.vertices, "mesh.vertices")
     dev = v.device
     H, W = int(intr.height), int(intr.width)
     viewpoints = list(viewpoints)
+    if isinstance(depths, str):
+        if depths != "render":
+            raise ValueError(f'depths must be None, a list of images or "render", got {depths!r}')
+        if occluder is None:
+            raise ValueError('depths="render" needs the mesh to render as occluder=')
+        depths = render_depths(occluder, viewpoints, intr)
     if depths is not None and len(depths) != len(viewpoints):
         raise ValueError("depths must hold one image per viewpoint")
     seen = torch.zeros(v.shape[0], dtype=torch.uint8, device=dev)
@@ -183,13 +203,18 @@ def eval_reconstruction(rec, gt, n_samples: int = 200_000, threshold: float = 0.
     """Accuracy (mean distance reconstruction -> ground truth), completion (ground truth -> reconstruction), completion ratio (share
     of ground-truth samples within ``threshold``), Chamfer-L1 (the mean of the first two) and precision / recall / F-score at
     ``threshold``, between ``n_samples`` samples of each mesh (seeds ``seed`` and ``seed + 1``).  With ``viewpoints`` (and ``intr``,
-    optionally ``depths``) both meshes are first culled: only triangles with a vertex ``seen_vertices`` reports are sampled (``cull_mesh``'s rule).  ``readbacks`` is 1: the result vector
+    optionally ``depths``) both meshes are first culled: only triangles with a vertex ``seen_vertices`` reports are sampled (``cull_mesh``'s rule);
+    ``depths="render"``: the ground-truth mesh rendered from each viewpoint is the occlusion test for both.  ``readbacks`` is 1: the result vector
     (sums, counts, areas, status words).  ``return_samples``: also ``rec_samples``, ``gt_samples``, ``rec_d2``, ``gt_d2`` (device)."""
     keep_rec = keep_gt = None
+    if isinstance(depths, str) and depths != "render":
+        raise ValueError(f'depths must be None, a list of images or "render", got {depths!r}')
     if viewpoints is not None:
         if intr is None:
             raise ValueError("culling by viewpoints needs the intrinsics")
         viewpoints = list(viewpoints)
+        if isinstance(depths, str):
+            depths = render_depths(gt, viewpoints, intr)
         # (cull_mesh's rule as the sampler's keep mask: indexing the triangles by it would read their number back)
         keep_rec = seen_vertices(rec, viewpoints, intr, depths, **cull_kw)[rec.triangles.long()].any(dim=1)
         keep_gt = seen_vertices(gt, viewpoints, intr, depths, **cull_kw)[gt.triangles.long()].any(dim=1)

@@ -144,20 +144,37 @@ def room_rectangles():
     return out
 
 
-def room_mesh(device, max_edge: float = 0.1, dtype=torch.float32):
-    """The room's true surfaces (``room_rectangles``) as a ``TriangleMesh`` without colours, every rectangle diced into a grid of cells
+def _room_grids(max_edge: float):
+    """``room_rectangles`` with the dicing of ``room_mesh``: ``(rectangle number, axis, side, (a, a_lo, a_hi), (b, b_lo, b_hi), na, nb)``."""
+    cell = float(max_edge) / math.sqrt(2.0)
+    for n, (ax, side, (a, a_lo, a_hi), (b, b_lo, b_hi)) in enumerate(room_rectangles()):
+        na, nb = max(1, int(math.ceil((a_hi - a_lo) / cell - 1e-9))), max(1, int(math.ceil((b_hi - b_lo) / cell - 1e-9)))
+        yield n, ax, side, (a, a_lo, a_hi), (b, b_lo, b_hi), na, nb
+
+
+def _rectangle_surface_id(n: int, ax: int) -> int:
+    """The id ``raycast_room(with_ids=True)`` reports for rectangle ``n`` of ``room_rectangles``: walls ``2 axis + (the + side)``,
+    the faces of box ``k`` ``6 + 3 k + axis``."""
+    return 2 * ax + (n % 2) if n < 6 else 6 + 3 * ((n - 6) // 6) + ax
+
+
+def room_mesh(device, max_edge: float = 0.1, dtype=torch.float32, colors: bool = False):
+    """The room's true surfaces (``room_rectangles``) as a ``TriangleMesh``, every rectangle diced into a grid of cells
     split along one diagonal so that no edge -- the diagonals included -- exceeds ``max_edge``: the visibility cull of
-    ``mesh_eval.seen_vertices`` is per vertex.  Vertices are computed in float64 and stored as ``dtype``."""
+    ``mesh_eval.seen_vertices`` is per vertex.  Vertices are computed in float64 and stored as ``dtype``.  ``colors``: the room's
+    texture (``raycast_room``'s) evaluated at the vertices; without, the mesh has no colours."""
     import numpy as np
     from .tsdf import TriangleMesh
-    verts, tris, base = [], [], 0
-    cell = float(max_edge) / math.sqrt(2.0)
-    for ax, side, (a, a_lo, a_hi), (b, b_lo, b_hi) in room_rectangles():
-        na, nb = max(1, int(math.ceil((a_hi - a_lo) / cell - 1e-9))), max(1, int(math.ceil((b_hi - b_lo) / cell - 1e-9)))
+    verts, tris, cols, base = [], [], [], 0
+    for n, ax, side, (a, a_lo, a_hi), (b, b_lo, b_hi), na, nb in _room_grids(max_edge):
         A, B = np.meshgrid(np.linspace(a_lo, a_hi, na + 1), np.linspace(b_lo, b_hi, nb + 1), indexing="ij")
         p = np.zeros(A.shape + (3,))
         p[..., a], p[..., b], p[..., ax] = A, B, side
         verts.append(p.reshape(-1, 3))
+        if colors:
+            pt = torch.from_numpy(verts[-1]).to(torch.float32)
+            cols.append(_room_texture(pt, torch.full((len(pt),), ax, dtype=torch.long),
+                                      torch.full((len(pt),), _rectangle_surface_id(n, ax), dtype=torch.long)))
         i, j = np.meshgrid(np.arange(na), np.arange(nb), indexing="ij")
         v00 = (base + i * (nb + 1) + j).reshape(-1)
         v10, v01, v11 = v00 + (nb + 1), v00 + 1, v00 + (nb + 1) + 1
@@ -165,7 +182,38 @@ def room_mesh(device, max_edge: float = 0.1, dtype=torch.float32):
         base += (na + 1) * (nb + 1)
     v = torch.from_numpy(np.concatenate(verts)).to(dtype).to(device)
     t = torch.from_numpy(np.concatenate(tris).astype(np.int32)).to(device)
-    return TriangleMesh(v, t, None)
+    return TriangleMesh(v, t, torch.cat(cols).to(torch.float32).to(device) if colors else None)
+
+
+def room_mesh_surface_ids(max_edge: float = 0.1) -> torch.Tensor:
+    """[T] int32 (CPU): per triangle of ``room_mesh(max_edge=max_edge)``, the surface id ``raycast_room(with_ids=True)`` reports for it."""
+    out = []
+    for n, ax, _, _, _, na, nb in _room_grids(max_edge):
+        out.append(torch.full((2 * na * nb,), _rectangle_surface_id(n, ax), dtype=torch.int32))
+    return torch.cat(out)
+
+
+@torch.no_grad()
+def make_mesh_sequence(mesh, poses, intrinsics, device, face_labels=None, bg=(0.0, 0.0, 0.0)):
+    """``(frames, intr)`` in the shape of ``make_room_sequence``: one ``Viewpoint`` per world->camera pose ``(R, t)`` of ``poses`` with the
+    coloured mesh rendered on the device (``mesh_render.MeshRenderer``) as ``rgb`` and ``depth``, the pose as ground truth and, with
+    ``face_labels`` [T], the label image as ``segmentation``.  A mesh without colours is refused."""
+    if mesh.colors is None:
+        raise ValueError("make_mesh_sequence needs a mesh with vertex colours")
+    from .mesh_render import MeshRenderer
+    k = dict(cam.INTRINSICS[intrinsics]) if isinstance(intrinsics, str) else dict(intrinsics)
+    intr = Intrinsics(k, device)
+    renderer = MeshRenderer(intr, device)
+    want = ("depth", "rgb") + (("label",) if face_labels is not None else ())
+    frames: List[Viewpoint] = []
+    for i, (R, t) in enumerate(poses):
+        R = torch.as_tensor(R, dtype=torch.float32).to(device).contiguous()
+        t = torch.as_tensor(t, dtype=torch.float32).to(device).contiguous()
+        out = renderer.render(mesh, R, t, want=want, face_labels=face_labels, bg=bg)
+        frames.append(Viewpoint(i, out["rgb"].clone(), out["depth"].clone(), device, gt_R=R, gt_T=t,
+                                segmentation=out["label"].clone() if face_labels is not None else None))
+    renderer.status()
+    return frames, intr
 
 
 def make_room_sequence(n_frames: int, intrinsics="fr3_office", device="cuda:0", step_scale: float = 1.0,

@@ -299,7 +299,9 @@ def _finish(s):
     triangle-mesh PLY (``tsdf.mesh_from_map``): ``path, vertices, triangles, voxel, integrate_ms, extract_ms`` and, on the synthetic
     room, ``accuracy_mean_m`` (mean distance of the vertices to the room's true surfaces).  ``mesh_gt`` (a mesh PLY in the sequence's
     world frame, or ``"room"`` for ``sequences.room_mesh``): ``mesh["reconstruction"]`` = ``mesh_eval.eval_reconstruction`` of the written
-    mesh against it, ``mesh_samples`` samples each, both culled by the keyframes (their estimated poses) and their depth images."""
+    mesh against it, ``mesh_samples`` samples each, both culled by the keyframes (their estimated poses) and their depth images.
+    ``mesh_depth_l1`` (with both): ``mesh["depth_l1"]`` = ``mesh_render.eval_depth_l1`` of the two meshes over the keyframes; a monocular
+    run then culls by the rendered ground-truth mesh (``depths="render"``) instead of without an occlusion test."""
     c, frames, gmap, intr, bg, mapper, kf_list = s.c, s.frames, s.gmap, s.intr, s.bg, s.mapper, s.kf_list
     _drop_tracking_graph(s)
     extra = {}
@@ -354,7 +356,12 @@ def _finish(s):
                 gt = load_mesh_ply(str(c.mesh_gt), device=gmap._xyz.device)
             kfs = [frames[k] for k in kf_list]
             depths = [f.depth for f in kfs] if c.sensor == "depth" else None     # (a monocular frame's depth is the all-zero image)
+            if depths is None and c.mesh_depth_l1:          # (only with the flag: an existing monocular run's figures stay)
+                depths = "render"
             m["reconstruction"] = eval_reconstruction(mesh, gt, n_samples=int(c.mesh_samples), viewpoints=kfs, intr=intr, depths=depths)
+            if c.mesh_depth_l1:
+                from .mesh_render import eval_depth_l1
+                m["depth_l1"] = eval_depth_l1(mesh, gt, kfs, intr)
         extra["mesh"] = m
     return extra
 
@@ -414,7 +421,8 @@ def run_slam(n_frames=12, intrinsics="fr3_office", tracking_itr_num=100, mapping
              scene="cloud", reference_densify=False, eager_probe=0, exclusive_device=False,
              kf_selection="interval", check_viewpoints_overlap=False, kf_trace=None, refine_iters=0, eval_render=False,
              sequence=None, nr_objects=None, sensor="depth", viewer_dir=None, viewer_modes=("rgb",), viewer_every=0,
-             learn_objects=0, mesh_path=None, mesh_voxel=0.02, mesh_gt=None, mesh_samples=200_000):
+             learn_objects=0, mesh_path=None, mesh_voxel=0.02, mesh_gt=None, mesh_samples=200_000,
+             mesh_depth_l1=False):
     """Tracks and maps a sequence in one process; returns tracking / mapping rates, iterations and the trajectory error (``_report``).
     Every argument is described where it acts: ``_setup``, ``_track_frame``, ``_select_keyframe``, ``_map_keyframe``, ``_map_window``,
     ``_finish`` (what follows the last frame).  ``log``: a callable that gets a line per frame.  ``sensor="monocular"`` adds the result
@@ -424,7 +432,7 @@ def run_slam(n_frames=12, intrinsics="fr3_office", tracking_itr_num=100, mapping
     ``learn_objects=N`` (with ``nr_objects``): learn the object rows, N trainer iterations over the window after each mapping call; only
     then does the result hold an ``objects`` entry (iterations, first and last label loss, label accuracy and mIoU).
     ``mesh_path``: write the final map's triangle mesh there (``_finish``); only then does the result hold a ``mesh`` entry;
-    with ``mesh_gt`` that entry gains ``reconstruction`` (``_finish``)."""
+    with ``mesh_gt`` that entry gains ``reconstruction`` and, with ``mesh_depth_l1``, ``depth_l1`` (``_finish``)."""
     s = _setup(SimpleNamespace(**locals()))              # (every argument, by name: must stay the first statement)
     for i, vp in enumerate(s.frames):
         if i == 0:

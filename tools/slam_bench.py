@@ -15,6 +15,8 @@ stand-in; the TUM / Replica sequences are not available offline).  Prints one JS
       # the final map fused from every keyframe into a TSDF volume and written as a coloured triangle mesh (monogs_amd.tsdf)
   python tools/slam_bench.py --config tum --room --graph --mesh room.ply --mesh-gt room
       # ... and scored against the ground-truth mesh: accuracy, completion, completion ratio, Chamfer-L1, F-score (monogs_amd.mesh_eval)
+  python tools/slam_bench.py --config tum --room --graph --mesh room.ply --mesh-gt room --mesh-depth-l1
+      # ... and Depth L1 between the two meshes rendered from the keyframes (monogs_amd.mesh_render)
 """
 import argparse
 import json
@@ -86,9 +88,14 @@ if __name__ == "__main__":
                          "--room scene's true surfaces); `mesh` gains `reconstruction`: accuracy, completion, completion ratio, Chamfer-L1, "
                          "precision / recall / F-score between samples of both meshes, culled by the keyframes (monogs_amd.mesh_eval)")
     ap.add_argument("--mesh-samples", type=int, default=200000, help="with --mesh-gt: samples per mesh")
+    ap.add_argument("--mesh-depth-l1", action="store_true",
+                    help="with --mesh-gt: `mesh` gains `depth_l1`, the two meshes rendered from the keyframes and compared "
+                         "(monogs_amd.mesh_render.eval_depth_l1)")
     a = ap.parse_args()
     if a.mesh_gt and not a.mesh:
         ap.error("--mesh-gt evaluates the mesh --mesh writes")
+    if a.mesh_depth_l1 and not a.mesh_gt:
+        ap.error("--mesh-depth-l1 compares the mesh with --mesh-gt")
     from monogs_amd.slam_harness import run_slam
     cfg = dict(CONFIGS[a.config])
     init_iters = a.init_iters
@@ -123,7 +130,8 @@ if __name__ == "__main__":
                    refine_iters=a.refine, eval_render=a.eval, sensor=sensor, viewer_dir=a.viewer,
                    viewer_modes=tuple(a.viewer_modes), viewer_every=a.viewer_every, log=lambda s: print("[slam]", s, file=sys.stderr, flush=True), **objects, **cfg,
                    **(dict(mesh_path=a.mesh, mesh_voxel=a.mesh_voxel) if a.mesh else {}),
-                   **(dict(mesh_gt=a.mesh_gt, mesh_samples=a.mesh_samples) if a.mesh_gt else {}))
+                   **(dict(mesh_gt=a.mesh_gt, mesh_samples=a.mesh_samples) if a.mesh_gt else {}),
+                   **(dict(mesh_depth_l1=True) if a.mesh_depth_l1 else {}))
     what = f"{a.dataset}, every {a.stride}. frame" if a.dataset else f"synthetic {a.config}-like sequence"
     out["workload"] = f"{what}, {a.frames} frames" + (" (fork's hard-coded run configuration)" if a.fork else "")
     if sensor == "monocular":
