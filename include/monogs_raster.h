@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define MGS_ABI_VERSION 25
+#define MGS_ABI_VERSION 26
 #define MGS_TILE 16 /* tile edge in pixels; ranges are per 16x16 tile */
 
 /* GaussianRasterizationSettings, minus `prefiltered` / `debug` which are call flags
@@ -1012,6 +1012,39 @@ int mgs_mesh_render(const MgsMeshRender* params, void* scratch, void* stream);
 size_t mgs_depth_l1_scratch_bytes(void);
 int mgs_depth_l1(int32_t W, int32_t H, const float* a /* [H][W] */, const float* b /* [H][W] */, float max_depth,
                  double* row /* device [3] */, void* scratch, void* stream);
+
+/* ---- Rigid object motion: per-object SE(3) poses on the object layer (ABI v26) ---------------------------------------------
+ * The specification is DESIGN.md, "Object motion" (tests/object_motion_mirror.py restates it in float64).
+ * `labels` [P]: the object id of every Gaussian; `slot_of_label`: a DEVICE table of 256 int32, the pose slot 0..M-1 of an id or -1
+ * (any value outside 0..M-1 counts as -1): that Gaussian is static.  Object m has the WORLD-frame pose (R_m, T_m).
+ * mgs_object_transform_forward: for a moved Gaussian  x' = R_m x + T_m  (three fused multiply-adds per component) and
+ * q' = quat(R_m) (x) q  in the (r, x, y, z) order of the map's rotations (quat(R): Shepperd's branches in float64, rounded
+ * once); every other Gaussian is copied bit for bit.  M = 0 is a copy (R, T may be NULL).  `rots` and `rots_out` are both given
+ * or both NULL.  One launch.
+ * mgs_object_transform_backward: the pose is retracted as the camera's is,  T_m <- exp([rho; theta]^) T_m  with the deltas zero
+ * at evaluation, so  dL/drho_m = sum g_i,  dL/dtheta_m = sum x'_i x g_i  (+ 1/2 (w gq_v - gq_w v + v x gq_v) per Gaussian with a
+ * rotation gradient gq = (gq_w, gq_v) on q' = (w, v)), written to grad_tau [M,6] as rho then theta; grad_means = R_m^T g (g for a
+ * static Gaussian), grad_rots = conj(quat(R_m)) (x) gq (gq).  `rots_out`, `grad_rots_out` both given or both NULL (grad_rots then
+ * must be NULL); grad_means / grad_rots may be NULL: not wanted.
+ * The [M,6] sums use no float atomics and are bitwise reproducible: every workgroup of 256 threads adds its 1024 Gaussians in a
+ * fixed order (a wave skips a slot none of its lanes holds) and writes one row of partials, a second launch adds the rows in a
+ * fixed order.  A slot without Gaussians gets exact zeros.  Two launches (M = 0: one).  `scratch`:
+ * mgs_object_motion_scratch_bytes(P, M) bytes, a pure function.
+ * No host synchronisation, no allocation: capturable in a hipGraph.  Refused with 1 and a message before any launch: P < 0,
+ * M outside 0..MGS_MAX_MOVING_OBJECTS, a NULL required pointer (labels, slot_of_label, means..., and R, T, grad_tau, scratch
+ * when M > 0), one of a rotation pair without the other. */
+#define MGS_MAX_MOVING_OBJECTS 16
+size_t mgs_object_motion_scratch_bytes(int32_t P, int32_t M);
+int mgs_object_transform_forward(int32_t P, int32_t M, const uint8_t* labels /* [P] */,
+                                 const int32_t* slot_of_label /* device [256], -1 = static */, const float* R /* [M,3,3] row-major */,
+                                 const float* T /* [M,3] */, const float* means /* [P,3] */,
+                                 const float* rots /* [P,4] (r,x,y,z) or NULL */, float* means_out, float* rots_out /* or NULL */,
+                                 void* stream);
+int mgs_object_transform_backward(int32_t P, int32_t M, const uint8_t* labels, const int32_t* slot_of_label, const float* R,
+                                  const float* means_out, const float* rots_out /* or NULL */,
+                                  const float* grad_means_out /* [P,3] */, const float* grad_rots_out /* [P,4] or NULL */,
+                                  float* grad_means /* [P,3] or NULL */, float* grad_rots /* [P,4] or NULL */,
+                                  float* grad_tau /* [M,6]: rho then theta */, void* scratch, void* stream);
 
 #ifdef __cplusplus
 }

@@ -11,7 +11,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MGS_LIB_PATH") or os.path.join(_HERE, "lib", "libmonogs_raster.so")   # (override: kernel experiments)
-ABI_VERSION = 25
+ABI_VERSION = 26
 
 c_float_p = C.c_void_p   # device pointers travel as integers (tensor.data_ptr())
 
@@ -183,6 +183,9 @@ SIGNATURES = {
     "mgs_mesh_render": (C.c_int, [C.POINTER(MgsMeshRender), C.c_void_p, C.c_void_p]),
     "mgs_depth_l1_scratch_bytes": (C.c_size_t, []),
     "mgs_depth_l1": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mgs_object_motion_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "mgs_object_transform_forward": (C.c_int, [C.c_int32, C.c_int32] + [C.c_void_p] * 9),
+    "mgs_object_transform_backward": (C.c_int, [C.c_int32, C.c_int32] + [C.c_void_p] * 12),
 }
 
 _lib = None

@@ -4,6 +4,7 @@
 // (`update_pose`) in ~60 tiny launches and one host sync per iteration.  One single-wave kernel here.
 // Caller-side widening (optimiser step next to the rasteriser backward).
 #include "common.h"
+#include "object_motion.h"   // rigid object motion: the poses mgs_pose_step_batch steps, applied to the map (kernels, entry points)
 
 namespace mgs {
 

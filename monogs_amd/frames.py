@@ -89,6 +89,28 @@ class Viewpoint:
         return conv
 
 
+def mask_objects(vp: Viewpoint, ids, keep: bool = False, border: int = 0) -> Viewpoint:
+    """A new ``Viewpoint`` of the same frame that does not look at the objects ``ids`` of ``vp.segmentation`` -- what the camera of a
+    dynamic scene is tracked on: its ``mask`` excludes their pixels and its depth is zero there -- or, with ``keep=True``, that
+    looks at nothing else (what the objects are tracked on).  ``border``: the pixels within that many pixels of the boundary between
+    the objects and the rest are dropped as well (a render mixes the two sides of a silhouette; DESIGN.md, "Object motion").  Pose,
+    exposure, ground truth, edge mask and segmentation are carried over; ``vp`` itself is untouched."""
+    seg = getattr(vp, "segmentation", None)
+    if seg is None:
+        raise ValueError(f"frame {getattr(vp, 'frame_idx', '?')} carries no segmentation")
+    hit = torch.isin(seg, torch.as_tensor([int(i) for i in ids], dtype=seg.dtype, device=seg.device))
+    sel = hit if keep else ~hit
+    if border > 0:            # erode what is kept: a pixel stays when its (2 border + 1)^2 neighbourhood holds nothing of the other side
+        other = torch.nn.functional.max_pool2d((~sel)[None, None].float(), 2 * int(border) + 1, stride=1, padding=int(border))[0, 0]
+        sel = other < 0.5
+    out = Viewpoint(vp.frame_idx, vp.rgb, torch.where(sel, vp.depth, torch.zeros_like(vp.depth)), vp.device, gt_R=vp.R_gt, gt_T=vp.T_gt,
+                    mask=vp.mask.bool() & sel, grad_mask=vp.grad_mask, segmentation=seg, sensor=vp.sensor)
+    out.update_RT(vp.R.clone(), vp.T.clone())
+    with torch.no_grad():
+        out.exposure_a.copy_(vp.exposure_a); out.exposure_b.copy_(vp.exposure_b)
+    return out
+
+
 def position_error(vp) -> torch.Tensor:
     """Distance between the camera centre of ``vp``'s pose and that of its ground-truth pose (0-d tensor, metres)."""
     return (-(vp.R.t() @ vp.T) + (vp.R_gt.t() @ vp.T_gt)).norm()

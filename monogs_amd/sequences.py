@@ -131,12 +131,13 @@ def room_surface_distance(points: torch.Tensor) -> torch.Tensor:
     return best.to(points.dtype)
 
 
-def room_rectangles():
+def room_rectangles(boxes=None):
     """The room's true surfaces as axis-aligned rectangles ``(axis, side, (a, a_lo, a_hi), (b, b_lo, b_hi))``: the plane ``x[axis] =
     side`` over ``[a_lo, a_hi] x [b_lo, b_hi]`` of the other two axes -- the six walls and the six faces of every box, from the tables
-    ``room_surface_distance`` uses (a box standing on the floor or against a wall keeps that face: it is part of the union's distance)."""
+    ``room_surface_distance`` uses (a box standing on the floor or against a wall keeps that face: it is part of the union's distance).
+    ``boxes``: the ``(lo, hi)`` boxes to take the faces of instead."""
     out = []
-    for lo, hi in [((-_ROOM_HALF[0], -_ROOM_HALF[1], -_ROOM_HALF[2]), _ROOM_HALF)] + list(_ROOM_BOXES):
+    for lo, hi in ([((-_ROOM_HALF[0], -_ROOM_HALF[1], -_ROOM_HALF[2]), _ROOM_HALF)] + list(_ROOM_BOXES)) if boxes is None else boxes:
         for ax in range(3):
             a, b = [i for i in range(3) if i != ax]
             for side in (lo[ax], hi[ax]):
@@ -144,10 +145,10 @@ def room_rectangles():
     return out
 
 
-def _room_grids(max_edge: float):
+def _room_grids(max_edge: float, boxes=None):
     """``room_rectangles`` with the dicing of ``room_mesh``: ``(rectangle number, axis, side, (a, a_lo, a_hi), (b, b_lo, b_hi), na, nb)``."""
     cell = float(max_edge) / math.sqrt(2.0)
-    for n, (ax, side, (a, a_lo, a_hi), (b, b_lo, b_hi)) in enumerate(room_rectangles()):
+    for n, (ax, side, (a, a_lo, a_hi), (b, b_lo, b_hi)) in enumerate(room_rectangles(boxes)):
         na, nb = max(1, int(math.ceil((a_hi - a_lo) / cell - 1e-9))), max(1, int(math.ceil((b_hi - b_lo) / cell - 1e-9)))
         yield n, ax, side, (a, a_lo, a_hi), (b, b_lo, b_hi), na, nb
 
@@ -163,10 +164,17 @@ def room_mesh(device, max_edge: float = 0.1, dtype=torch.float32, colors: bool =
     split along one diagonal so that no edge -- the diagonals included -- exceeds ``max_edge``: the visibility cull of
     ``mesh_eval.seen_vertices`` is per vertex.  Vertices are computed in float64 and stored as ``dtype``.  ``colors``: the room's
     texture (``raycast_room``'s) evaluated at the vertices; without, the mesh has no colours."""
+    return _grid_mesh(_room_grids(max_edge), device, dtype, _rectangle_surface_id if colors else None)
+
+
+def _grid_mesh(grids, device, dtype, surface_id):
+    """The diced rectangles ``grids`` (``_room_grids``) as one ``TriangleMesh``; ``surface_id(n, axis)``: the texture id of rectangle
+    ``n`` for ``_room_texture`` at the vertices, or None: no colours."""
     import numpy as np
     from .tsdf import TriangleMesh
+    colors = surface_id is not None
     verts, tris, cols, base = [], [], [], 0
-    for n, ax, side, (a, a_lo, a_hi), (b, b_lo, b_hi), na, nb in _room_grids(max_edge):
+    for n, ax, side, (a, a_lo, a_hi), (b, b_lo, b_hi), na, nb in grids:
         A, B = np.meshgrid(np.linspace(a_lo, a_hi, na + 1), np.linspace(b_lo, b_hi, nb + 1), indexing="ij")
         p = np.zeros(A.shape + (3,))
         p[..., a], p[..., b], p[..., ax] = A, B, side
@@ -174,7 +182,7 @@ def room_mesh(device, max_edge: float = 0.1, dtype=torch.float32, colors: bool =
         if colors:
             pt = torch.from_numpy(verts[-1]).to(torch.float32)
             cols.append(_room_texture(pt, torch.full((len(pt),), ax, dtype=torch.long),
-                                      torch.full((len(pt),), _rectangle_surface_id(n, ax), dtype=torch.long)))
+                                      torch.full((len(pt),), surface_id(n, ax), dtype=torch.long)))
         i, j = np.meshgrid(np.arange(na), np.arange(nb), indexing="ij")
         v00 = (base + i * (nb + 1) + j).reshape(-1)
         v10, v01, v11 = v00 + (nb + 1), v00 + 1, v00 + (nb + 1) + 1
@@ -197,8 +205,10 @@ def room_mesh_surface_ids(max_edge: float = 0.1) -> torch.Tensor:
 def make_mesh_sequence(mesh, poses, intrinsics, device, face_labels=None, bg=(0.0, 0.0, 0.0)):
     """``(frames, intr)`` in the shape of ``make_room_sequence``: one ``Viewpoint`` per world->camera pose ``(R, t)`` of ``poses`` with the
     coloured mesh rendered on the device (``mesh_render.MeshRenderer``) as ``rgb`` and ``depth``, the pose as ground truth and, with
-    ``face_labels`` [T], the label image as ``segmentation``.  A mesh without colours is refused."""
-    if mesh.colors is None:
+    ``face_labels`` [T], the label image as ``segmentation``.  A mesh without colours is refused.  ``mesh`` may be a function of the
+    frame number (a scene that changes; the triangle count, hence ``face_labels``, stays)."""
+    mesh_of = mesh if callable(mesh) else (lambda i: mesh)
+    if mesh_of(0).colors is None:
         raise ValueError("make_mesh_sequence needs a mesh with vertex colours")
     from .mesh_render import MeshRenderer
     k = dict(cam.INTRINSICS[intrinsics]) if isinstance(intrinsics, str) else dict(intrinsics)
@@ -209,11 +219,20 @@ def make_mesh_sequence(mesh, poses, intrinsics, device, face_labels=None, bg=(0.
     for i, (R, t) in enumerate(poses):
         R = torch.as_tensor(R, dtype=torch.float32).to(device).contiguous()
         t = torch.as_tensor(t, dtype=torch.float32).to(device).contiguous()
-        out = renderer.render(mesh, R, t, want=want, face_labels=face_labels, bg=bg)
+        out = renderer.render(mesh_of(i), R, t, want=want, face_labels=face_labels, bg=bg)
         frames.append(Viewpoint(i, out["rgb"].clone(), out["depth"].clone(), device, gt_R=R, gt_T=t,
                                 segmentation=out["label"].clone() if face_labels is not None else None))
     renderer.status()
     return frames, intr
+
+
+def room_path_pose(s: float):
+    """The world->camera pose ``(R, t)`` (CPU float32) at parameter ``s`` of the hand-held-like path of ``make_room_sequence``."""
+    c = torch.tensor([0.35 * math.sin(0.022 * s) - 0.2, 0.05 * math.sin(0.05 * s) + 0.1, -1.6 + 0.25 * (1 - math.cos(0.02 * s))])
+    yaw, pitch = 0.0055 * s - 0.1, 0.05 + 0.03 * math.sin(0.04 * s)
+    Rwc = cam.so3_exp(torch.tensor([0.0, yaw, 0.0])) @ cam.so3_exp(torch.tensor([pitch, 0.0, 0.0]))   # camera -> world
+    Rcw = Rwc.t().contiguous()
+    return Rcw, -(Rcw @ c)
 
 
 def make_room_sequence(n_frames: int, intrinsics="fr3_office", device="cuda:0", step_scale: float = 1.0,
@@ -225,13 +244,51 @@ def make_room_sequence(n_frames: int, intrinsics="fr3_office", device="cuda:0", 
     intr = Intrinsics(k, device)
     frames: List[Viewpoint] = []
     for i in range(n_frames):
-        s = step_scale * i
-        c = torch.tensor([0.35 * math.sin(0.022 * s) - 0.2, 0.05 * math.sin(0.05 * s) + 0.1, -1.6 + 0.25 * (1 - math.cos(0.02 * s))])
-        yaw, pitch = 0.0055 * s - 0.1, 0.05 + 0.03 * math.sin(0.04 * s)
-        Rwc = cam.so3_exp(torch.tensor([0.0, yaw, 0.0])) @ cam.so3_exp(torch.tensor([pitch, 0.0, 0.0]))   # camera -> world
-        Rcw = Rwc.t().contiguous()
-        tcw = -(Rcw @ c)
+        Rcw, tcw = room_path_pose(step_scale * i)
         rgb, depth, *seg = raycast_room(Rcw, tcw, k, device, with_ids=with_segmentation)
         frames.append(Viewpoint(i, rgb, depth, device, gt_R=Rcw.to(device), gt_T=tcw.to(device),
                                 segmentation=seg[0] if seg else None))
     return frames, intr
+
+
+# ---- a dynamic scene: the room with one more box, which moves ------------------------------------------------------------------
+DYNAMIC_BOX = ((-0.30, -0.45, 0.50), (0.35, 0.25, 1.10))      # (lo, hi) at frame 0: in the middle of the first view, 2.4 m away
+DYNAMIC_BOX_ID = ROOM_SURFACES                                # its segmentation id: the first one the room does not use
+
+
+def dynamic_box_motion(i: int):
+    """The default ``object_motion`` of ``make_dynamic_room_sequence``: the world-frame ``(R, t)`` (CPU float32) of the box at frame
+    ``i`` relative to frame 0 -- its centre moves 1.02 cm per frame along (0.8, -0.2, 0.6) cm while it turns 0.5 degrees per frame
+    about the axis (0.2, 1, 0.1) through that centre."""
+    lo, hi = (torch.tensor(v, dtype=torch.float64) for v in DYNAMIC_BOX)
+    c0 = 0.5 * (lo + hi)
+    axis = torch.tensor([0.2, 1.0, 0.1], dtype=torch.float64)
+    R = cam.so3_exp(axis / axis.norm() * math.radians(0.5) * i)
+    c = c0 + i * torch.tensor([0.008, -0.002, 0.006], dtype=torch.float64)
+    return R.to(torch.float32), (c - R @ c0).to(torch.float32)
+
+
+@torch.no_grad()
+def make_dynamic_room_sequence(n_frames: int, intrinsics, device="cuda:0", object_motion=None, step_scale: float = 1.0):
+    """``(frames, intr, object_poses)``: the room (``room_mesh(colors=True)``, faces labelled with the ids of ``raycast_room``) plus one
+    box, ``DYNAMIC_BOX`` diced to 2 cm edges, textured like the room's surfaces and labelled ``DYNAMIC_BOX_ID``, which is moved by
+    ``object_motion(i) -> (R, t)`` (world frame, relative to frame 0; default ``dynamic_box_motion``, about 1 cm and 0.5 degrees per
+    frame; ``lambda i: (eye, zeros)`` holds it still) and rendered through ``make_mesh_sequence`` from the camera path of
+    ``make_room_sequence``.  Every frame carries ``segmentation``; ``object_poses[i]`` is the ground-truth ``(R, t)`` of the box at frame
+    ``i`` (device float32)."""
+    from .tsdf import TriangleMesh
+    motion = dynamic_box_motion if object_motion is None else object_motion
+    room = room_mesh(device, colors=True)
+    box = _grid_mesh(_room_grids(0.02, boxes=[DYNAMIC_BOX]), device, torch.float32, lambda n, ax: 6 + ax)      # the desk's three base colours
+    tris = torch.cat((room.triangles, box.triangles + room.vertices.shape[0]))
+    cols = torch.cat((room.colors, box.colors))
+    labels = torch.cat((room_mesh_surface_ids().to(device), torch.full((box.triangles.shape[0],), DYNAMIC_BOX_ID, dtype=torch.int32,
+                                                                       device=device)))
+    object_poses = [tuple(torch.as_tensor(x, dtype=torch.float32).to(device).contiguous() for x in motion(i)) for i in range(n_frames)]
+
+    def mesh_of(i):
+        R, t = object_poses[i]
+        return TriangleMesh(torch.cat((room.vertices, box.vertices @ R.t() + t)), tris, cols)
+    poses = [room_path_pose(step_scale * i) for i in range(n_frames)]
+    frames, intr = make_mesh_sequence(mesh_of, poses, intrinsics, device, face_labels=labels)
+    return frames, intr, object_poses
