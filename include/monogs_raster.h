@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define MGS_ABI_VERSION 26
+#define MGS_ABI_VERSION 27
 #define MGS_TILE 16 /* tile edge in pixels; ranges are per 16x16 tile */
 
 /* GaussianRasterizationSettings, minus `prefiltered` / `debug` which are call flags
@@ -285,6 +285,14 @@ int mgs_debug_set_blend_events(void* fwd_start, void* fwd_end, void* bwd_start, 
 /* TEST USE ONLY, process-global: 1 / 0 = the last blend backward launched by mgs_backward with blend_bwd_transposed = 2 walked
  * the lists split / unsplit; -1 = there was none yet. */
 int mgs_debug_last_backward_split(void);
+/* TEST USE ONLY, process-global: the number of 256-tile bands of the last render call's banded tile sort; 0 = it took the
+ * two tile-sort passes.  The banded sort is the default on the per-tile path (mgs_binning_path() == 1, "pre_scan" on) when the
+ * tile id is wider than 8 bits, the image has at most 32 bands of 256 tiles and the one pass's scratch fits the binning
+ * scratch (it does from a few thousand instances up): the instances are emitted grouped by band from exact per-band counts
+ * and ONE segmented 8-bit pass orders each band.  One more knob of mgs_debug_set_option switches it: "tile_sort_banded",
+ * 1 = default, 0 = the plain emission and two passes everywhere; the same tables either way.  Set it between whole forwards,
+ * like "pre_scan". */
+int mgs_debug_last_tile_sort_bands(void);
 
 /* Diagnostic (not on the hot path): counts what the blend backward of the matching forward does, into
  * stats_dev[MGS_BLEND_STATS_WORDS] (device uint64): [0] 64-instance steps walked, [1] instances that pass the per-quadrant

@@ -26,6 +26,8 @@ template <class F> static void geometry_layout(int P, F& f) {
     const size_t n = (size_t)P;
     f("rec", &GeometryState::rec, n * REC_FLOATS * sizeof(float));
     f("depth_key", &GeometryState::depth_key, n * sizeof(uint32_t));
+    // (depth_alt .. perm, contiguous, belong to the global depth sort.  On the per-tile path, which runs none, the banded tile
+    //  sort keeps its band tables there -- GeometryState::carve, band_table_bytes() -- so the scratch does not grow)
     f("depth_alt", &GeometryState::depth_alt, n * sizeof(uint32_t));
     f("iota", &GeometryState::iota, n * sizeof(uint32_t));
     f("iota_alt", &GeometryState::iota_alt, n * sizeof(uint32_t));
@@ -91,6 +93,11 @@ GeometryState GeometryState::carve(void* base, int P) {
     Carver<GeometryState> c(base);
     geometry_layout(P, c);
     c.s.sort_temp_bytes = radix_depth_temp_bytes((uint64_t)P);
+    // the band tables of the banded tile sort, over the global depth sort's buffers: [64 words: totals][bands x blocks: counts]
+    c.s.band_totals = c.s.depth_alt;
+    c.s.band_live = c.s.depth_alt + 32;
+    c.s.band_counts = c.s.depth_alt + 64;
+    c.s.band_room = (size_t)((char*)c.s.point_offsets - (char*)c.s.depth_alt);
     c.s.end = c.p;
     return c.s;
 }
@@ -243,7 +250,7 @@ int mgs_forward_preprocess(const mgs_camera* cam, int32_t P, const float* means3
     const int items = scan_items(P, cam->image_width, cam->image_height);      // (the decision launch_preprocess_forward took)
     if (per_tile) {                         // no global depth sort: the scan runs in index order (binning.hip)
         tm.mark();
-        if (int rc = launch_scan(g, P, s, exclusive, g.rect, items)) return rc;
+        if (int rc = launch_scan(g, P, s, exclusive, g.rect, items, tile_sort_bands(P, cam->image_width, cam->image_height))) return rc;
     } else {
         if (int rc = launch_depth_sort(g, P, depth_sort_payload(P, cam->image_width, cam->image_height), s, exclusive)) return rc;
         tm.mark();
@@ -303,7 +310,7 @@ static int forward_render_impl(const mgs_camera* cam, int32_t P, uint64_t R, boo
     tm.mark();
     // (the sort's final pass writes the per-tile ranges: no ranges launch since round 4)
     if (int rc = launch_sort(g, b, R, tile_bits(W, H), s, n_dev, (cam->flags & MGS_FLAG_EXCLUSIVE_DEVICE) != 0, img.ranges,
-                             per_tile)) return rc;
+                             per_tile, per_tile ? tile_sort_bands_render(P, W, H, R) : 0)) return rc;
     const uint32_t* sort_err = R > 0 ? radix_error_flag(b.sort_temp, R, tile_bits(W, H)) : nullptr;
     // per-tile depth order: each tile's list, in index order now, sorted by depth in LDS -- by the blend forward's workgroup
     // of the tile (timed with the blend forward), or by a launch of its own (timed with the sort)
@@ -515,6 +522,7 @@ int mgs_debug_valu_ceiling(float* out, int32_t iters, void* stream) {
 }
 
 int mgs_debug_last_backward_split(void) { return g_dbg_last_bwd_split; }
+int mgs_debug_last_tile_sort_bands(void) { return g_dbg_last_tile_sort_bands; }
 
 int mgs_debug_set_radix_spin_limit(uint32_t limit) { return set_radix_spin_limit(limit); }
 
@@ -567,6 +575,7 @@ int mgs_debug_set_option(const char* name, int64_t value) {
         {"blend_bwd_split_frac", &g_opt_blend_bwd_split_frac, 32, INT_MAX},
         {"scan_small", &g_opt_scan_small, -1, 1},
         {"pre_scan", &g_opt_pre_scan, -1, 1},
+        {"tile_sort_banded", &g_opt_tile_sort_banded, 1, 1},
         {"tile_sort_fused", &g_opt_tile_sort_fused, 1, 1},
         {"knn_grid_min", &g_opt_knn_grid_min, -1, INT_MAX},
     };

@@ -12,6 +12,12 @@
 // Stability of both sorts makes the result identical to the single 64-bit sort.  The sort itself is
 // the hand-written LSD radix sort of radix_sort.hip.  The last pass of the depth sort also lays the tile
 // rectangles out in depth order, so the scan and duplicate below read everything coalesced.
+//
+// Large maps (binning_path() == 1) skip (1): the instances are emitted in index order with their depth in the pair and each
+// tile's list is sorted by depth on its own (tile_sort.h).  There the tile sort only has to group by tile, stably -- and the
+// band of 256 tiles an instance falls into is known where the instance is made: tile_sort_bands() != 0 emits the instances
+// grouped by band from exact counts (preprocess counts them per scan block, scan_blocks_kernel scans them, emit_banded_kernel
+// places them) and (3) is ONE segmented 8-bit pass, radix_sort_banded, instead of two passes over everything.
 #include "common.h"
 #include "tile_sort.h"
 
@@ -85,9 +91,17 @@ __global__ void __launch_bounds__(SCAN_THREADS) scan_local_kernel(const uint2* _
 // scan_block_rows: wave w owns items [w * 512, (w + 1) * 512) of the iteration, item (i, lane) = i * 64 + lane of them.
 constexpr int SCANB_THREADS = 1024, SCANB_PER_THREAD = 8, SCANB_WAVES = SCANB_THREADS / WAVE;
 constexpr int SCANB_ITEMS = SCANB_THREADS * SCANB_PER_THREAD;
-__global__ void __launch_bounds__(SCANB_THREADS) scan_blocks_kernel(uint32_t* block_sums, int nblocks) {
+// Banded tile sort: the launch has one more workgroup per band; workgroup 1 + b scans row b of band_counts (the column of
+// band b over the scan blocks) the same way and leaves the band's total in band_totals[b].  Nobody waits for anybody.
+__global__ void __launch_bounds__(SCANB_THREADS) scan_blocks_kernel(uint32_t* block_sums, int nblocks, uint32_t* band_counts,
+                                                                    uint32_t* band_totals) {
     __shared__ uint32_t smem[SCANB_WAVES];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    uint32_t* total_out = block_sums + nblocks;             // grand total = number of instances R (read back by the exact path)
+    if (blockIdx.x > 0) {                                   // (workgroup-uniform)
+        block_sums = band_counts + (size_t)(blockIdx.x - 1) * nblocks;
+        total_out = band_totals + (blockIdx.x - 1);
+    }
     uint32_t carry = 0;
     for (int start = 0; start < nblocks; start += SCANB_ITEMS) {          // (workgroup-uniform: every thread reaches the barriers)
         const int cbase = start + wv * (SCANB_PER_THREAD * WAVE);
@@ -121,7 +135,7 @@ __global__ void __launch_bounds__(SCANB_THREADS) scan_blocks_kernel(uint32_t* bl
         carry += total;
         __syncthreads();                                                   // smem is rewritten by the next iteration
     }
-    if (threadIdx.x == 0) block_sums[nblocks] = carry;      // grand total = number of instances R (read back by the exact path)
+    if (threadIdx.x == 0) *total_out = carry;
 }
 
 // ONE launch for P <= SCAN_SMALL_MAX_BLOCKS * SCAN_ITEMS (every SLAM-sized map): each workgroup publishes its total as a
@@ -181,6 +195,31 @@ int g_opt_pre_scan = -1;            // mgs_debug_set_option("pre_scan", -1 | 0 |
 int scan_items(int P, int W, int H) {
     return (g_opt_pre_scan != 0 && binning_path(P, W, H) != 0) ? SCAN_ITEMS_PRE : SCAN_ITEMS;
 }
+int g_opt_tile_sort_banded = 1;     // mgs_debug_set_option("tile_sort_banded", 0): today's two tile-sort passes everywhere
+int g_dbg_last_tile_sort_bands = 0; // mgs_debug_last_tile_sort_bands(): bands of the last forward's tile sort (0: two passes)
+// The ONE host-side place that decides the banded tile sort (common.h): preprocess (does it count bands?), launch_scan (the
+// column scan), launch_duplicate (which emission kernel) and launch_sort (one segmented pass) all ask here.
+int tile_sort_bands(int P, int W, int H) {
+    if (g_opt_tile_sort_banded == 0 || scan_items(P, W, H) != SCAN_ITEMS_PRE) return 0;      // (per-tile path, preprocess scans)
+    const int tb = tile_bits(W, H), ntiles = tiles_x(W) * tiles_y(H);
+    const int bands = (ntiles + (1 << TILE_BAND_BITS) - 1) >> TILE_BAND_BITS;
+    return (tb > TILE_BAND_BITS && bands <= TILE_SORT_MAX_BANDS) ? bands : 0;
+}
+constexpr uint64_t DUP_SLOT_MAJOR_MIN = 768ull * 1024;      // instances (capacity in capacity mode)
+int g_opt_dup_slot_major = -1;      // mgs_debug_set_option("dup_slot_major", -1 | 0 | 1): -1 = by size
+// duplicate_kernel's emission balanced by output slots (see the kernel and launch_duplicate): forced, or many instances AND
+// many per Gaussian
+static bool dup_slot_major(int P, uint64_t sort_n) {
+    return P > 0 && g_opt_dup_slot_major != 0 &&
+           (g_opt_dup_slot_major > 0 || (sort_n >= DUP_SLOT_MAJOR_MIN && sort_n >= 6ull * (uint64_t)P));
+}
+// Scenes of big splats keep the slot-balanced duplicate_kernel and the two passes: emit_banded_kernel is one workgroup per 256
+// Gaussians, the Gaussian-major balance that kernel was built to escape (a forced "dup_slot_major" = 1 is honoured the same way).
+int tile_sort_bands_render(int P, int W, int H, uint64_t R) {
+    const int bands = tile_sort_bands(P, W, H);
+    if (!bands || R == 0 || dup_slot_major(P, R)) return 0;
+    return radix_banded_temp_bytes(R, bands) <= radix_temp_bytes(R, tile_bits(W, H)) ? bands : 0;
+}
 // (SCAN_ITEMS granularity only: the single-launch scan writes GLOBAL sums)
 static bool scan_is_small(int P, int items) {
     return items == SCAN_ITEMS && g_opt_scan_small != 0 && scan_nblocks(P, SCAN_ITEMS) <= SCAN_SMALL_MAX_BLOCKS;
@@ -195,11 +234,12 @@ static bool scan_is_small(int P, int items) {
 // What is launched:  items == SCAN_ITEMS_PRE (per-tile path): preprocess_forward_kernel already wrote the block-local sums
 // of its 256-Gaussian workgroups and their totals -- scan_blocks_kernel alone (the "scan_small" option has no effect).
 // items == SCAN_ITEMS: scan_small_kernel (one launch, P <= 131 072) or scan_local_kernel + scan_blocks_kernel.
-int launch_scan(const GeometryState& g, int P, hipStream_t s, bool exclusive, const uint2* rects, int items) {
+int launch_scan(const GeometryState& g, int P, hipStream_t s, bool exclusive, const uint2* rects, int items, int bands) {
     if (P == 0) return 0;
     const int nb = scan_nblocks(P, items);
     if (items == SCAN_ITEMS_PRE) {
-        hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(SCANB_THREADS), 0, s, g.scan_blocks, nb);
+        hipLaunchKernelGGL(scan_blocks_kernel, dim3(1 + bands), dim3(SCANB_THREADS), 0, s, g.scan_blocks, nb, g.band_counts,
+                           g.band_totals);
         MGS_HIP(hipGetLastError());
         return 0;
     }
@@ -212,7 +252,7 @@ int launch_scan(const GeometryState& g, int P, hipStream_t s, bool exclusive, co
     }
     hipLaunchKernelGGL(scan_local_kernel, dim3(nb), dim3(SCAN_THREADS), 0, s, rects, g.point_offsets,
                        g.scan_blocks, P);
-    hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(SCANB_THREADS), 0, s, g.scan_blocks, nb);
+    hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(SCANB_THREADS), 0, s, g.scan_blocks, nb, nullptr, nullptr);
     MGS_HIP(hipGetLastError());
     return 0;
 }
@@ -498,8 +538,221 @@ __global__ void __launch_bounds__(256) duplicate_kernel(int P, const uint2* __re
     }
 }
 
-constexpr uint64_t DUP_SLOT_MAJOR_MIN = 768ull * 1024;      // instances (capacity in capacity mode)
-int g_opt_dup_slot_major = -1;      // mgs_debug_set_option("dup_slot_major", -1 | 0 | 1): -1 = by size
+// ------------------------------------------------------------------------------------------------
+// Banded emission (tile_sort_bands() != 0): duplicate_kernel's pairs, written grouped by band of 256 tiles.  One workgroup per
+// scan block of 256 Gaussians.  The block's instances are its local slots [0, n) in Gaussian-major order (point_offsets[] are
+// the block-local inclusive sums); a chunk of EB_CHUNK slots is decoded (owner of a slot: binary search of the 256 sums in
+// LDS, then duplicate_kernel's slot decode), ranked stably by band with returning LDS atomics (the radix sort's ranking:
+// lanes in ascending order, a wave's instructions in program order, the waves joined by a prefix), laid out band by band in
+// an LDS stage and streamed to  band base + column scan of the band at this block + pairs of earlier chunks + rank.
+// All counts are exact (preprocess counted them, scan_blocks_kernel scanned them): no atomics on global memory, no waiting.
+// Capacity mode with fewer slots than instances: duplicate_kernel keeps the first r_cap slots of the Gaussian-major order, and so
+// does this kernel -- the scan blocks before block B (the last one whose exclusive sum is <= r_cap) whole, the first
+// r_cap - sum(B) slots of block B, nothing behind it.  The bands then hold fewer pairs than preprocess counted: EVERY
+// workgroup finds B, decodes block B's kept slots and counts them per band itself (nobody waits for anybody; the overflowing
+// forward is flagged and slow, not wrong), so that live total of band b = column scan of b at B + its share of block B.
+// Workgroup 0 leaves the live totals in band_live[] for the segmented pass (without overflow: the totals themselves).
+// Scan blocks are dealt to the workgroups one contiguous range per XCD (block ids go round-robin over the 8 XCDs), so that
+// the short runs neighbouring blocks write into one band meet in one L2 -- the tile sort's xcd_band, for the same reason.
+// ------------------------------------------------------------------------------------------------
+constexpr int EB_THREADS = 256, EB_ITEMS = 4, EB_CHUNK = EB_THREADS * EB_ITEMS;
+struct EmitBandedArgs {
+    int P;
+    const uint2* rects;
+    const uint32_t* depth_key;
+    int tshift, lo;
+    const uint32_t* offsets;           // block-local inclusive sums
+    const uint32_t* block_sums;        // [nblk] exclusive, [nblk] = total
+    const uint32_t* band_counts;       // [nbands][nblk] exclusive along the blocks
+    const uint32_t* band_totals;       // [nbands]
+    uint32_t* band_live;               // [TILE_SORT_MAX_BANDS] out: pairs per band actually emitted
+    int nbands, nblk;
+    uint32_t* keys;
+    uint32_t* vals;
+    int gx;
+    uint32_t r_cap;
+    int32_t* n_touched;
+    uint2* ranges;
+    int ntiles;
+    uint32_t* zero_ptr;
+    size_t zero_words;
+    uint32_t* count;
+    uint32_t* overflow;
+    const uint32_t* depth_err;
+    int n_threads;
+    unsigned long long* prepare;
+};
+__global__ void __launch_bounds__(EB_THREADS) emit_banded_kernel(EmitBandedArgs a) {
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const int i = blockIdx.x * EB_THREADS + t;
+    if (i == 0 && a.prepare) {                             // (see duplicate_kernel)
+        a.prepare[1] = a.prepare[0];
+        a.prepare[0] = 0ull;
+    }
+    const uint32_t nq = (uint32_t)a.nblk >> 3, nr = (uint32_t)a.nblk & 7u, xcd = blockIdx.x & 7u, j = blockIdx.x >> 3;
+    const bool has = j < nq + (xcd < nr ? 1u : 0u);        // (workgroups past the scan blocks: housekeeping only)
+    const uint32_t blk = has ? xcd * nq + min(xcd, nr) + j : 0u;
+    // ---- every input requested before the housekeeping stores (see duplicate_kernel)
+    const int gi = (int)blk * EB_THREADS + t, ci = gi < a.P ? gi : a.P - 1;
+    const uint2 in_rect = a.rects[ci];
+    const uint32_t in_off = a.offsets[ci], in_dkey = a.depth_key[ci];
+    uint32_t in_bt = 0, in_bc = 0;
+    if (t < a.nbands) {
+        in_bt = a.band_totals[t];
+        in_bc = a.band_counts[(size_t)t * a.nblk + blk];
+    }
+    const uint32_t R_all = a.block_sums[a.nblk];
+    const bool depth_bad = a.depth_err && radix_failed(a.depth_err) != 0u;
+    asm volatile("" ::"v"(in_rect.x), "v"(in_rect.y), "v"(in_off), "v"(in_dkey), "v"(in_bt), "v"(in_bc), "v"(R_all));
+    // ---- housekeeping: duplicate_kernel's, word for word
+    grid_zero(a.zero_ptr, a.zero_words, (size_t)a.n_threads, EB_THREADS);
+    if (i == 0 && a.count) {
+        const uint32_t R = !depth_bad ? R_all : 0u;
+        a.count[0] = min(R, a.r_cap);
+        a.count[1] = R > a.r_cap ? 1u : 0u;
+    }
+    if (i == 0 && a.overflow)
+        a.overflow[0] = (a.count ? a.count[1] : 0u) | (depth_bad ? (uint32_t)MGS_STATUS_DEPTH_SORT_TIMEOUT : 0u);
+    if (i < a.ntiles) a.ranges[i] = make_uint2(0xFFFFFFFFu, 0u);
+    if (i < a.P) a.n_touched[i] = 0;
+    if (!has || depth_bad) return;                         // (workgroup-uniform)
+
+    __shared__ uint32_t s_incl[EB_THREADS];
+    __shared__ uint4 s_ent[EB_THREADS];                    // dup_entry
+    __shared__ uint32_t s_kf[EB_THREADS];
+    __shared__ uint32_t s_cnt[EB_THREADS / WAVE][TILE_SORT_MAX_BANDS], s_dbase[TILE_SORT_MAX_BANDS], s_g[TILE_SORT_MAX_BANDS];
+    __shared__ uint32_t s_k[EB_CHUNK], s_v[EB_CHUNK];
+    uint32_t lim_blk = 0xFFFFFFFFu, lim_k = 0u;            // overflow: block lim_blk keeps its first lim_k slots
+    if (R_all > a.r_cap) {                                 // (grid-uniform; see the header)
+        uint32_t lo = 0u, hi = (uint32_t)a.nblk;           // block_sums[lo] <= r_cap < block_sums[hi]
+        while (hi - lo > 1u) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (a.block_sums[mid] <= a.r_cap) lo = mid; else hi = mid;
+        }
+        lim_blk = lo; lim_k = a.r_cap - a.block_sums[lo];
+        const int g2 = (int)lim_blk * EB_THREADS + t, c2 = g2 < a.P ? g2 : a.P - 1;
+        const uint2 r2 = a.rects[c2];
+        const uint32_t off2 = a.offsets[c2];
+        const int w2 = g2 < a.P ? (int)(r2.y & 0xFFFFu) : 0, h2 = g2 < a.P ? (int)(r2.y >> 16) : 0;
+        s_incl[t] = off2;
+        s_ent[t] = dup_entry(off2 - (uint32_t)(w2 * h2), (int)(r2.x & 0xFFFFu), (int)(r2.x >> 16), w2, a.gx, 0u);
+        if (t < TILE_SORT_MAX_BANDS) s_dbase[t] = 0u;
+        __syncthreads();
+        for (uint32_t o = (uint32_t)t; o < lim_k; o += EB_THREADS) {
+            uint32_t g = 0;
+#pragma unroll
+            for (uint32_t step = EB_THREADS / 2; step; step >>= 1)
+                if (s_incl[g + step - 1u] <= o) g += step;
+            const uint4 e = s_ent[g];
+            uint32_t yy, xx;
+            dup_divmod(o - e.x, e.z, true, yy, xx);
+            atomicAdd(&s_dbase[(e.y + yy * (uint32_t)a.gx + xx) >> TILE_BAND_BITS], 1u);
+        }
+        __syncthreads();
+        if (t < a.nbands) in_bt = a.band_counts[(size_t)t * a.nblk + lim_blk] + s_dbase[t];
+        __syncthreads();                                   // (the arrays are filled again below)
+    }
+    if (blockIdx.x == 0 && t < TILE_SORT_MAX_BANDS) a.band_live[t] = in_bt;
+    {
+        const int w = gi < a.P ? (int)(in_rect.y & 0xFFFFu) : 0, h = gi < a.P ? (int)(in_rect.y >> 16) : 0;
+        uint32_t val, kf;
+        dup_pair((uint32_t)ci, true, in_dkey, a.lo, val, kf);
+        s_incl[t] = in_off;                                // (lanes past P hold the last Gaussian's sum: the block's total)
+        s_ent[t] = dup_entry(in_off - (uint32_t)(w * h), (int)(in_rect.x & 0xFFFFu), (int)(in_rect.x >> 16), w, a.gx, val);
+        s_kf[t] = kf;
+    }
+    // band base (the prefix over the <= 32 band totals, formed in one wave) + what earlier scan blocks put into the band
+    uint32_t gpos = 0;
+    if (wv == 0) gpos = wave_incl_scan_dpp(in_bt) - in_bt + in_bc;
+    __syncthreads();
+    const uint32_t n_blk = blk < lim_blk ? s_incl[EB_THREADS - 1] : (blk == lim_blk ? lim_k : 0u);
+    const int bshift = a.tshift + TILE_BAND_BITS;
+    for (uint32_t c0 = 0; c0 < n_blk; c0 += EB_CHUNK) {    // (workgroup-uniform)
+        if (t < (EB_THREADS / WAVE) * TILE_SORT_MAX_BANDS) s_cnt[t >> 5][t & 31] = 0u;
+        __syncthreads();
+        uint32_t key[EB_ITEMS], val[EB_ITEMS], rank[EB_ITEMS];
+#pragma unroll
+        for (int k = 0; k < EB_ITEMS; ++k) {
+            const uint32_t o = c0 + (uint32_t)(wv * (EB_ITEMS * WAVE) + k * WAVE + lane);
+            uint32_t g = 0;                                // the smallest g with s_incl[g] > o: the Gaussian that owns slot o
+#pragma unroll
+            for (uint32_t step = EB_THREADS / 2; step; step >>= 1)
+                if (s_incl[g + step - 1u] <= o) g += step;
+            const uint4 e = s_ent[g];
+            uint32_t yy, xx;
+            dup_divmod(o - e.x, e.z, true, yy, xx);
+            key[k] = ((e.y + yy * (uint32_t)a.gx + xx) << a.tshift) | s_kf[g];
+            val[k] = e.w;
+            rank[k] = 0u;
+            if (o < n_blk) rank[k] = __hip_atomic_fetch_add(&s_cnt[wv][key[k] >> bshift], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+        __syncthreads();
+        if (wv == 0) {                                     // band `lane`: exclusive prefixes over the waves, then over the bands
+            uint32_t tot = 0;
+            if (lane < TILE_SORT_MAX_BANDS) {
+#pragma unroll
+                for (int w = 0; w < EB_THREADS / WAVE; ++w) {
+                    const uint32_t c = s_cnt[w][lane];
+                    s_cnt[w][lane] = tot;
+                    tot += c;
+                }
+            }
+            const uint32_t db = wave_incl_scan_dpp(tot) - tot;
+            if (lane < TILE_SORT_MAX_BANDS) {
+                s_dbase[lane] = db;
+                s_g[lane] = gpos - db;                     // global position of stage slot 0 for the band, modulo 2^32
+                gpos += tot;                               // ranks carry over to the next chunk
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < EB_ITEMS; ++k) {
+            const uint32_t o = c0 + (uint32_t)(wv * (EB_ITEMS * WAVE) + k * WAVE + lane);
+            if (o < n_blk) {
+                const uint32_t b = key[k] >> bshift, slot = s_dbase[b] + s_cnt[wv][b] + rank[k];
+                s_k[slot] = key[k];
+                s_v[slot] = val[k];
+            }
+        }
+        __syncthreads();
+        const uint32_t chunk_n = min((uint32_t)EB_CHUNK, n_blk - c0);
+#pragma unroll
+        for (int k = 0; k < EB_ITEMS; ++k) {
+            const uint32_t p = (uint32_t)(k * EB_THREADS + t);
+            if (p < chunk_n) {
+                const uint32_t kk = s_k[p], pos = s_g[kk >> bshift] + p;
+                if (pos < a.r_cap) {                       // capacity mode: never write past the buffers
+                    a.keys[pos] = kk;
+                    a.vals[pos] = s_v[p];
+                }
+            }
+        }
+        // (the two barriers at the head of the next chunk stand between these reads and the next writes of s_g / the stage)
+    }
+}
+
+int launch_emit_banded(const mgs_camera& cam, int P, const GeometryState& g, uint32_t* keys, uint32_t* vals, uint64_t r_cap,
+                       int32_t* n_touched, const ImageState& img, uint32_t* zero_ptr, size_t zero_words, uint32_t* count,
+                       uint32_t* overflow, int bands, hipStream_t s) {
+    EmitBandedArgs a;
+    const int tb = tile_bits(cam.image_width, cam.image_height);
+    a.P = P; a.rects = g.rect; a.depth_key = g.depth_key; a.tshift = 32 - tb; a.lo = tile_depth_lo_bits(tb);
+    a.offsets = g.point_offsets; a.block_sums = g.scan_blocks; a.band_counts = g.band_counts; a.band_totals = g.band_totals;
+    a.band_live = g.band_live; a.nbands = bands; a.nblk = scan_nblocks(P, SCAN_ITEMS_PRE);
+    a.keys = keys; a.vals = vals; a.gx = tiles_x(cam.image_width);
+    a.r_cap = (uint32_t)(r_cap > 0xFFFFFFFFull ? 0xFFFFFFFFull : r_cap);
+    a.n_touched = n_touched; a.ranges = img.ranges; a.ntiles = tiles_x(cam.image_width) * tiles_y(cam.image_height);
+    a.zero_ptr = zero_ptr; a.zero_words = zero_words; a.count = count; a.overflow = overflow;
+    a.depth_err = radix_depth_error_flag(g.sort_temp, (uint64_t)P);
+    const int tile_blocks = (a.ntiles + EB_THREADS - 1) / EB_THREADS;
+    const int blocks = a.nblk > tile_blocks ? a.nblk : tile_blocks;
+    a.n_threads = blocks * EB_THREADS;
+    a.prepare = g.prepare;
+    hipLaunchKernelGGL(emit_banded_kernel, dim3(blocks), dim3(EB_THREADS), 0, s, a);
+    MGS_HIP(hipGetLastError());
+    return 0;
+}
+
 
 int launch_duplicate(const mgs_camera& cam, int P, const GeometryState& g, const BinningState& b, uint64_t r_cap,
                      int32_t* n_touched, const ImageState& img, uint64_t sort_n, int sort_bits, uint32_t* count,
@@ -512,8 +765,7 @@ int launch_duplicate(const mgs_camera& cam, int P, const GeometryState& g, const
     // output slots (see the kernel), with enough waves for ~512 slots each.  Otherwise the Gaussian-major walk: no search, fewer
     // loads per slot (C5, 2.6 instances per Gaussian: 22 us against 31 us slot-major; 102 k Gaussians at 1200x680, 13 per
     // Gaussian: 81 us against 8.6 us; 39 k at VGA, 415 k instances: 7.5 against 8.8 us).
-    const bool slot_major = P > 0 && g_opt_dup_slot_major != 0 &&
-                            (g_opt_dup_slot_major > 0 || (sort_n >= DUP_SLOT_MAJOR_MIN && sort_n >= 6ull * (uint64_t)P));
+    const bool slot_major = dup_slot_major(P, sort_n);
     if (slot_major) {
         const uint64_t want = sort_n / 8;
         if (want > (uint64_t)n) n = (int)(want > 0x3FFFFFFFull ? 0x3FFFFFFFull : want);
@@ -521,7 +773,16 @@ int launch_duplicate(const mgs_camera& cam, int P, const GeometryState& g, const
     const int n_threads = (n + 255) / 256 * 256;
     uint32_t* zero_ptr = nullptr;
     size_t zero_words = 0;
-    if (sort_n > 0) radix_zero_region(b.sort_temp, sort_n, sort_bits, &zero_ptr, &zero_words);
+    const int bands = per_tile ? tile_sort_bands_render(P, cam.image_width, cam.image_height, sort_n) : 0;
+    g_dbg_last_tile_sort_bands = bands;
+    if (sort_n > 0) {
+        if (bands) radix_banded_zero_region(b.sort_temp, sort_n, bands, &zero_ptr, &zero_words);
+        else radix_zero_region(b.sort_temp, sort_n, sort_bits, &zero_ptr, &zero_words);
+    }
+    if (bands)          // the pairs go to the ping-pong side: the ONE pass that follows ends where two passes end.  (r_cap: never
+                        // past the buffers, whatever the counts say)
+        return launch_emit_banded(cam, P, g, b.keys_b, b.vals_b, r_cap < sort_n ? r_cap : sort_n, n_touched, img, zero_ptr,
+                                  zero_words, count, overflow, bands, s);
     const bool count_digits = P > 0 && sort_bits <= 16 && radix_wants_hist(sort_n);
     const int tb = tile_bits(cam.image_width, cam.image_height);
     const int items = scan_items(P, cam.image_width, cam.image_height);
@@ -551,8 +812,11 @@ int launch_depth_sort(const GeometryState& g, int P, bool payload, hipStream_t s
 }
 
 int launch_sort(const GeometryState& g, const BinningState& b, uint64_t R, int bits, hipStream_t s, const uint32_t* n_dev,
-                bool exclusive, uint2* ranges, bool per_tile) {
+                bool exclusive, uint2* ranges, bool per_tile, int bands) {
     if (R == 0) return 0;
+    // banded: emit_banded_kernel left the pairs grouped by band on the ping-pong side; one segmented pass on the low 8 tile bits
+    if (bands)
+        return radix_sort_banded(b.keys_b, b.vals_b, b.keys_a, b.vals_a, R, 32 - bits, b.sort_temp, s, n_dev, g.band_live, bands, ranges);
     // the scratch was cleared by duplicate_kernel, which also counted the digits of the keys it emitted (small sorts; the
     // same predicate as launch_duplicate's `count_digits` -- R > 0 implies P > 0, forward_render_impl)
     const bool counted = bits <= 16 && radix_wants_hist(R) && g.tile_hist != nullptr;

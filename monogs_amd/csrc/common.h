@@ -148,12 +148,22 @@ static inline hipError_t zero_fill(void* ptr, size_t bytes, hipStream_t s) {
 struct GeometryState {
     float* rec;               // [P][16]
     uint32_t* depth_key;      // [P] float32 bits of the view-space depth (0xFFFFFFFF when culled); sort input
-    uint32_t* depth_alt;      // [P] ping-pong partner of depth_key
+    uint32_t* depth_alt;      // [P] ping-pong partner of depth_key.  NOTE: depth_alt .. perm (contiguous) are ALSO the band tables of
+                              //     the banded tile sort on the per-tile path, which runs no global depth sort (band_totals
+                              //     below): whoever uses one of the four there must move those tables first
     uint32_t* iota;           // [P] ping-pong buffers of the depth sort's values (the first pass takes value = index and
     uint32_t* iota_alt;       // [P] reads neither)
     uint32_t* perm;           // [P] Gaussian index in (depth, index) order -- culled ones last: written by the sort's final pass
     uint32_t* point_offsets;  // [P] inclusive scan, in depth order, of the tiles each Gaussian touches (w * h of its rectangle)
     uint32_t* scan_blocks;    // [scan_nblocks(P, SCAN_ITEMS_PRE) + 64]: sized for the finer of the two scan granularities
+    // Banded tile sort (binning.hip; per-tile path only, where depth_alt .. perm are free: no sub-buffers of their own)
+    uint32_t* band_totals;    // [TILE_SORT_MAX_BANDS] instances per band of 256 tiles (scan_blocks_kernel); band bases = their prefix
+    uint32_t* band_counts;    // [bands][scan_nblocks(P, SCAN_ITEMS_PRE)] instances of each 256-Gaussian scan block per band,
+                              //     band-major; counted by preprocess, scanned along each band (exclusive, in place) by
+                              //     scan_blocks_kernel
+    uint32_t* band_live;      // [TILE_SORT_MAX_BANDS] pairs per band actually emitted (emit_banded_kernel: the totals, or with
+                              //     fewer slots than instances what the kept slots hold); the segmented pass's band sizes
+    size_t band_room;         // bytes from band_totals to the end of perm
     uint8_t* clamped;         // [P][4] SH colour clamp flags
     uint2* rect;              // [P] tile rectangle {x0 | y0 << 16, w | h << 16} (w = h = 0: culled), by Gaussian index; or
                               //     (depth_sort_payload()) uint32[2 P]: the first half x0 | y0 << 8 | w << 16 | h << 24,
@@ -216,6 +226,18 @@ int scan_items(int P, int W, int H);
 inline int scan_shift(int items) { return items == SCAN_ITEMS_PRE ? 8 : 11; }
 static_assert(SCAN_ITEMS == 1 << 11 && SCAN_ITEMS_PRE == 1 << 8, "scan_shift");
 
+// Banded tile sort (binning.hip): on the per-tile path, when the tile id is wider than one 8-bit digit and the image has at
+// most TILE_SORT_MAX_BANDS bands of 256 tiles, the instances are emitted already grouped by band (exact counts from
+// preprocess) and ONE segmented 8-bit pass orders each band.  tile_sort_bands() = the number of bands, 0: the plain emission and two passes.
+constexpr int TILE_BAND_BITS = 8;
+constexpr int TILE_SORT_MAX_BANDS = 32;
+int tile_sort_bands(int P, int W, int H);
+// ... and the render call's half of the decision, once the instance count (or the capacity) R is known: the scratch of the
+// one segmented pass must fit what mgs_binning_bytes() reserves for the two passes (for a few thousand instances it does
+// not: a partial tile per band outweighs them).  0: the plain emission and the two passes, whatever preprocess counted.
+int tile_sort_bands_render(int P, int W, int H, uint64_t R);
+inline size_t band_table_bytes(int P, int bands) { return (64 + (size_t)bands * ((P + 255) / 256)) * sizeof(uint32_t); }
+
 inline int tiles_x(int W) { return (W + TILE - 1) / TILE; }
 inline int tiles_y(int H) { return (H + TILE - 1) / TILE; }
 inline int tile_bits(int W, int H) {     // bits of the tile id that can be set
@@ -268,7 +290,8 @@ struct BackwardState {
 // left in g.prepare[0] for the render call that follows, whose blend forward clears the P gradient lines (blend.hip)
 // `rects`: the rectangles in the order the scan runs in (rect_sorted after a depth sort, rect by index on the per-tile path)
 // `items`: scan_items() of this forward; SCAN_ITEMS_PRE: preprocess wrote the block-local sums, only the block sums are scanned
-int launch_scan(const GeometryState& g, int P, hipStream_t s, bool exclusive, const uint2* rects, int items);
+// `bands`: tile_sort_bands() of this forward (SCAN_ITEMS_PRE only): the launch also scans the band counts along each band
+int launch_scan(const GeometryState& g, int P, hipStream_t s, bool exclusive, const uint2* rects, int items, int bands = 0);
 // `r_cap`: capacity of the binning buffers; `count` (device): [0] live instance count min(R, r_cap), [1] overflow flag
 // `per_tile`: emit in Gaussian-index order with the depth bits packed into the pairs (binning_path() == 1)
 int launch_duplicate(const mgs_camera& cam, int P, const GeometryState& g, const BinningState& b, uint64_t r_cap,
@@ -297,6 +320,13 @@ int radix_sort_pairs(uint32_t* ka, uint32_t* va, uint32_t* kb, uint32_t* vb, uin
                      int key_shift = 0);                     // the bits sorted are [key_shift, key_shift + bits); ranges are indexed
                                                              // by key >> key_shift, and the final pass keeps the keys
 bool radix_wants_hist(uint64_t n);
+// Banded tile sort (radix_sort.hip): (ka, va) hold <= 32 independent runs end to end, run b of band_totals[b] pairs (device);
+// ONE counted-tiles pass on key bits [key_shift, key_shift + 8) orders each run into the same positions of (kb, vb) and
+// writes `ranges` (indexed by key >> key_shift).  Scratch: radix_banded_temp_bytes(n, bands), its zero region as for the other sorts.
+size_t radix_banded_temp_bytes(uint64_t n, int bands);
+void radix_banded_zero_region(void* temp, uint64_t n, int bands, uint32_t** ptr, size_t* words);
+int radix_sort_banded(const uint32_t* ka, const uint32_t* va, uint32_t* kb, uint32_t* vb, uint64_t n, int key_shift, void* temp,
+                      hipStream_t s, const uint32_t* n_dev, const uint32_t* band_totals, int bands, uint2* ranges);
 // The forward's first sort (radix_sort.hip): depth keys -> perm + rect_sorted; three 9-bit passes (+ a fourth that only
 // runs for depths beyond 13 107 units).  radix_depth_payload(n): the sort carries the packed rectangles itself.
 bool radix_depth_payload(uint64_t n);
@@ -307,7 +337,8 @@ int radix_sort_depth(uint32_t* keys, uint32_t* key_b, uint32_t* val_a, uint32_t*
 inline bool depth_sort_payload(int P, int W, int H) { return radix_depth_payload((uint64_t)P) && tiles_x(W) <= 255 && tiles_y(H) <= 255; }
 int launch_depth_sort(const GeometryState& g, int P, bool payload, hipStream_t s, bool exclusive = false);
 int launch_sort(const GeometryState& g, const BinningState& b, uint64_t R, int bits, hipStream_t s,
-                const uint32_t* n_dev = nullptr, bool exclusive = false, uint2* ranges = nullptr, bool per_tile = false);
+                const uint32_t* n_dev = nullptr, bool exclusive = false, uint2* ranges = nullptr, bool per_tile = false,
+                int bands = 0 /* tile_sort_bands() of this forward: one segmented pass behind the banded emission */);
 // per-tile depth order: each tile's list, grouped by the tile sort in index order, sorted by (depth, index) in place
 // (tile_sort.h) -- by blend_forward_kernel (launch_blend_forward's `tile_sort`) or by a launch of its own
 struct TileSortArgs {
@@ -326,8 +357,8 @@ int launch_tile_depth_sort(const mgs_camera& cam, const TileSortArgs& ts, const 
                            hipStream_t s);
 int set_radix_spin_limit(uint32_t limit);
 extern bool g_opt_blend_bwd_transposed_set;
-extern int g_dbg_last_bwd_split;
-extern int g_opt_radix_ballot_rank, g_opt_radix_scanned, g_opt_radix_xcd_band, g_opt_knn_grid_min, g_opt_scan_small, g_opt_pre_scan, g_opt_dup_slot_major, g_opt_blend_bwd_transposed, g_opt_blend_bwd_split, g_opt_blend_bwd_split_min, g_opt_blend_bwd_split_frac;      // test knobs (mgs_debug_set_option)
+extern int g_dbg_last_bwd_split, g_dbg_last_tile_sort_bands;
+extern int g_opt_radix_ballot_rank, g_opt_radix_scanned, g_opt_radix_xcd_band, g_opt_knn_grid_min, g_opt_scan_small, g_opt_pre_scan, g_opt_tile_sort_banded, g_opt_dup_slot_major, g_opt_blend_bwd_transposed, g_opt_blend_bwd_split, g_opt_blend_bwd_split_min, g_opt_blend_bwd_split_frac;      // test knobs (mgs_debug_set_option)
 // `sort_err`: the tile sort's error words (NULL: nothing was sorted); a raised word empties every tile and sets
 // MGS_STATUS_TILE_SORT_TIMEOUT in *status (what ranges_kernel did until round 4).  `tile_sort` (per-tile depth order, or
 // NULL): every workgroup first sorts its tile's list (tile_sort.h)

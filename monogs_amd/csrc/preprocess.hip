@@ -176,6 +176,8 @@ struct PreArgs {
     size_t zero_words;
     uint32_t* point_offsets;  // SCAN: [P] block-local inclusive scan of the tiles touched, [ceil(P / 256)] block totals
     uint32_t* scan_blocks;
+    uint32_t* band_counts;    // SCAN, banded tile sort (binning.hip): [nbands][ceil(P / 256)] instances of the workgroup's
+    int nbands, nblk;         //       Gaussians per band of 256 tiles (band-major: the column scan reads rows); else NULL
     float* grad_acc;          // optional: accumulator of the backward that will follow ([P][16] + pose slots + 16): the
                               //           pose part is cleared here, the P lines by the blend forward that follows, which
     unsigned long long* prepare;   //      finds the accumulator's address (or 0: nothing to clear) in prepare[0]
@@ -286,7 +288,7 @@ __device__ __forceinline__ bool preprocess_one(const PreArgs& a, const Cam& c, i
 // One Gaussian, idx < P: loads, projection, every per-Gaussian output.  Returns the tiles it touches (w * h of its
 // rectangle; 0: culled).  `s_rec`: the workgroup's record hand-over rows (per wave; a lane's fifth float4 is padding).
 template <bool COV, bool PRECOMP>
-__device__ __forceinline__ uint32_t preprocess_gaussian(const PreArgs& a, const int idx, float4 (*s_rec)[WAVE * 5]) {
+__device__ __forceinline__ uint32_t preprocess_gaussian(const PreArgs& a, const int idx, float4 (*s_rec)[WAVE * 5], uint2& rect) {
     // ---- every per-Gaussian input is requested up front: ONE memory round trip before the arithmetic starts (a load
     //      placed behind each early exit used to cost a dependent round trip of its own; the 32 bytes this reads for a
     //      Gaussian that turns out to be culled are cheaper than the latency they hide)
@@ -352,6 +354,7 @@ __device__ __forceinline__ uint32_t preprocess_gaussian(const PreArgs& a, const 
     // (The gradient lines of the accumulator are NOT cleared here: this kernel runs at the copy ceiling, where their 64 bytes
     //  per Gaussian cost 17 us at 2 M.  The blend forward of the render call that follows clears them while the memory
     //  system is mostly idle -- blend.hip, through a.prepare.)
+    rect = vis ? o.rect : make_uint2(0u, 0u);
     return vis ? (o.rect.y & 0xFFFFu) * (o.rect.y >> 16) : 0u;
 }
 
@@ -371,7 +374,8 @@ __global__ void __launch_bounds__(256) preprocess_forward_kernel(PreArgs a) {
     __shared__ float4 s_rec[4][WAVE * 5];
     // (a predicate, not an early return: with SCAN every thread of every workgroup must reach the barrier below)
     uint32_t nt = 0u;                                      // lanes past P and culled Gaussians count 0
-    if (idx < a.P) nt = preprocess_gaussian<COV, PRECOMP>(a, idx, s_rec);
+    uint2 rect = make_uint2(0u, 0u);
+    if (idx < a.P) nt = preprocess_gaussian<COV, PRECOMP>(a, idx, s_rec, rect);
     if (SCAN) {
         // all 256 threads are here, EXEC is full: DPP wave scan, the four waves joined through LDS.  The wave totals go to
         // the padding float4 of lane 0's hand-over row (never touched by the hand-over), so the kernel's LDS -- 20 480
@@ -380,11 +384,36 @@ __global__ void __launch_bounds__(256) preprocess_forward_kernel(PreArgs a) {
         const uint32_t sc = wave_incl_scan_dpp(nt);
         uint32_t* tot = reinterpret_cast<uint32_t*>(&s_rec[0][4]);
         if (lane == 63) tot[wv] = sc;
+        // Banded tile sort: the workgroup's instances per band of 256 tiles, exact, in 32 counters that live in the padding
+        // float4 of the hand-over rows 1-8 (four each).  A row of the rectangle is a contiguous range of tile ids; a band
+        // boundary can cut it (120 tiles per row at 1080p: a band is 2.13 rows).
+        const bool band = a.band_counts != nullptr;            // (grid-uniform)
+        uint32_t* bc = reinterpret_cast<uint32_t*>(&s_rec[0][(1 + (threadIdx.x >> 2)) * 5 + 4]) + (threadIdx.x & 3);   // threads < 32
+        if (band && threadIdx.x < 32) *bc = 0u;
         __syncthreads();
         const uint32_t t0 = tot[0], t1 = tot[1], t2 = tot[2], t3 = tot[3];
         const uint32_t base = (wv > 0 ? t0 : 0u) + (wv > 1 ? t1 : 0u) + (wv > 2 ? t2 : 0u);
         if (idx < a.P) a.point_offsets[idx] = base + sc;
         if (threadIdx.x == 0) a.scan_blocks[blockIdx.x] = (t0 + t1) + (t2 + t3);
+        if (band) {
+            auto counter = [&](uint32_t b) { return reinterpret_cast<uint32_t*>(&s_rec[0][(1 + (b >> 2)) * 5 + 4]) + (b & 3u); };
+            if (nt) {
+                const uint32_t w = rect.y & 0xFFFFu, h = rect.y >> 16;
+                const uint32_t first = (rect.x >> 16) * (uint32_t)a.gx + (rect.x & 0xFFFFu);      // tile id of the corner
+                const uint32_t last = first + (h - 1u) * (uint32_t)a.gx + w - 1u;
+                if ((first >> 8) == (last >> 8)) {
+                    atomicAdd(counter(first >> 8), nt);
+                } else {
+                    for (uint32_t r = 0, lo = first; r < h; ++r, lo += (uint32_t)a.gx) {
+                        const uint32_t hi = lo + w;                                              // the row's ids: [lo, hi)
+                        for (uint32_t b = lo >> 8; b <= (hi - 1u) >> 8; ++b)
+                            atomicAdd(counter(b), min(hi, (b + 1u) << 8) - max(lo, b << 8));
+                    }
+                }
+            }
+            __syncthreads();
+            if ((int)threadIdx.x < a.nbands) a.band_counts[(size_t)threadIdx.x * a.nblk + blockIdx.x] = *bc;
+        }
     }
 }
 
@@ -421,6 +450,12 @@ int launch_preprocess_forward(const mgs_camera& cam, int P, const float* means3D
     // the scan folded in (see the kernel): the same host-side decision launch_scan and launch_duplicate take
     const bool scan = scan_items(P, cam.image_width, cam.image_height) == SCAN_ITEMS_PRE;
     a.point_offsets = g.point_offsets; a.scan_blocks = g.scan_blocks;
+    // banded tile sort: the same host-side decision launch_scan, launch_duplicate and launch_sort take
+    a.nbands = tile_sort_bands(P, cam.image_width, cam.image_height);
+    a.band_counts = a.nbands ? g.band_counts : nullptr;
+    // (the tables lie over the global depth sort's four idle u32[P] buffers: P / 2 + 256 bytes against >= 16 P)
+    if (a.nbands && band_table_bytes(P, a.nbands) > g.band_room) { set_error("band tables do not fit the geometry scratch"); return 1; }
+    a.nblk = (int)grid.x;
 #define MGS_PRE(COV, PRECOMP)                                                                                      \
     do {                                                                                                           \
         if (scan) hipLaunchKernelGGL((preprocess_forward_kernel<COV, PRECOMP, true>), grid, block, 0, s, a);       \

@@ -218,14 +218,20 @@ struct RsTemp {
     size_t zero_bytes;     // everything from `hist` that must be zero before the sort
     size_t bytes;
 };
-static RsTemp rs_carve(void* temp, uint64_t n, const RsPlan& pl, bool scanned) {
+// the header every layout of the scratch starts with (radix_error_flag() finds the error words through it, whichever sort
+// runs on the scratch); returns where the rest begins
+static char* rs_carve_header(void* temp, int radix, RsTemp& t) {
     char* p = (char*)align_up((size_t)temp, 256);
-    RsTemp t;
     t.hist = (uint32_t*)p;
-    t.tickets = t.hist + RS_MAX_PASSES * pl.radix;
+    t.tickets = t.hist + RS_MAX_PASSES * radix;
     t.error = t.tickets + RS_MAX_PASSES;      // one word per pass
     t.wide = t.error + RS_MAX_PASSES;
-    char* q = (char*)align_up((size_t)(t.wide + 1), 256);
+    return (char*)align_up((size_t)(t.wide + 1), 256);
+}
+static RsTemp rs_carve(void* temp, uint64_t n, const RsPlan& pl, bool scanned) {
+    RsTemp t;
+    char* q = rs_carve_header(temp, pl.radix, t);
+    char* p = (char*)t.hist;
     t.status = (uint64_t*)q;
     t.sums = (uint32_t*)q;
     const uint32_t tiles = rs_tiles(n, scanned);
@@ -321,10 +327,49 @@ struct RsTileHistArgs {
     uint32_t* wide;           // depth keys: the wide flag
     int detect;               // ... this launch reads the keys first: raise it for a visible key beyond the narrow passes
     int only_if_wide;         // ... this launch belongs to the fourth pass
+    const uint32_t* band_totals;   // BANDED: [bands] pairs per band (device); see radix_sort_banded
+    int bands;
 };
+
+// ---- BANDED: the input is <= 32 independent sorts laid end to end -- band b holds band_totals[b] pairs, from the prefix over the
+// totals of the bands before it -- and ONE launch sorts them all (radix_sort_banded).  Every workgroup forms the table of
+// the bands in one wave: first pair and length of each band, clamped to the live count (capacity mode), and the cumulative
+// number of sort tiles, band b having ceil(len / TILE_PAIRS) of them -- only the last one of a band is partial.
+constexpr int RS_MAX_BANDS = TILE_SORT_MAX_BANDS;
+struct RsBandLds {
+    uint32_t base[RS_MAX_BANDS], len[RS_MAX_BANDS], T[RS_MAX_BANDS + 1];       // T[b] = tiles of the bands before b, T[32] = all
+};
+template <uint32_t TILE_PAIRS>
+__device__ __forceinline__ void rs_band_table(const uint32_t* __restrict__ totals, int bands, uint32_t n_live, RsBandLds& s, int wv, int lane) {
+    if (wv == 0) {                                   // (a full wave: DPP scans)
+        const uint32_t tot = lane < bands ? totals[lane] : 0u;
+        const uint32_t incl = wave_incl_scan_dpp(tot);
+        const uint32_t lo = min(incl - tot, n_live), hi = min(incl, n_live);
+        const uint32_t nt = (hi - lo + TILE_PAIRS - 1u) / TILE_PAIRS;
+        const uint32_t tincl = wave_incl_scan_dpp(nt);
+        if (lane < RS_MAX_BANDS) { s.base[lane] = lo; s.len[lane] = hi - lo; s.T[lane] = tincl - nt; }
+        if (lane == 63) s.T[RS_MAX_BANDS] = tincl;
+    }
+    __syncthreads();
+}
+// the last band b with start(b) <= x, for a non-decreasing start with start(0) = 0 (bands without tiles share their start with
+// the next band that has some, or with the end: they are never found for an x below the end)
+template <class F>
+__device__ __forceinline__ uint32_t rs_band_find(uint32_t x, F start) {
+    uint32_t b = 0;
+#pragma unroll
+    for (uint32_t step = RS_MAX_BANDS / 2; step; step >>= 1)
+        if (start(b + step) <= x) b += step;
+    return b;
+}
+// Trees: every band has a tree of its own over its tiles, so that a tile adds up what lies before it IN ITS BAND.  Level 0 is
+// dense (row = T[b] + tile in band).  At level l >= 1 band b's nodes start at row (T[b] >> 2 l) + b of the level: the bands'
+// row ranges cannot overlap (floor(T / q) + ceil(n / q) <= floor((T + n) / q) + 1), at the price of <= one unused row per band.
+__device__ __forceinline__ uint32_t rs_band_row(const RsBandLds& s, uint32_t b, int l) { return l == 0 ? s.T[b] : (s.T[b] >> (RS_FAN_LOG * l)) + b; }
+
 // TPW = tiles per workgroup (1 or 4), DB = digit bits (8 or 9)
-template <int ITEMS, int TPW, int DB>
-__global__ void __launch_bounds__(RS_THREADS * TPW) rs_tile_hist_kernel(RsTileHistArgs a) {
+template <int ITEMS, int TPW, int DB, bool BANDED>
+__device__ __forceinline__ void rs_tile_hist_body(const RsTileHistArgs& a) {
     static_assert(TPW == 1 || TPW == (1 << RS_FAN_LOG), "a workgroup counts one tile or one level-1 node");
     constexpr int RADIX = 1 << DB, DPT = RADIX / RS_THREADS, COPIES = 16 / DPT;     // 16 KB of counters per tile
     constexpr uint32_t TILE_PAIRS = RS_THREADS * ITEMS;
@@ -337,9 +382,42 @@ __global__ void __launch_bounds__(RS_THREADS * TPW) rs_tile_hist_kernel(RsTileHi
     // dead has nothing to write: nobody reads the count row of a dead tile (a tile adds up rows of EARLIER siblings only),
     // and the tree rows it would add zeros to were cleared with the sort's scratch.  (With a single level -- at most 8 tiles,
     // never the case on this path -- the count rows ARE the top level, which is read in full.)
-    if (a.tr.levels > 1 && (uint64_t)blockIdx.x * TPW * TILE_PAIRS >= n_live) return;
-    const uint32_t tile = blockIdx.x * TPW + q, tile_start = tile * TILE_PAIRS;
-    const uint32_t tile_n = tile_start < n_live ? min(TILE_PAIRS, n_live - tile_start) : 0u;     // 0: dead (capacity mode) or past the end
+    uint32_t tile, tile_start, tile_n;         // tile_n 0: dead (capacity mode) or past the end
+    bool tile_row;                             // the tile has a row of counts
+    uint32_t node1 = blockIdx.x;               // TPW == 4: this workgroup's level-1 row
+    uint32_t bT = 0, bb = 0, bj = 0;           // BANDED: tiles before the band, the band, the tile in the band
+    if constexpr (BANDED) {
+        // a workgroup is one tile of one band (TPW == 1: block id = dense tile id) or one level-1 node of one band's tree
+        // (TPW == 4: block id = row of level 1, the bands' unused rows included)
+        __shared__ RsBandLds s_band;
+        rs_band_table<TILE_PAIRS>(a.band_totals, a.bands, n_live, s_band, threadIdx.x >> 6, lane);      // (the workgroup's first wave)
+        uint32_t b, jt;
+        if (TPW == 1) {
+            if (blockIdx.x >= s_band.T[RS_MAX_BANDS]) return;
+            b = rs_band_find(blockIdx.x, [&](uint32_t x) { return s_band.T[x]; });
+            jt = blockIdx.x - s_band.T[b];
+        } else {
+            b = rs_band_find(blockIdx.x, [&](uint32_t x) { return rs_band_row(s_band, x, 1); });
+            jt = (blockIdx.x - rs_band_row(s_band, b, 1)) * TPW + q;
+        }
+        const uint32_t ntile = s_band.T[b + 1] - s_band.T[b];
+        if (jt - q >= ntile) return;                                   // (workgroup-uniform: an unused row, or past the end)
+        tile = s_band.T[b] + jt; tile_row = jt < ntile;
+        tile_start = s_band.base[b] + jt * TILE_PAIRS;
+        tile_n = tile_row ? min(TILE_PAIRS, s_band.len[b] - jt * TILE_PAIRS) : 0u;
+        bT = s_band.T[b]; bb = b; bj = jt;
+        if (TPW != 1) node1 = blockIdx.x;
+    } else {
+        if (a.tr.levels > 1 && (uint64_t)blockIdx.x * TPW * TILE_PAIRS >= n_live) return;
+        tile = blockIdx.x * TPW + q; tile_start = tile * TILE_PAIRS;
+        tile_n = tile_start < n_live ? min(TILE_PAIRS, n_live - tile_start) : 0u;
+        tile_row = tile < a.tiles;
+    }
+    // row of the tile's ancestor at level l >= 1
+    auto up = [&](int l) -> uint32_t {
+        if constexpr (BANDED) return (bT >> (RS_FAN_LOG * l)) + bb + (bj >> (RS_FAN_LOG * l));
+        else return tile >> (RS_FAN_LOG * l);
+    };
     uint32_t k[ITEMS];
 #pragma unroll
     for (int i = 0; i < ITEMS; ++i) {
@@ -370,14 +448,14 @@ __global__ void __launch_bounds__(RS_THREADS * TPW) rs_tile_hist_kernel(RsTileHi
         c[j] = 0;
 #pragma unroll
         for (int i = 0; i < COPIES; ++i) c[j] += wh[q][i][t * DPT + j];
-        if (tile < a.tiles) a.counts[(size_t)tile * RADIX + t * DPT + j] = c[j];       // dead tiles: zeros
+        if (tile_row) a.counts[(size_t)tile * RADIX + t * DPT + j] = c[j];       // dead tiles: zeros
     }
     if (TPW == 1) {
 #pragma unroll
         for (int j = 0; j < DPT; ++j)
             if (c[j])
                 for (int l = 1; l < a.tr.levels; ++l)
-                    atomicAdd(a.sums + ((size_t)a.tr.off[l] + (tile >> (RS_FAN_LOG * l))) * RADIX + t * DPT + j, c[j]);
+                    atomicAdd(a.sums + ((size_t)a.tr.off[l] + up(l)) * RADIX + t * DPT + j, c[j]);
     } else if (a.tr.levels > 1) {
         __syncthreads();
 #pragma unroll
@@ -389,16 +467,20 @@ __global__ void __launch_bounds__(RS_THREADS * TPW) rs_tile_hist_kernel(RsTileHi
                 uint32_t s1 = 0;
 #pragma unroll
                 for (int m = 0; m < TPW; ++m) s1 += wh[m][0][t * DPT + j];
-                a.sums[((size_t)a.tr.off[1] + blockIdx.x) * RADIX + t * DPT + j] = s1;         // level 1: this workgroup's own row
+                a.sums[((size_t)a.tr.off[1] + node1) * RADIX + t * DPT + j] = s1;         // level 1: this workgroup's own row
                 if (s1)
                     for (int l = 2; l < a.tr.levels; ++l)
-                        atomicAdd(a.sums + ((size_t)a.tr.off[l] + (blockIdx.x >> (RS_FAN_LOG * (l - 1)))) * RADIX + t * DPT + j, s1);
+                        atomicAdd(a.sums + ((size_t)a.tr.off[l] + up(l)) * RADIX + t * DPT + j, s1);
             }
         }
     }
     RS_DRAIN();
     RS_HSTAMP(3);
 }
+template <int ITEMS, int TPW, int DB>
+__global__ void __launch_bounds__(RS_THREADS * TPW) rs_tile_hist_kernel(RsTileHistArgs a) { rs_tile_hist_body<ITEMS, TPW, DB, false>(a); }
+template <int ITEMS, int TPW>
+__global__ void __launch_bounds__(RS_THREADS * TPW) rs_tile_hist_banded_kernel(RsTileHistArgs a) { rs_tile_hist_body<ITEMS, TPW, 8, true>(a); }
 template <int ITEMS, int DB>
 static void rs_launch_tile_hist(const RsTileHistArgs& a, hipStream_t s) {
     if (a.tiles >= 1024u)
@@ -440,6 +522,8 @@ struct RsPassArgs {
     const uint32_t* counts;   // counted tiles: [tiles][radix] digit counts of every tile for this pass
     const uint32_t* sums;     // counted tiles: the levels >= 1 of the tree over them (RsTreeArgs)
     RsTreeArgs tree;
+    const uint32_t* band_totals;   // BANDED: [bands] pairs per band (device); see radix_sort_banded
+    int bands;
 };
 
 // value x[i] sits at slot[i] of the digit-ordered tile: returns in x[i] the value of slot i * 256 + t (the staging buffer
@@ -510,8 +594,11 @@ __device__ __forceinline__ bool rs_gather(const uint64_t* row, size_t stride, ui
 // PAYLOAD:         a second value travels with the pair.
 // BALLOT:          rank with one ballot per digit bit and item instead of one returning LDS atomic (reference for the tests).
 // VIDX:            value = index of the pair; vin is not read (first pass of the depth sort).
-template <int ITEMS, int DB, bool SCANNED, bool PAYLOAD, bool BALLOT, bool VIDX>
-__global__ void __launch_bounds__(RS_THREADS, (SCANNED && ITEMS == RS_ITEMS_WIDE && DB == 8 && !PAYLOAD) ? 7 : 1) rs_pass_kernel(RsPassArgs a) {
+// BANDED:          the input is <= 32 independent sorts end to end (rs_band_table): a tile belongs to one band, adds up the
+//                  tiles before it in the band's own tree and writes behind the band's first pair.
+template <int ITEMS, int DB, bool SCANNED, bool PAYLOAD, bool BALLOT, bool VIDX, bool BANDED>
+__device__ __forceinline__ void rs_pass_body(const RsPassArgs& a) {
+    static_assert(!BANDED || (SCANNED && !VIDX), "banded passes are counted-tiles passes over pairs");
     constexpr int TILE_PAIRS = RS_THREADS * ITEMS;
     constexpr int RADIX = 1 << DB, DPT = RADIX / RS_THREADS;
     constexpr int SBUF = (SCANNED && 2 * RS_WAVES * RADIX > TILE_PAIRS) ? 2 * RS_WAVES * RADIX : TILE_PAIRS;
@@ -539,6 +626,8 @@ __global__ void __launch_bounds__(RS_THREADS, (SCANNED && ITEMS == RS_ITEMS_WIDE
         if (failed) return;
     }
     const uint32_t n_live = a.n_dev ? min(a.n, a.n_dev[0]) : a.n;
+    __shared__ RsBandLds s_band;                         // (BANDED only: unused, and not allocated, otherwise)
+    if constexpr (BANDED) rs_band_table<(uint32_t)TILE_PAIRS>(a.band_totals, a.bands, n_live, s_band, wv, lane);
     if (t == 0) {
         uint32_t id = blockIdx.x;
         if (a.xcd_band) {
@@ -548,7 +637,7 @@ __global__ void __launch_bounds__(RS_THREADS, (SCANNED && ITEMS == RS_ITEMS_WIDE
             // is written in pieces by several L2s.  One contiguous band of the LIVE tiles per XCD lets the pieces meet in
             // ONE L2 before the line leaves it: tile sort 83 -> 58 us, depth sort 102 -> 94 us at C5 (round 4).  (Capacity
             // mode launches tiles for the capacity: banding those would leave the XCDs of the last bands without work.)
-            const uint32_t live = (n_live + (uint32_t)TILE_PAIRS - 1) / (uint32_t)TILE_PAIRS;
+            const uint32_t live = BANDED ? s_band.T[RS_MAX_BANDS] : (n_live + (uint32_t)TILE_PAIRS - 1) / (uint32_t)TILE_PAIRS;
             const uint32_t q = live >> 3, r = live & 7u, x = id & 7u, j = id >> 3;
             id = j < q + (x < r ? 1u : 0u) ? x * q + min(x, r) + j : 0xFFFFFFFFu;      // (its XCD's band is handed out: nothing to do)
         }
@@ -559,12 +648,35 @@ __global__ void __launch_bounds__(RS_THREADS, (SCANNED && ITEMS == RS_ITEMS_WIDE
 #pragma unroll
         for (int j = 0; j < DPT; ++j) wave_hist[w][t * DPT + j] = 0;
     __syncthreads();
-    const uint32_t tile = s_tile;
+    uint32_t tile = s_tile;
     if (tile == 0xFFFFFFFFu) return;
-    const uint32_t tile_start = tile * (uint32_t)TILE_PAIRS;
-    if (tile_start >= n_live) return;        // capacity mode: tiles past the live count have nothing to do
+    uint32_t tile_start = tile * (uint32_t)TILE_PAIRS, tile_n;
+    uint32_t band = 0, band_T = 0, band_base = 0, top_rows = a.tree.top_rows;
+    if constexpr (BANDED) {
+        // `tile` so far: the dense id over all bands' tiles.  From here on: the tile's number IN ITS BAND; tile_start: its first
+        // pair in the input (the band's output starts at the band's first pair too: there is no padding)
+        if (tile >= s_band.T[RS_MAX_BANDS]) return;
+        // (everything here is workgroup-uniform but comes out of LDS: readfirstlane keeps it in scalar registers -- the 3072-pair
+        //  kernel has none of its 72 vector registers to spare)
+        auto uni = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
+        tile = uni(tile);
+        band = uni(rs_band_find(tile, [&](uint32_t x) { return s_band.T[x]; }));
+        band_T = uni(s_band.T[band]); band_base = uni(s_band.base[band]);
+        tile -= band_T;
+        tile_n = uni(min((uint32_t)TILE_PAIRS, s_band.len[band] - tile * (uint32_t)TILE_PAIRS));
+        tile_start = band_base + tile * (uint32_t)TILE_PAIRS;
+        const int top_shift = RS_FAN_LOG * (a.tree.levels - 1);
+        top_rows = uni((s_band.T[band + 1] - band_T + (1u << top_shift) - 1u) >> top_shift);
+    } else {
+        if (tile_start >= n_live) return;    // capacity mode: tiles past the live count have nothing to do
                                              // (tickets are dense, so no live tile ever looks back at them)
-    const uint32_t tile_n = min((uint32_t)TILE_PAIRS, n_live - tile_start);
+        tile_n = min((uint32_t)TILE_PAIRS, n_live - tile_start);
+    }
+    // first row of the tree level the tile's siblings are found in (BANDED: the band's own tree, rs_band_row)
+    auto level_row0 = [&](int l) -> uint32_t {
+        if constexpr (BANDED) return l == 0 ? band_T : (band_T >> (RS_FAN_LOG * l)) + band;
+        else return 0u;
+    };
 
     // ---- digits t * DPT + j: count over the whole input (hcount) and, counted tiles, over everything before this tile
     //      (before).  Requested first: needed only after the ranking, their round trips hide behind the key loads.
@@ -581,7 +693,8 @@ __global__ void __launch_bounds__(RS_THREADS, (SCANNED && ITEMS == RS_ITEMS_WIDE
     const int levels = a.tree.levels;
     const uint32_t top_node = tile >> (RS_FAN_LOG * (levels - 1));
     const uint4* __restrict__ c4 = reinterpret_cast<const uint4*>(a.counts);
-    const uint4* __restrict__ top4 = levels == 1 ? c4 : reinterpret_cast<const uint4*>(a.sums) + (size_t)a.tree.off[levels - 1] * R4;
+    const uint4* __restrict__ top4 = (levels == 1 ? c4 : reinterpret_cast<const uint4*>(a.sums) + (size_t)a.tree.off[levels - 1] * R4) +
+                                     (size_t)level_row0(levels - 1) * R4;
     if (SCANNED) {
 #pragma unroll
         for (int l = 0; l < RS_MAX_LEVELS - 1; ++l) {
@@ -590,12 +703,12 @@ __global__ void __launch_bounds__(RS_THREADS, (SCANNED && ITEMS == RS_ITEMS_WIDE
             const uint4* base = (l == 0 || !have) ? c4 : reinterpret_cast<const uint4*>(a.sums) + (size_t)a.tree.off[l] * R4;
             lw[l] = (have && (uint32_t)wv < nb) ? 1u : 0u;                     // wave w takes sibling w
 #pragma unroll
-            for (int j = 0; j < DPT; ++j) lv[l][j] = base[(size_t)(lw[l] ? first + (uint32_t)wv : 0u) * R4 + j * WAVE + lane];
+            for (int j = 0; j < DPT; ++j) lv[l][j] = base[(size_t)(lw[l] ? level_row0(l) + first + (uint32_t)wv : 0u) * R4 + j * WAVE + lane];
         }
 #pragma unroll
         for (int q = 0; q < RS_TOP_BATCH / RS_WAVES; ++q) {
             const uint32_t r = (uint32_t)wv + 4u * q;
-            tw[q] = r < a.tree.top_rows ? 1u : 0u;
+            tw[q] = r < top_rows ? 1u : 0u;
             tb[q] = r < top_node ? 1u : 0u;
 #pragma unroll
             for (int j = 0; j < DPT; ++j) tv[q][j] = top4[(size_t)(tw[q] ? r : 0u) * R4 + j * WAVE + lane];
@@ -631,11 +744,11 @@ __global__ void __launch_bounds__(RS_THREADS, (SCANNED && ITEMS == RS_ITEMS_WIDE
                 at.x += tw[q] ? tv[q][j].x : 0u; at.y += tw[q] ? tv[q][j].y : 0u; at.z += tw[q] ? tv[q][j].z : 0u; at.w += tw[q] ? tv[q][j].w : 0u;
                 ab.x += tb[q] ? tv[q][j].x : 0u; ab.y += tb[q] ? tv[q][j].y : 0u; ab.z += tb[q] ? tv[q][j].z : 0u; ab.w += tb[q] ? tv[q][j].w : 0u;
             }
-            for (uint32_t r0 = RS_TOP_BATCH; r0 < a.tree.top_rows; r0 += RS_TOP_BATCH)      // > 8192 tiles only
+            for (uint32_t r0 = RS_TOP_BATCH; r0 < top_rows; r0 += RS_TOP_BATCH)      // > 8192 tiles only
 #pragma unroll
                 for (int q = 0; q < RS_TOP_BATCH / RS_WAVES; ++q) {
                     const uint32_t r = r0 + (uint32_t)wv + 4u * q;
-                    if (r < a.tree.top_rows) {
+                    if (r < top_rows) {
                         const uint4 v = top4[(size_t)r * R4 + j * WAVE + lane];
                         at.x += v.x; at.y += v.y; at.z += v.z; at.w += v.w;
                         if (r < top_node) { ab.x += v.x; ab.y += v.y; ab.z += v.z; ab.w += v.w; }
@@ -720,7 +833,20 @@ __global__ void __launch_bounds__(RS_THREADS, (SCANNED && ITEMS == RS_ITEMS_WIDE
     if constexpr (SCANNED) {
         rs_digit_bases<DPT>(hcount, gdigit_base, wsum, lane, wv);
 #pragma unroll
-        for (int j = 0; j < DPT; ++j) gbase[t * DPT + j] = gdigit_base[j] + before[j] - dbase[j];
+        for (int j = 0; j < DPT; ++j) gbase[t * DPT + j] = band_base + gdigit_base[j] + before[j] - dbase[j];
+        if constexpr (BANDED) {
+            // The ranges of the band's 256 keys ARE its digit bases and totals, which every tile of the band has just formed:
+            // the band's first tile stores them, plain stores, once.  (Opened and closed from the neighbouring keys as below,
+            // every sort tile offers a piece of every key of its band: 2 x 256 atomics per tile on 54 tiles' worth of
+            // contention per word -- the pass took 43.7 us at C5 instead of 21.)  A key without pairs keeps its preset.
+            if (a.ranges && tile == 0u) {
+#pragma unroll
+                for (int j = 0; j < DPT; ++j)
+                    if (hcount[j])
+                        a.ranges[(band << DB) + (uint32_t)(t * DPT + j)] =
+                            make_uint2(band_base + gdigit_base[j], band_base + gdigit_base[j] + hcount[j]);
+            }
+        }
         __syncthreads();
     } else {
         // ---- publish, gather, publish: a two-level all-gather of the tiles' digit counts (one digit per thread).
@@ -797,7 +923,7 @@ __global__ void __launch_bounds__(RS_THREADS, (SCANNED && ITEMS == RS_ITEMS_WIDE
             if (a.kfinal) a.kfinal[g[i]] = key[i];
             a.vfinal[g[i]] = val[i];
         }
-    if (a.ranges) {
+    if (!BANDED && a.ranges) {
         // The per-key ranges (the rasteriser's tile ranges), from the keys this thread holds in output order: equal keys are
         // neighbours in the tile's digit-ordered array (same digit; the earlier passes ordered the rest), so an element whose
         // LEFT neighbour carries another key opens its key's run inside this tile and closes the neighbour's; the tile's
@@ -859,6 +985,15 @@ __global__ void __launch_bounds__(RS_THREADS, (SCANNED && ITEMS == RS_ITEMS_WIDE
     }
     RS_DRAIN();
     RS_STAMP(7);
+}
+
+template <int ITEMS, int DB, bool SCANNED, bool PAYLOAD, bool BALLOT, bool VIDX>
+__global__ void __launch_bounds__(RS_THREADS, (SCANNED && ITEMS == RS_ITEMS_WIDE && DB == 8 && !PAYLOAD) ? 7 : 1) rs_pass_kernel(RsPassArgs a) {
+    rs_pass_body<ITEMS, DB, SCANNED, PAYLOAD, BALLOT, VIDX, false>(a);
+}
+template <int ITEMS>
+__global__ void __launch_bounds__(RS_THREADS, ITEMS == RS_ITEMS_WIDE ? 7 : 1) rs_pass_banded_kernel(RsPassArgs a) {
+    rs_pass_body<ITEMS, 8, true, false, false, false, true>(a);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -978,6 +1113,7 @@ static int rs_run(const RsPlan& pl, const RsBuffers& b, uint64_t n, void* temp, 
         a.xcd_band = (scanned && g_opt_radix_xcd_band != 0) ? 1 : 0;
         a.counts = t.counts; a.sums = t.sums + (size_t)p * tree.sum_rows * pl.radix;
         a.tree = ta;
+        a.band_totals = nullptr; a.bands = 0;
         a.wide = pl.depth ? t.wide : nullptr;
         a.cond = pl.depth ? (p == 2 ? 1 : (p == 3 ? 2 : 0)) : 0;
         a.last = (!pl.depth && p == pl.npasses - 1) ? 1 : 0;
@@ -995,6 +1131,7 @@ static int rs_run(const RsPlan& pl, const RsBuffers& b, uint64_t n, void* temp, 
             h.keys = kin; h.n = (uint32_t)n; h.n_dev = n_dev; h.shift = a.shift; h.sub = pl.sub; h.tiles = tiles; h.tr = ta;
             h.counts = t.counts; h.sums = const_cast<uint32_t*>(a.sums);
             h.wide = t.wide; h.detect = (pl.depth && p == 0) ? 1 : 0; h.only_if_wide = a.cond == 2 ? 1 : 0;
+            h.band_totals = nullptr; h.bands = 0;
             if (items == RS_ITEMS_WIDE) {
                 if (pl.db[p] == 9) rs_launch_tile_hist<RS_ITEMS_WIDE, 9>(h, s); else rs_launch_tile_hist<RS_ITEMS_WIDE, 8>(h, s);
             } else {
@@ -1029,6 +1166,87 @@ int radix_sort_pairs(uint32_t* ka, uint32_t* va, uint32_t* kb, uint32_t* vb, uin
     b.ka = ka; b.va = va; b.va_is_index = false; b.pa = nullptr; b.kb = kb; b.vb = vb; b.pb = nullptr; b.kfinal = nullptr; b.vfinal = nullptr;
     b.aux_in = aux_in; b.aux_out = aux_out; b.aux_skip_ones = aux_empty_for_ones;
     return rs_run(pl, b, n, temp, s, n_dev, temp_zeroed, ext_hist, exclusive, key_shift);
+}
+
+// ---- banded tile sort (binning.hip, tile_sort_bands()): the pairs arrive grouped by band of 256 tiles -- band b's
+// band_totals[b] pairs (a device table: the host never learns the sizes) behind those of the bands before it -- so the 8 key
+// bits from key_shift up order each band completely: ONE counted-tiles pass, run as <= 32 independent sorts in one
+// rs_tile_hist + one rs_pass launch.  Band b has ceil(n_b / tile) sort tiles of its own, only the last one partial; the grids
+// are sized for the capacity (+ one partial tile per band), workgroups past the live tiles return at once.  Input (ka, va),
+// output (kb, vb): the same positions a sort of all n pairs by band and key fills -- no padding anywhere.  It is the final
+// pass: it opens and closes `ranges` and keeps the keys.
+struct RsBandedTemp {
+    RsTemp t;
+    RsTree tree;               // off[] / sum_rows with the bands' slack rows (rs_band_row)
+    uint32_t tmax;             // dense tile ids
+    uint32_t rows1;            // rows of level 1, slack included
+    int items;
+};
+static RsBandedTemp rs_carve_banded(void* temp, uint64_t n, int bands) {
+    RsBandedTemp bt;
+    bt.items = rs_tile_items(n, true);
+    const uint64_t tile = (uint64_t)RS_THREADS * bt.items;
+    bt.tmax = (uint32_t)((n + tile - 1) / tile) + (uint32_t)bands;        // (every band may end in a partial tile)
+    bt.tree = rs_tree(bt.tmax);
+    bt.tree.sum_rows = 0;
+    for (int l = 1; l < bt.tree.levels; ++l) {
+        bt.tree.off[l] = bt.tree.sum_rows;
+        bt.tree.sum_rows += (bt.tmax >> (RS_FAN_LOG * l)) + (uint32_t)bands + 2;
+    }
+    bt.rows1 = (bt.tmax >> RS_FAN_LOG) + (uint32_t)bands + 2;
+    RsTemp& t = bt.t;
+    char* q = rs_carve_header(temp, 256, t);    // (the plain plan's radix: the tile sort's error words stay where they were)
+    char* p = (char*)t.hist;
+    t.status = nullptr;
+    t.sums = (uint32_t*)q;
+    const size_t sums_bytes = (size_t)bt.tree.sum_rows * 256 * sizeof(uint32_t);
+    t.counts = (uint32_t*)(q + sums_bytes);
+    t.zero_bytes = (size_t)(q - p) + sums_bytes;
+    t.bytes = t.zero_bytes + (size_t)bt.tmax * 256 * sizeof(uint32_t);
+    return bt;
+}
+size_t radix_banded_temp_bytes(uint64_t n, int bands) { return rs_carve_banded(nullptr, n ? n : 1, bands).t.bytes + 512; }
+void radix_banded_zero_region(void* temp, uint64_t n, int bands, uint32_t** ptr, size_t* words) {
+    const RsBandedTemp bt = rs_carve_banded(temp, n ? n : 1, bands);
+    *ptr = bt.t.hist;
+    *words = bt.t.zero_bytes / 4;
+}
+int radix_sort_banded(const uint32_t* ka, const uint32_t* va, uint32_t* kb, uint32_t* vb, uint64_t n, int key_shift, void* temp,
+                      hipStream_t s, const uint32_t* n_dev, const uint32_t* band_totals, int bands, uint2* ranges) {
+    if (n == 0) return 0;
+    if (n >= (1ull << 32)) { set_error("radix sort: more than 2^32-1 pairs"); return 1; }
+    if (bands < 1 || bands > RS_MAX_BANDS) { set_error("radix sort: 1..%d bands", RS_MAX_BANDS); return 1; }
+    const RsBandedTemp bt = rs_carve_banded(temp, n, bands);
+    RsTreeArgs ta;
+    ta.levels = bt.tree.levels;
+    for (int l = 0; l < RS_MAX_LEVELS; ++l) ta.off[l] = l < bt.tree.levels ? bt.tree.off[l] : 0u;
+    ta.top_rows = 0;                               // (per band: the kernels form it)
+    RsTileHistArgs h;
+    h.keys = ka; h.n = (uint32_t)n; h.n_dev = n_dev; h.shift = key_shift; h.sub = 0u; h.tiles = bt.tmax; h.tr = ta;
+    h.counts = bt.t.counts; h.sums = bt.t.sums; h.wide = nullptr; h.detect = 0; h.only_if_wide = 0;
+    h.band_totals = band_totals; h.bands = bands;
+    RsPassArgs a;
+    a.kin = ka; a.vin = va; a.pin = nullptr; a.kout = kb; a.vout = vb; a.pout = nullptr; a.vfinal = vb; a.kfinal = kb;
+    a.aux_in = nullptr; a.aux_out = nullptr; a.aux_skip_ones = 0;
+    a.n = (uint32_t)n; a.n_dev = n_dev; a.shift = key_shift; a.sub = 0u;
+    a.hist = nullptr; a.status = nullptr; a.tiles = bt.tmax; a.ticket = nullptr; a.error = bt.t.error; a.pass = 0;
+    a.xcd_band = g_opt_radix_xcd_band != 0 ? 1 : 0;
+    a.last = 1; a.range_shift = key_shift; a.cond = 0; a.wide = nullptr; a.ranges = ranges;
+    a.counts = bt.t.counts; a.sums = bt.t.sums; a.tree = ta;
+    a.band_totals = band_totals; a.bands = bands;
+    const bool four = bt.tmax >= 1024u;            // (rs_launch_tile_hist's rule)
+    const dim3 hgrid(four ? bt.rows1 : bt.tmax), hblock(four ? RS_THREADS * 4 : RS_THREADS);
+    if (bt.items == RS_ITEMS_WIDE) {
+        if (four) hipLaunchKernelGGL((rs_tile_hist_banded_kernel<RS_ITEMS_WIDE, 4>), hgrid, hblock, 0, s, h);
+        else hipLaunchKernelGGL((rs_tile_hist_banded_kernel<RS_ITEMS_WIDE, 1>), hgrid, hblock, 0, s, h);
+        hipLaunchKernelGGL((rs_pass_banded_kernel<RS_ITEMS_WIDE>), dim3(bt.tmax), dim3(RS_THREADS), 0, s, a);
+    } else {
+        if (four) hipLaunchKernelGGL((rs_tile_hist_banded_kernel<RS_ITEMS, 4>), hgrid, hblock, 0, s, h);
+        else hipLaunchKernelGGL((rs_tile_hist_banded_kernel<RS_ITEMS, 1>), hgrid, hblock, 0, s, h);
+        hipLaunchKernelGGL((rs_pass_banded_kernel<RS_ITEMS>), dim3(bt.tmax), dim3(RS_THREADS), 0, s, a);
+    }
+    MGS_HIP(hipGetLastError());
+    return 0;
 }
 
 // The depth sort of the forward (see the header): keys[P] = float bits of the depths (all ones: culled), destroyed;
