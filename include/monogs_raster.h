@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define MGS_ABI_VERSION 27
+#define MGS_ABI_VERSION 28
 #define MGS_TILE 16 /* tile edge in pixels; ranges are per 16x16 tile */
 
 /* GaussianRasterizationSettings, minus `prefiltered` / `debug` which are call flags
@@ -73,6 +73,14 @@ typedef struct mgs_camera {
  * its ids by an atomic ticket, so a workgroup only ever waits for workgroups that have already started: forward progress does not
  * depend on where, or in which order, the hardware places workgroups of competing grids. */
 #define MGS_FLAG_EXCLUSIVE_DEVICE 1
+/* MGS_FLAG_INTRINSICS_GRAD (ABI v28): mgs_backward also sums dL/d(fx, fy, cx, cy), the gradient with respect to the pinhole
+ * intrinsics in pixels, with projmatrix_raw depending on them as P00 = 2 fx / W, P11 = 2 fy / H, P02 = (2 cx - W) / W,
+ * P12 = (2 cy - H) / H and tanfovx = W / (2 fx), tanfovy = H / (2 fy).  Culling, radius, tile rectangle and the 1.3 tanfov
+ * clamp test are constants, as they are for the pose gradient.  dL_dtau is then TEN floats (rho, theta, dfx, dfy, dcx, dcy)
+ * and must not be NULL.  The four sums take the path of the pose gradient -- floats 6..9 of the same 16-float lines, the same
+ * float atomics across workgroups, so the same reproducibility: deterministic up to the order of those adds.  The forward
+ * entry points ignore the bit. */
+#define MGS_FLAG_INTRINSICS_GRAD 2
 
 /* Per-stage device time in milliseconds, measured with HIP events on `stream`.
  * Passing a non-NULL mgs_timing makes the call synchronise `stream` before returning. */
@@ -109,7 +117,8 @@ size_t mgs_geometry_bytes(int32_t P);
 size_t mgs_image_bytes(int32_t width, int32_t height);
 size_t mgs_binning_bytes(uint64_t num_rendered, int32_t width, int32_t height);
 size_t mgs_backward_bytes(int32_t P);
-/* The six floats inside a backward scratch that a PREPARED backward (below) accumulates dL/dtau into. */
+/* The floats inside a backward scratch that a PREPARED backward (below) accumulates dL/dtau into: a 64-byte line of which the
+ * first six are used -- the first ten with MGS_FLAG_INTRINSICS_GRAD.  The preparing forward clears the whole line. */
 float* mgs_backward_tau(void* backward_scratch, int32_t P);
 /* TEST USE ONLY, pure: byte offset (from the 256-byte-aligned base the carving uses) and length of a named
  * sub-buffer; non-zero with mgs_last_error() set for an unknown name.  This export is the statement of the scratch layout:
@@ -242,7 +251,8 @@ int mgs_forward_capacity(const mgs_camera* cam, int32_t P, const float* means3D,
 
 /* Backward.  Consumes dL/dcolor[3,H,W] and dL/ddepth[1,H,W] (dL/dopacity is ignored, as upstream) and
  * the scratch of the matching forward.  Any output pointer may be NULL (that gradient is then not
- * stored); dL_dtau is [6] = (rho, theta), already summed over Gaussians.
+ * stored); dL_dtau is [6] = (rho, theta), already summed over Gaussians -- with MGS_FLAG_INTRINSICS_GRAD in cam->flags it is
+ * [10] = (rho, theta, dfx, dfy, dcx, dcy) and must not be NULL (return 1 with a message before any launch).
  * scratch_prepared = 1: `backward_scratch` was handed to the matching mgs_forward_preprocess as prepare_backward and has
  * not been used by a backward since; dL_dtau must then be NULL or mgs_backward_tau(backward_scratch, P).
  * `out_color` [3,H,W] and `out_depth` [1,H,W] are the images the matching forward wrote, unchanged; with them the blend
@@ -263,7 +273,7 @@ int mgs_backward(const mgs_camera* cam, int32_t P, uint64_t num_rendered,
                  float* dL_dsh,       /* [P,M,3] (shs) */
                  float* dL_dscales,   /* [P,3] */
                  float* dL_drotations,/* [P,4] */
-                 float* dL_dtau,      /* [6]   */
+                 float* dL_dtau,      /* [6], or [10] with MGS_FLAG_INTRINSICS_GRAD */
                  void* backward_scratch, int32_t scratch_prepared, mgs_timing* timing, void* stream);
 
 /* Diagnostic: MGS_VALU_CEILING_BLOCKS x 256 threads (8 waves per SIMD on all 256 compute units) run `iters` trips of 8

@@ -11,7 +11,9 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MGS_LIB_PATH") or os.path.join(_HERE, "lib", "libmonogs_raster.so")   # (override: kernel experiments)
-ABI_VERSION = 27
+ABI_VERSION = 28
+FLAG_EXCLUSIVE_DEVICE = 1          # MGS_FLAG_* bits of mgs_camera.flags (include/monogs_raster.h)
+FLAG_INTRINSICS_GRAD = 2
 
 c_float_p = C.c_void_p   # device pointers travel as integers (tensor.data_ptr())
 

@@ -38,7 +38,8 @@ def fused_camera_matrices(R: torch.Tensor, t: torch.Tensor, projmatrix_raw: torc
     """(viewmatrix, projmatrix, campos) -- the three transposed camera tensors of GaussianRasterizationSettings --
     from device tensors R[3,3], t[3] (world->camera) and the transposed projection, in one launch
     (``mgs_camera_setup``).  Same values as ``world2view(R, t).T``, ``viewmatrix @ projmatrix_raw`` and
-    ``viewmatrix.inverse()[3, :3]``; no autograd (the rasteriser gives the camera tensors no gradient).
+    ``viewmatrix.inverse()[3, :3]``; no autograd (the pose and the intrinsics take their gradients through the rasteriser's
+    ``theta`` / ``rho`` / ``intr`` holders, not through these tensors).
     ``out``: three existing tensors to write into (a loop whose pose step keeps them current -- ``PoseAdam.step_and_retract(camera=...)`` --
     computes them once per frame, not once per render)."""
     from . import _lib

@@ -372,8 +372,12 @@ int mgs_backward(const mgs_camera* cam, int32_t P, uint64_t R, const float* mean
     if (P < 0) { set_error("P must be >= 0"); return 1; }
     if (check_map_size(P)) return 1;
     hipStream_t s = (hipStream_t)stream;
+    // MGS_FLAG_INTRINSICS_GRAD: dL_dtau is ten floats, (rho, theta, dfx, dfy, dcx, dcy)
+    const bool intr = (cam->flags & MGS_FLAG_INTRINSICS_GRAD) != 0;
+    if (intr && !dL_dtau) { set_error("MGS_FLAG_INTRINSICS_GRAD needs dL_dtau (ten floats)"); return 1; }
+    const size_t tau_bytes = (intr ? 10 : 6) * sizeof(float);
     if (P == 0) {
-        if (dL_dtau) MGS_HIP(zero_fill(dL_dtau, 6 * sizeof(float), s));
+        if (dL_dtau) MGS_HIP(zero_fill(dL_dtau, tau_bytes, s));
         return 0;
     }
     if (!means3D || !opacities || !radii || !geometry || !image || !dL_dcolor || !dL_ddepth || !backward_scratch) {
@@ -389,14 +393,14 @@ int mgs_backward(const mgs_camera* cam, int32_t P, uint64_t R, const float* mean
     // (the pose-gradient slots sit right behind the accumulator: one clear covers both)
     float* tau_part = (dL_dtau && (P + 255) / 256 > TAU_DIRECT_MAX_BLOCKS) ? bw.tau_part : nullptr;
     if (scratch_prepared) {
-        // the matching forward cleared the lines of the visible Gaussians, the slots and the six floats of dL/dtau
+        // the matching forward cleared the lines of the visible Gaussians, the slots and the whole 16-float line of dL/dtau
         if (dL_dtau && dL_dtau != bw.tau) {
             set_error("scratch_prepared: dL_dtau must be mgs_backward_tau(backward_scratch, P)");
             return 1;
         }
     } else {
         MGS_HIP(zero_fill2(grad_acc, (size_t)P * GRAD_FLOATS * sizeof(float) + (tau_part ? (size_t)TAU_SLOTS * 16 * sizeof(float) : 0),
-                           dL_dtau, 6 * sizeof(float), s));
+                           dL_dtau, tau_bytes, s));
     }
     tm.mark();
     if (R > 0) {

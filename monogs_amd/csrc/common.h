@@ -281,7 +281,8 @@ constexpr int TAU_SLOTS = 256;              // one 64-byte line each
 struct BackwardState {
     float* grad_acc;     // [P][16] gradient lines
     float* tau_part;     // [TAU_SLOTS][16] pose-gradient slots
-    float* tau;          // [16] dL/dtau of a prepared backward (six floats used)
+    float* tau;          // [16] dL/dtau of a prepared backward: floats 0..5 (rho, theta); 6..9 (dfx, dfy, dcx, dcy) with
+                         //      MGS_FLAG_INTRINSICS_GRAD; the same lanes of every tau_part line
     static constexpr size_t ALIGN = 64;
     static size_t bytes(int P);
     static BackwardState carve(void* base, int P);

@@ -486,10 +486,15 @@ struct BwdArgs {
 
 // SH = false: colours are precomputed (MonoGS's path) -- the spherical-harmonics backward is compiled out,
 // which takes the kernel from 168 to far fewer VGPRs (occupancy) on the path that matters.
-template <bool SH, bool COV>
+// INTR = true (MGS_FLAG_INTRINSICS_GRAD): the four sums dL/d(fx, fy, cx, cy) ride beside the pose gradient as floats 6..9 of the
+// same 16-float lines, through the same reduction.  A variant of its own, so that the default path keeps its registers.
+template <bool SH, bool COV, bool INTR = false>
 __global__ void __launch_bounds__(256) geom_backward_kernel(BwdArgs a) {
     const int idx = blockIdx.x * 256 + threadIdx.x;        // (launched with 256 threads; blockDim would be a packet fetch)
-    float tau[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    constexpr int NT = INTR ? 10 : 6;                      // floats of the tau line this variant sums
+    float tau[NT];
+#pragma unroll
+    for (int k = 0; k < NT; ++k) tau[k] = 0.f;
     const bool in = idx < a.P;
     const size_t ci = in ? (size_t)idx : 0;                // clamped index: the lanes past P load element 0 and ignore it
     // ---- every input is requested up front -- camera block (scalar loads), radius, mean, covariance or scale +
@@ -621,6 +626,15 @@ __global__ void __launch_bounds__(256) geom_backward_kernel(BwdArgs a) {
                       dph[3] * c.PR[4 * j + 3];
         // ---- depth = p_c.z
         gpc[2] += ga[G_DDEPTH];
+        if constexpr (INTR) {
+            // ---- intrinsics ("Intrinsics gradient"): P00 = 2 fx / W and P02 = (2 cx - W) / W move the
+            //      pixel mean, J00 = fx / tz and J02 = -fx tx / tz^2 the covariance.  A clamped tx is +-1.3 (W / 2 fx) tz, so
+            //      fx tx -- and with it J02 -- does not depend on fx; the clamp decision itself is a constant.
+            tau[6] += (gpx * pv[0] * p_w + dJ00 * itz) - (p.clamp_x ? 0.f : dJ02 * p.tx * itz2);
+            tau[7] += (gpy * pv[1] * p_w + dJ11 * itz) - (p.clamp_y ? 0.f : dJ12 * p.ty * itz2);
+            tau[8] += gpx * pv[2] * p_w;
+            tau[9] += gpy * pv[2] * p_w;
+        }
 
         // ---- colour
         float gmean_w[3] = {0.f, 0.f, 0.f};   // direct world-space contributions (SH view direction)
@@ -778,15 +792,15 @@ __global__ void __launch_bounds__(256) geom_backward_kernel(BwdArgs a) {
         if (!a.iso) store3(a.g.dL_dscales, o_sc[0], o_sc[1], o_sc[2]);
     }
     if (a.g.dL_dtau) {
-        __shared__ float part[4][6];
+        __shared__ float part[4][NT];
         const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #pragma unroll
-        for (int k = 0; k < 6; ++k) {
+        for (int k = 0; k < NT; ++k) {
             const float v = wave_sum(tau[k]);
             if (lane == 0) part[wv][k] = v;
         }
         __syncthreads();
-        if (threadIdx.x < 6) {
+        if (threadIdx.x < NT) {
             const float v = (part[0][threadIdx.x] + part[1][threadIdx.x]) + (part[2][threadIdx.x] + part[3][threadIdx.x]);
             // Thousands of workgroups adding into the SAME 24 bytes serialise at the memory-side atomic unit (at C5 the
             // 7 813 x 6 same-address adds were 45 % of this kernel: 0.116 vs 0.065 ms without them).  Large launches
@@ -800,19 +814,27 @@ __global__ void __launch_bounds__(256) geom_backward_kernel(BwdArgs a) {
 }
 
 // dL_dtau[k] = sum over the slots (one block; fixed order, so the only non-determinism left is inside a slot)
-__global__ void __launch_bounds__(256) tau_finalize_kernel(const float* __restrict__ tau_part, float* __restrict__ dL_dtau) {
-    __shared__ float part[4][6];
+template <int NT>
+__device__ __forceinline__ void tau_finalize(const float* __restrict__ tau_part, float* __restrict__ dL_dtau) {
+    __shared__ float part[4][NT];
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    float v[6];
+    float v[NT];
 #pragma unroll
-    for (int k = 0; k < 6; ++k) v[k] = t < TAU_SLOTS ? tau_part[(size_t)t * 16 + k] : 0.f;
+    for (int k = 0; k < NT; ++k) v[k] = t < TAU_SLOTS ? tau_part[(size_t)t * 16 + k] : 0.f;
 #pragma unroll
-    for (int k = 0; k < 6; ++k) {
+    for (int k = 0; k < NT; ++k) {
         const float r = wave_sum(v[k]);
         if (lane == 0) part[wv][k] = r;
     }
     __syncthreads();
-    if (t < 6) dL_dtau[t] = (part[0][t] + part[1][t]) + (part[2][t] + part[3][t]);
+    if (t < NT) dL_dtau[t] = (part[0][t] + part[1][t]) + (part[2][t] + part[3][t]);
+}
+__global__ void __launch_bounds__(256) tau_finalize_kernel(const float* __restrict__ tau_part, float* __restrict__ dL_dtau) {
+    tau_finalize<6>(tau_part, dL_dtau);
+}
+// the ten columns of the intrinsics variant: (rho, theta, dfx, dfy, dcx, dcy)
+__global__ void __launch_bounds__(256) tau_finalize_intr_kernel(const float* __restrict__ tau_part, float* __restrict__ dL_dtau) {
+    tau_finalize<10>(tau_part, dL_dtau);
 }
 
 int launch_geom_backward(const mgs_camera& cam, int P, const GeometryState& g, const GeomBackwardArgs& ga,
@@ -832,11 +854,22 @@ int launch_geom_backward(const mgs_camera& cam, int P, const GeometryState& g, c
     a.drot_aligned16 = ga.dL_drotations && ((size_t)ga.dL_drotations % 16 == 0);
     const dim3 grid((P + 255) / 256), block(256);
     const bool cov = ga.cov3D_precomp != nullptr;
-    if (ga.colors_precomp && cov) hipLaunchKernelGGL((geom_backward_kernel<false, true>), grid, block, 0, s, a);
-    else if (ga.colors_precomp) hipLaunchKernelGGL((geom_backward_kernel<false, false>), grid, block, 0, s, a);
-    else if (cov) hipLaunchKernelGGL((geom_backward_kernel<true, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((geom_backward_kernel<true, false>), grid, block, 0, s, a);
-    if (ga.tau_part && ga.dL_dtau) hipLaunchKernelGGL(tau_finalize_kernel, dim3(1), dim3(256), 0, s, ga.tau_part, ga.dL_dtau);
+    // MGS_FLAG_INTRINSICS_GRAD only selects the instantiation (api.hip has checked that dL_dtau holds ten floats)
+    const bool intr = (cam.flags & MGS_FLAG_INTRINSICS_GRAD) != 0 && ga.dL_dtau != nullptr;
+#define MGS_GEOM_BWD(SH, COV)                                                                                      \
+    do {                                                                                                           \
+        if (intr) hipLaunchKernelGGL((geom_backward_kernel<SH, COV, true>), grid, block, 0, s, a);                 \
+        else hipLaunchKernelGGL((geom_backward_kernel<SH, COV>), grid, block, 0, s, a);                            \
+    } while (0)
+    if (ga.colors_precomp && cov) MGS_GEOM_BWD(false, true);
+    else if (ga.colors_precomp) MGS_GEOM_BWD(false, false);
+    else if (cov) MGS_GEOM_BWD(true, true);
+    else MGS_GEOM_BWD(true, false);
+#undef MGS_GEOM_BWD
+    if (ga.tau_part && ga.dL_dtau) {
+        if (intr) hipLaunchKernelGGL(tau_finalize_intr_kernel, dim3(1), dim3(256), 0, s, ga.tau_part, ga.dL_dtau);
+        else hipLaunchKernelGGL(tau_finalize_kernel, dim3(1), dim3(256), 0, s, ga.tau_part, ga.dL_dtau);
+    }
     MGS_HIP(hipGetLastError());
     return 0;
 }

@@ -12,13 +12,28 @@ from . import camera as cam
 
 
 class Intrinsics:
-    def __init__(self, k: dict, device):
-        self.k, self.device = dict(k), device
+    """``learnable=True``: the object owns ``delta``, a zero ``nn.Parameter`` of four floats that ``render()`` hands to the rasteriser
+    as ``intr`` -- its ``.grad`` receives dL/d(fx, fy, cx, cy) -- and ``set`` moves the intrinsics (``calibration.IntrinsicsAdam``)."""
+
+    def __init__(self, k: dict, device, learnable: bool = False):
+        self.device = device
         self.height, self.width = k["H"], k["W"]
+        self._build(dict(k))
+        if learnable:
+            self.delta = torch.nn.Parameter(torch.zeros(4, dtype=torch.float32, device=device))
+
+    def _build(self, k: dict):
+        self.k = k
         self.fx, self.fy, self.cx, self.cy = k["fx"], k["fy"], k["cx"], k["cy"]
         m = cam.camera_matrices(torch.eye(3), torch.zeros(3), k["fx"], k["fy"], k["cx"], k["cy"], k["W"], k["H"])
-        self.projection_matrix = m.projmatrix_raw.to(device)        # transposed, as the reference's property
+        self.projection_matrix = m.projmatrix_raw.to(self.device)   # transposed, as the reference's property
         self.FoVx, self.FoVy = 2 * math.atan(m.tanfovx), 2 * math.atan(m.tanfovy)
+
+    def set(self, fx, fy, cx, cy):
+        """New pinhole numbers: ``fx, fy, cx, cy``, ``k``, ``FoVx / FoVy`` and ``projection_matrix`` are rebuilt exactly as
+        ``Intrinsics(new_k)`` builds them.  The matrix is a NEW tensor object, so every viewpoint's ``cached_camera_tensors``
+        entry (keyed on the object) misses at its next render."""
+        self._build(dict(self.k, fx=float(fx), fy=float(fy), cx=float(cx), cy=float(cy)))
 
 
 def scharr_grad_mask(rgb: torch.Tensor, edge_threshold: float = 1.1, eps: float = 0.01) -> torch.Tensor:

@@ -30,7 +30,8 @@ def rasterize(intr, bg, cam3, leaves, holder, theta, rho):
     in the order of ``MapStep.leaves``; ``holder``: the caller's zeros whose ``.grad`` receives dL/dmean2D; ``cam3``: the camera."""
     xyz, feat, opac, scales3, rot = leaves
     color, radii, depth, _, n_touched = GaussianRasterizer(raster_settings(intr, bg, *cam3))(
-        means3D=xyz, means2D=holder, opacities=opac, colors_precomp=feat, scales=scales3, rotations=rot, theta=theta, rho=rho)
+        means3D=xyz, means2D=holder, opacities=opac, colors_precomp=feat, scales=scales3, rotations=rot, theta=theta, rho=rho,
+        intr=getattr(intr, "delta", None))
     return color, radii, depth, n_touched
 
 

@@ -218,7 +218,7 @@ def _stream():
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                theta, rho, raster_settings):
+                theta, rho, raster_settings, intr=None):
         lib = _lib.load()
         rs = raster_settings
         means3D = _f32(means3D.detach(), "means3D")
@@ -326,6 +326,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.scale_dim = scale_dim
         ctx.has = (sh_ is not None, col_ is not None, sc_ is not None, cov_ is not None,
                    theta is not None, rho is not None)
+        ctx.has_intr = intr is not None
         dummy = torch.empty(0, device=dev)
         ctx.save_for_backward(means3D, sh_ if sh_ is not None else dummy, col_ if col_ is not None else dummy,
                               opac_, sc_ if sc_ is not None else dummy, rot_ if rot_ is not None else dummy,
@@ -346,7 +347,8 @@ class _RasterizeGaussians(torch.autograd.Function):
         P = means3D.shape[0]
         dev = means3D.device
         H, W = int(rs.image_height), int(rs.image_width)
-        need = ctx.needs_input_grad   # means3D, means2D, sh, colors, opacities, scales, rotations, cov3D, theta, rho
+        need = ctx.needs_input_grad   # means3D, means2D, sh, colors, opacities, scales, rotations, cov3D, theta, rho, -, intr
+        want_intr = ctx.has_intr and len(need) > 11 and need[11]
 
         with _device_guard(dev):
             cam = ctx.cam
@@ -368,15 +370,19 @@ class _RasterizeGaussians(torch.autograd.Function):
                 views.append(flat[o:o + P * w].view(P, w) if w else None)
                 o += P * w
             d_means3D, d_col, d_opac, d_scales, d_rot = views
-            want_tau = (need[8] and has_theta) or (need[9] and has_rho)
+            want_tau = (need[8] and has_theta) or (need[9] and has_rho) or want_intr
+            n_tau = 10 if want_intr else 6      # MGS_FLAG_INTRINSICS_GRAD: (rho, theta, dfx, dfy, dcx, dcy)
+            if want_intr:                       # (a copy: the forward's camera block stays as the forward scratch handle saw it)
+                cam = _lib.MgsCamera.from_buffer_copy(cam)
+                cam.flags |= _lib.FLAG_INTRINSICS_GRAD
             prepared = ctx.scratch is not None and not ctx.scratch_used      # (a second backward through the same forward
             ctx.scratch_used = True                                          #  clears a fresh scratch with a launch)
             scratch = ctx.scratch if prepared else torch.empty(lib.mgs_backward_bytes(P), dtype=torch.uint8, device=dev)
             if want_tau and prepared:       # the six floats live inside the prepared scratch (the forward cleared them)
                 off = int(lib.mgs_backward_tau(scratch.data_ptr(), P)) - scratch.data_ptr()
-                d_tau = scratch[off:off + 24].view(torch.float32)
+                d_tau = scratch[off:off + 4 * n_tau].view(torch.float32)
             else:
-                d_tau = torch.empty(6, **f32) if want_tau else None
+                d_tau = torch.empty(n_tau, **f32) if want_tau else None
             timing = _lib.MgsTiming() if _timing_sink is not None else None
             tref = C.byref(timing) if timing is not None else None
             out5 = ctx.out_ref() if ctx.out_ref is not None else None
@@ -398,9 +404,12 @@ class _RasterizeGaussians(torch.autograd.Function):
                 d.update(kind="backward", num_rendered=ctx.num_rendered, P=P)
                 _timing_sink.append(d)
         # (views of the 6-float result: autograd takes them as .grad without a copy kernel)
-        d_theta = d_tau[3:] if (d_tau is not None and need[8] and has_theta) else None
+        d_theta = d_tau[3:6] if (d_tau is not None and need[8] and has_theta) else None
         d_rho = d_tau[:3] if (d_tau is not None and need[9] and has_rho) else None
-        return (d_means3D, d_means2D, d_sh, d_col, d_opac, d_scales, d_rot, d_cov, d_theta, d_rho, None)
+        if not ctx.has_intr:
+            return (d_means3D, d_means2D, d_sh, d_col, d_opac, d_scales, d_rot, d_cov, d_theta, d_rho, None)
+        return (d_means3D, d_means2D, d_sh, d_col, d_opac, d_scales, d_rot, d_cov, d_theta, d_rho, None,
+                d_tau[6:10] if want_intr else None)
 
 
 class ForwardScratch(NamedTuple):
@@ -474,9 +483,14 @@ def debug_blend_mask_stats(color: torch.Tensor) -> dict:
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        theta, rho, raster_settings):
+                        theta, rho, raster_settings, intr=None):
+    if intr is None:        # today's call, argument for argument
+        return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                                         cov3Ds_precomp, theta, rho, raster_settings)
+    if tuple(intr.shape) != (4,) or intr.dtype != torch.float32 or intr.device != means3D.device:
+        raise RuntimeError("intr must be a [4] float32 tensor (fx, fy, cx, cy) on the device of means3D")
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                     cov3Ds_precomp, theta, rho, raster_settings)
+                                     cov3Ds_precomp, theta, rho, raster_settings, intr)
 
 
 class GaussianRasterizer(nn.Module):
@@ -501,6 +515,21 @@ class GaussianRasterizer(nn.Module):
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                 cov3D_precomp=None, theta=None, rho=None):
+        # (the reference's signature, parameter for parameter -- tests/test_host_api.py holds the drop-in packages to it; the one
+        #  keyword the reference does not have, ``intr``, is taken by ``__call__`` below, which is how every caller calls the module)
+        return self._rasterize(means3D, means2D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp, theta, rho)
+
+    def __call__(self, *args, intr=None, **kwargs):
+        """``rasterizer(means3D=..., ..., theta=None, rho=None, intr=None)``: ``forward`` plus ``intr``.  ``theta``, ``rho`` and
+        ``intr`` are delta holders: their values are not read (they are zero at call time); they exist to receive ``.grad`` --
+        dL/dtheta, dL/drho and, for ``intr`` ([4] float32), dL/d(fx, fy, cx, cy) in pixels, evaluated at the intrinsics the raster
+        settings were built from (``MGS_FLAG_INTRINSICS_GRAD``).  Without ``intr`` this is ``nn.Module.__call__``."""
+        if intr is None:
+            return super().__call__(*args, **kwargs)
+        return self._rasterize(*args, intr=intr, **kwargs)
+
+    def _rasterize(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
+                   cov3D_precomp=None, theta=None, rho=None, intr=None):
         rs = self.raster_settings
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception("Please provide excatly one of either SHs or precomputed colors!")
@@ -508,4 +537,4 @@ class GaussianRasterizer(nn.Module):
                 ((scales is not None or rotations is not None) and cov3D_precomp is not None):
             raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                   cov3D_precomp, theta, rho, rs)
+                                   cov3D_precomp, theta, rho, rs, intr)

@@ -69,7 +69,8 @@ def render(viewpoint_camera, cam_intrinsics, means, rotations, scales, opacity, 
     rendered_image, radii, depth, opacity_img, n_touched = rasterizer(
         means3D=sel(means), means2D=sel(screenspace_points), shs=None, colors_precomp=sel(colors),
         opacities=sel(opacity), scales=sel(scales), rotations=sel(rotations), cov3D_precomp=None,
-        theta=viewpoint_camera.cam_rot_delta, rho=viewpoint_camera.cam_trans_delta)
+        theta=viewpoint_camera.cam_rot_delta, rho=viewpoint_camera.cam_trans_delta,
+        intr=getattr(cam_intrinsics, "delta", None))      # learnable intrinsics (frames.Intrinsics(learnable=True)); else None
 
     return {
         "render": rendered_image,
