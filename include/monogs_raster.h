@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define MGS_ABI_VERSION 28
+#define MGS_ABI_VERSION 29
 #define MGS_TILE 16 /* tile edge in pixels; ranges are per 16x16 tile */
 
 /* GaussianRasterizationSettings, minus `prefiltered` / `debug` which are call flags
@@ -361,6 +361,30 @@ int mgs_features_backward(const mgs_camera* cam, int32_t P, int32_t K, uint64_t 
                           const void* binning, const void* image, const float* dL_dout /* [K,H,W] */,
                           float* dL_dfeatures /* [P,K], cleared here */, void* stream);
 
+/* ---- Pose-tangent rendering (ABI v29) ---------------------------------------------------------------------
+ * The per-pixel Jacobian of the render with respect to the six pose tangents, tau = (rho_x, rho_y, rho_z, theta_x, theta_y,
+ * theta_z) in the order of mgs_backward's dL_dtau, of T_cw(tau) = exp(tau^) T_cw at tau = 0: a forward-mode pass through the
+ * lists and the per-pixel decisions a finished forward left in its scratch.
+ *
+ *     J[5 k + c, p] = d out_c[p] / d tau_k,   c = (R, G, B, depth, opacity),   J is [30, H, W] float32
+ *
+ * with the gradient conventions of mgs_backward: skip and termination decisions, radii and rectangles are constants, a
+ * view-space ratio clamped at 1.3 tanfov is a constant, the 0.99 cap of alpha is straight-through.  Hence, for any cotangent
+ * images (g_color, g_depth):  sum over p and c < 4 of g[c, p] J[5 k + c, p] = dL_dtau[k] of mgs_backward, to rounding.
+ * A pixel with an empty list is exactly 0 in all 30 planes.  Opacities and colours are constants: only a forward that took
+ * colors_precomp is supported (an SH colour depends on the camera position); after an `shs` forward (cam->sh_coeffs > 0) the
+ * call returns 1.  means3D, scales / rotations or cov3D_precomp and radii are the forward's (what mgs_backward takes).
+ * `tangent_scratch`: mgs_pose_tangent_bytes(P) bytes, written here (the per-Gaussian tangent records: 192 bytes each; the
+ * records of Gaussians with radii == 0 are neither written nor read).
+ * LIFETIME: as mgs_features_forward -- `geometry`, `binning`, `image` are the scratch of a finished mgs_forward_render /
+ * _capacity for the same cam, P and num_rendered; they are only READ, on either binning path, before or after mgs_backward.
+ * No host synchronisation, no state.  P == 0: J is cleared with one memset node, nothing else is read.  P > MGS_MAX_GAUSSIANS
+ * or a NULL required pointer returns 1 before any launch. */
+size_t mgs_pose_tangent_bytes(int32_t P);
+int mgs_pose_jacobian(const mgs_camera* cam, int32_t P, uint64_t num_rendered, const float* means3D, const float* scales,
+                      const float* rotations, const float* cov3D_precomp, const int32_t* radii, const void* geometry,
+                      const void* binning, const void* image, void* tangent_scratch, float* J /* [30,H,W] */, void* stream);
+
 /* ---- Label loss and confusion count of the object layer (ABI v21) ----------------------------------------
  * Softmax cross-entropy of a blended K-channel image against 8-bit ids, value + gradient to the image, for learning the
  * per-Gaussian object rows: feat is mgs_features_forward's `out` on the RAW rows (no background term), taken as logits, and
@@ -553,6 +577,40 @@ int mgs_pose_step(float* R, float* T, float* rot_delta, float* trans_delta, floa
  * step_counter [required], out, projmatrix_raw, viewmatrix, projmatrix, campos; NULL where optional); the scalars are shared. */
 int mgs_pose_step_batch(int32_t n, void* const* ptrs, float lr_rot, float lr_trans, float lr_exposure, float beta1,
                         float beta2, float eps, float converged_threshold, int32_t flags, void* stream);
+
+/* ---- Gauss-Newton tracking (ABI v29) ------------------------------------------------------------------------
+ * mgs_gn_normal_equations: the normal equations of the tracking loss's rows in the unknowns x = (rho, theta, a, b), from the
+ * planes J of mgs_pose_jacobian and the images mgs_loss_* takes in MGS_LOSS_TRACKING mode:
+ *
+ *     colour  r_c = e^a C_c + b - I_c   where mask grad_mask (O > 0.99)   d r / d x = (e^a J[5 k + c], e^a C_c, 1)   s = 0.5 / (3 H W)
+ *     depth   r_d = D - D_gt            where (D_gt > 0) (O > 0.99)        d r / d x = (J[5 k + 3], 0, 0)             s = 1 / N_d
+ *
+ *     H = sum s omega j j^T,   g = sum s omega r j,   E = sum s huber(r),   omega = 1 if |r| <= delta else delta / |r|
+ *
+ * omega is formed in float32 (delta_rgb for colour rows, delta_depth, in the depth's unit, for depth rows); every product and
+ * sum is carried in double.  The reference's factor mean(O) is dropped.  MGS_LOSS_RGB_ONLY drops the depth rows and their
+ * images (depth, gt_depth may be NULL).  exposure_a / exposure_b NULL (both): a = b = 0.  mask may be NULL (all ones).
+ * `system` [MGS_GN_SYSTEM_DOUBLES] device doubles: H[8][8] row-major (symmetric, full), g[8], E, N_rgb (pixels with colour
+ * rows), N_d.  N_d == 0 or an all-masked frame gives zeros, never NaN.  `scratch`: mgs_gn_scratch_bytes(width, height), 8-byte
+ * aligned.  Two launches, no atomics, partial sums added in a fixed order: bitwise reproducible.
+ *
+ * mgs_pose_gn_step: one wave solves (H + lam diag(H) + lam_abs I) x = -g by Cholesky in double -- with MGS_GN_FIX_EXPOSURE (or
+ * NULL exposure pointers) the 6 x 6 pose block --, scales the whole step so that |theta| <= max_rot and |rho| <= max_trans,
+ * retracts T_cw <- exp([rho; theta]^) T_cw exactly as mgs_pose_step does, adds x[6], x[7] to the exposure, and (optional, all
+ * four or none) refreshes the camera tensors bit-identically to mgs_camera_setup.
+ * out[4] = {converged (|tau| < converged_threshold), |tau|, E, status}; host_flag (optional, pinned) receives out[0].
+ * A non-positive or non-finite pivot: no update, status = 1, R, T, a, b bit-unchanged.  MGS_POSE_STICKY as for mgs_pose_step. */
+#define MGS_GN_SYSTEM_DOUBLES 75
+#define MGS_GN_FIX_EXPOSURE 2
+size_t mgs_gn_scratch_bytes(int32_t width, int32_t height);
+int mgs_gn_normal_equations(int32_t width, int32_t height, int32_t mode, const float* J /* [30,H,W] */, const float* render,
+                            const float* depth, const float* opacity, const float* gt_rgb, const float* gt_depth,
+                            const uint8_t* mask, const uint8_t* grad_mask, const float* exposure_a, const float* exposure_b,
+                            float delta_rgb, float delta_depth, void* scratch, double* system, void* stream);
+int mgs_pose_gn_step(float* R, float* T, float* exposure_a, float* exposure_b, const double* system, float lam, float lam_abs,
+                     float max_rot, float max_trans, float converged_threshold, float* out /* [4] */, int32_t flags,
+                     float* host_flag, const float* projmatrix_raw, float* viewmatrix, float* projmatrix, float* campos,
+                     void* stream);
 
 /* ---- Keyframe back-projection ------------------------------------------------
  * The per-point part of GaussianModel.create_viewpoint_pcd (/root/reference/gaussian_splatting/scene/gaussian_model.py:121-319)

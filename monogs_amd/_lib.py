@@ -11,7 +11,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MGS_LIB_PATH") or os.path.join(_HERE, "lib", "libmonogs_raster.so")   # (override: kernel experiments)
-ABI_VERSION = 28
+ABI_VERSION = 29
 FLAG_EXCLUSIVE_DEVICE = 1          # MGS_FLAG_* bits of mgs_camera.flags (include/monogs_raster.h)
 FLAG_INTRINSICS_GRAD = 2
 
@@ -189,6 +189,11 @@ SIGNATURES = {
     "mgs_object_motion_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "mgs_object_transform_forward": (C.c_int, [C.c_int32, C.c_int32] + [C.c_void_p] * 9),
     "mgs_object_transform_backward": (C.c_int, [C.c_int32, C.c_int32] + [C.c_void_p] * 12),
+    "mgs_pose_tangent_bytes": (C.c_size_t, [C.c_int32]),
+    "mgs_pose_jacobian": (C.c_int, [C.POINTER(MgsCamera), C.c_int32, C.c_uint64] + [C.c_void_p] * 11),
+    "mgs_gn_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "mgs_gn_normal_equations": (C.c_int, [C.c_int32] * 3 + [C.c_void_p] * 10 + [C.c_float] * 2 + [C.c_void_p] * 3),
+    "mgs_pose_gn_step": (C.c_int, [C.c_void_p] * 5 + [C.c_float] * 5 + [C.c_void_p, C.c_int32] + [C.c_void_p] * 6),
 }
 
 _lib = None

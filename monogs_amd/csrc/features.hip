@@ -278,3 +278,5 @@ int launch_features_backward(const mgs_camera& cam, int P, int K, const Geometry
 }
 
 }  // namespace mgs
+
+#include "pose_tangent.h"    // pose-tangent rendering: the forward-mode walk of the same lists (kernels, entry points)

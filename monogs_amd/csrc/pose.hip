@@ -69,6 +69,38 @@ __global__ void camera_setup_kernel(const float* __restrict__ R, const float* __
     camera_entry(R, T, proj_T, (int)threadIdx.x, view_T, full_T, campos);
 }
 
+// The retraction of every pose update of the library, stated once (pose_step_one, and gauss_newton.h's step):  T_cw <- exp(tau^) T_cw,
+// tau = [rho; theta]  (/root/reference/utils/pose_utils.py:25-93).  `th`, `rho`: float[3]; `R`, `T`: the pose, updated in place; declares
+// Rn[9], the new R, and tn = |tau|.  A macro, not a function: written in place the statements give pose_step_kernel the parent's
+// machine code instruction for instruction, as a helper they come out with another register assignment (tools/kernel_identity.py).
+#define MGS_SE3_RETRACT(th, rho, R, T)                                                                                  \
+    const float W[9] = {0.f, -th[2], th[1], th[2], 0.f, -th[0], -th[1], th[0], 0.f};                                    \
+    float W2[9];                                                                                                        \
+    mat3mul(W, W, W2);                                                                                                  \
+    const float angle = sqrtf(th[0] * th[0] + th[1] * th[1] + th[2] * th[2]);                                           \
+    float ca, cb, va, vb;   /* R = I + ca W + cb W2 ; V = I + va W + vb W2 */                                           \
+    if (angle < 1e-5f) {                                                                                                \
+        ca = 1.f; cb = 0.5f; va = 0.5f; vb = 1.f / 6.f;                                                                 \
+    } else {                                                                                                            \
+        const float s = sinf(angle), c = cosf(angle), a2 = angle * angle;                                               \
+        ca = s / angle; cb = (1.f - c) / a2; va = (1.f - c) / a2; vb = (angle - s) / (a2 * angle);                      \
+    }                                                                                                                   \
+    float dR[9], V[9];                                                                                                  \
+    for (int i = 0; i < 9; ++i) {                                                                                       \
+        const float eye = (i % 4 == 0) ? 1.f : 0.f;                                                                     \
+        dR[i] = eye + ca * W[i] + cb * W2[i];                                                                           \
+        V[i] = eye + va * W[i] + vb * W2[i];                                                                            \
+    }                                                                                                                   \
+    float dt[3];                                                                                                        \
+    for (int i = 0; i < 3; ++i) dt[i] = V[3 * i] * rho[0] + V[3 * i + 1] * rho[1] + V[3 * i + 2] * rho[2];              \
+    float Rn[9], Ro[9], To[3];                                                                                          \
+    for (int i = 0; i < 9; ++i) Ro[i] = (R)[i];                                                                         \
+    for (int i = 0; i < 3; ++i) To[i] = (T)[i];                                                                         \
+    mat3mul(dR, Ro, Rn);                                                                                                \
+    for (int i = 0; i < 9; ++i) (R)[i] = Rn[i];                                                                         \
+    for (int i = 0; i < 3; ++i) (T)[i] = dR[3 * i] * To[0] + dR[3 * i + 1] * To[1] + dR[3 * i + 2] * To[2] + dt[i];     \
+    const float tn = sqrtf(rho[0] * rho[0] + rho[1] * rho[1] + rho[2] * rho[2] + angle * angle)
+
 __device__ __forceinline__ void pose_step_one(const PoseStepArgs& a) {
     // Sticky convergence: the reference's tracker leaves its loop at the first converged update
     // (/root/reference/utils/slam_tracker.py:172-176).  With the loop replayed from a hipGraph the host learns of the
@@ -98,34 +130,9 @@ __device__ __forceinline__ void pose_step_one(const PoseStepArgs& a) {
     }
     if (a.exp_a) a.exp_a[0] = p[6];
     if (a.exp_b) a.exp_b[0] = p[7];
-    // ---- tau = [rho; theta];  T <- exp(tau^) T   (/root/reference/utils/pose_utils.py:25-93)
+    // ---- tau = [rho; theta];  T <- exp(tau^) T
     const float th[3] = {p[0], p[1], p[2]}, rho[3] = {p[3], p[4], p[5]};
-    const float W[9] = {0.f, -th[2], th[1], th[2], 0.f, -th[0], -th[1], th[0], 0.f};
-    float W2[9];
-    mat3mul(W, W, W2);
-    const float angle = sqrtf(th[0] * th[0] + th[1] * th[1] + th[2] * th[2]);
-    float ca, cb, va, vb;   // R = I + ca W + cb W2 ; V = I + va W + vb W2
-    if (angle < 1e-5f) {
-        ca = 1.f; cb = 0.5f; va = 0.5f; vb = 1.f / 6.f;
-    } else {
-        const float s = sinf(angle), c = cosf(angle), a2 = angle * angle;
-        ca = s / angle; cb = (1.f - c) / a2; va = (1.f - c) / a2; vb = (angle - s) / (a2 * angle);
-    }
-    float dR[9], V[9];
-    for (int i = 0; i < 9; ++i) {
-        const float eye = (i % 4 == 0) ? 1.f : 0.f;
-        dR[i] = eye + ca * W[i] + cb * W2[i];
-        V[i] = eye + va * W[i] + vb * W2[i];
-    }
-    float dt[3];
-    for (int i = 0; i < 3; ++i) dt[i] = V[3 * i] * rho[0] + V[3 * i + 1] * rho[1] + V[3 * i + 2] * rho[2];
-    float Rn[9], Ro[9], To[3];
-    for (int i = 0; i < 9; ++i) Ro[i] = a.R[i];
-    for (int i = 0; i < 3; ++i) To[i] = a.T[i];
-    mat3mul(dR, Ro, Rn);
-    for (int i = 0; i < 9; ++i) a.R[i] = Rn[i];
-    for (int i = 0; i < 3; ++i) a.T[i] = dR[3 * i] * To[0] + dR[3 * i + 1] * To[1] + dR[3 * i + 2] * To[2] + dt[i];
-    const float tn = sqrtf(rho[0] * rho[0] + rho[1] * rho[1] + rho[2] * rho[2] + angle * angle);
+    MGS_SE3_RETRACT(th, rho, a.R, a.T);
     a.out[0] = tn < a.converged_threshold ? 1.f : 0.f;
     a.out[1] = tn;
     if (a.host_flag) a.host_flag[0] = a.out[0];
@@ -226,3 +233,5 @@ extern "C" int mgs_pose_step_batch(int32_t n, void* const* ptrs, float lr_rot, f
     MGS_HIP(hipGetLastError());
     return 0;
 }
+
+#include "gauss_newton.h"    // Gauss-Newton tracking: normal equations of the tracking rows, the damped step (kernels, entry points)

@@ -108,3 +108,57 @@ class PoseAdam:
                 _lib.check(lib.mgs_pose_step_batch(len(grp), arr, o0.lrs[0], o0.lrs[1], o0.lrs[2], o0.betas[0], o0.betas[1],
                                                    o0.eps, float(converged_threshold), 1 if o0.sticky else 0, _stream()),
                            "mgs_pose_step_batch")
+
+
+class PoseGaussNewton:
+    """Damped Gauss-Newton pose step (``mgs_pose_gn_step``): solves ``(H + lam diag(H) + lam_abs I) x = -g`` for
+    ``x = (rho, theta, a, b)`` from the device system of ``pose_jacobian.normal_equations`` by Cholesky in double, scales the step
+    so that ``|theta| <= max_rot`` and ``|rho| <= max_trans``, retracts ``T_cw <- exp([rho; theta]^) T_cw`` with the device
+    function ``PoseAdam``'s step uses and adds ``x[6:8]`` to the exposure -- one single-wave launch, no host synchronisation
+    unless ``sync``.  ``fix_exposure``: the 6 x 6 pose block only.  ``sticky``: once converged, further steps are no-ops.
+    The reference has no counterpart (its tracker is Adam, /root/reference/utils/slam_tracker.py:113-176)."""
+    STICKY, FIX_EXPOSURE = 1, 2        # MGS_POSE_STICKY, MGS_GN_FIX_EXPOSURE
+
+    def __init__(self, viewpoint, lam=1e-3, lam_abs=0.0, max_rot=0.05, max_trans=0.05, fix_exposure=False, sticky=False):
+        self.vp = viewpoint
+        self.lam, self.lam_abs, self.max_rot, self.max_trans = float(lam), float(lam_abs), float(max_rot), float(max_trans)
+        self.flags = (self.STICKY if sticky else 0) | (self.FIX_EXPOSURE if fix_exposure else 0)
+        self.out = torch.zeros(4, device=viewpoint.cam_rot_delta.device)      # {converged, |tau|, E, status}
+        self._system = None
+
+    @torch.no_grad()
+    def reset(self):
+        self.out.zero_()
+
+    @torch.no_grad()
+    def step_and_retract(self, system, converged_threshold=1e-4, sync=True, host_flag=None, camera=None):
+        """``system``: what ``normal_equations`` returned.  Returns the convergence flag (bool) when ``sync`` else the device
+        tensor ``out[4] = {converged, |tau|, robust cost, status}``; status 1: a pivot of the factorisation was not positive and
+        finite, nothing moved.  ``host_flag`` and ``camera`` as for ``PoseAdam.step_and_retract``."""
+        lib = _lib.load()
+        vp = self.vp
+        if not vp.R.is_contiguous() or not vp.T.is_contiguous():
+            vp.R, vp.T = vp.R.contiguous(), vp.T.contiguous()
+        if camera is None:
+            c = getattr(vp, "_mgs_cam", None)
+            if c is not None and c[0] is vp.R and c[1] is vp.T:
+                camera = (c[2],) + tuple(c[3])
+        buf = getattr(system, "buf", system)
+        if buf.dtype != torch.float64 or buf.numel() < 75 or not buf.is_contiguous():
+            raise ValueError("system must be the 75 contiguous float64 values of normal_equations")
+        self._system = buf
+        with _device_guard(vp.R.device):
+            _lib.check(lib.mgs_pose_gn_step(vp.R.data_ptr(), vp.T.data_ptr(), vp.exposure_a.data_ptr(), vp.exposure_b.data_ptr(),
+                                            buf.data_ptr(), self.lam, self.lam_abs, self.max_rot, self.max_trans,
+                                            float(converged_threshold), self.out.data_ptr(), self.flags,
+                                            None if host_flag is None else host_flag.data_ptr(),
+                                            *((None,) * 4 if camera is None else tuple(t.data_ptr() for t in camera)), _stream()),
+                       "mgs_pose_gn_step")
+        return bool(self.out[0].item() > 0.5) if sync else self.out
+
+    def information(self) -> torch.Tensor:
+        """The 6 x 6 pose block (rho, theta) of the last step's ``H`` (float64, a copy): the information matrix of the tracked pose
+        under the robust weights; its inverse is the pose covariance up to the noise scale."""
+        if self._system is None:
+            raise RuntimeError("information(): no step has been taken yet")
+        return self._system[:64].view(8, 8)[:6, :6].clone()

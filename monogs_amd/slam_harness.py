@@ -22,6 +22,7 @@ from .map_step import render_map
 from .mapping import WindowMapper
 from .monocular import is_monocular, monocular_frames, pseudo_depth, valid_rgb
 from .sequences import make_room_sequence, make_sequence      # make_sequence: re-exported, bench.py imports it (and run_slam) from here
+from .gn_tracking import GaussNewtonGraph, track_gauss_newton
 from .tracking import TrackingGraph, track_eager
 
 
@@ -68,6 +69,8 @@ def _setup(c):
         raise ValueError('sensor must be "depth" or "monocular"')
     if c.kf_selection not in ("interval", "overlap"):
         raise ValueError('kf_selection must be "interval" or "overlap"')
+    if c.tracker not in ("adam", "gauss_newton"):
+        raise ValueError('tracker must be "adam" or "gauss_newton"')
     if c.viewer_dir is not None:
         from .viewer import MODES
         c.viewer_modes = tuple(c.viewer_modes)
@@ -146,21 +149,23 @@ def _map_window(s, iters, init=False):
     s.window_sizes.append(len(window))
 
 
-def _track_frame(s, vp, prev, max_iters, graph=True, exclusive=False, lookahead=1):
+def _track_frame(s, vp, prev, max_iters, graph=True, exclusive=False, lookahead=1, tracker="adam"):
     """Tracks ``vp`` from the pose of ``prev`` and clears the map's grads; of ``s`` it needs ``intr``, ``bg``, ``gmap``, ``tgraph`` and
     ``stats``.  ``graph``: one captured iteration per map version (``exclusive``: only a caller that owns the box may vouch for it),
-    the convergence flag read ``lookahead`` replays late, the capture accounted apart where ``stats`` has ``track_capture_s``."""
+    the convergence flag read ``lookahead`` replays late, the capture accounted apart where ``stats`` has ``track_capture_s``.
+    ``tracker``: "adam" (the reference's) or "gauss_newton" (``gn_tracking``), eager or captured alike."""
     stats = s.stats
+    gn = tracker == "gauss_newton"
     vp.update_RT(prev.R.clone(), prev.T.clone())     # the fused pose step updates R, T in place
     with _timed(stats, "track_s") as t0:
         if graph:
             if s.tgraph is None:                       # the map changed (or first frame): capture against the new map
-                s.tgraph = TrackingGraph(vp, s.intr, s.gmap, s.bg, exclusive=exclusive)
+                s.tgraph = (GaussNewtonGraph if gn else TrackingGraph)(vp, s.intr, s.gmap, s.bg, exclusive=exclusive)
                 if "track_capture_s" in stats:
                     stats["track_capture_s"] += _clock() - t0
             n_it = s.tgraph.track(vp, max_iters, lookahead=lookahead)
         else:
-            n_it = track_eager(vp, s.intr, s.gmap, s.bg, max_iters)
+            n_it = (track_gauss_newton if gn else track_eager)(vp, s.intr, s.gmap, s.bg, max_iters)
     stats["track_iters"] += n_it
     stats["tracked"] += 1
     for p in s.gmap.params():
@@ -384,6 +389,8 @@ def _report(s, extra):
         out.update(map=gmap, frame_list=frames, intr=s.intr)
     if c.viewer_dir is not None:         # (only then: tests/golden/run_slam_contract.json pins the keys of the default flags)
         out["viewer"] = dict(dir=str(c.viewer_dir), modes=list(c.viewer_modes), every=int(c.viewer_every), files=list(s.viewer_files))
+    if c.tracker != "adam":              # (the default tracker keeps exactly the keys it always had)
+        out["tracker"] = c.tracker
     if c.sensor == "monocular":          # (a depth run keeps exactly the keys it always had)
         from .evaluation import eval_ate
         out.update(sensor="monocular", ate_sim3=eval_ate(frames, align=True, correct_scale=True),
@@ -422,7 +429,7 @@ def run_slam(n_frames=12, intrinsics="fr3_office", tracking_itr_num=100, mapping
              kf_selection="interval", check_viewpoints_overlap=False, kf_trace=None, refine_iters=0, eval_render=False,
              sequence=None, nr_objects=None, sensor="depth", viewer_dir=None, viewer_modes=("rgb",), viewer_every=0,
              learn_objects=0, mesh_path=None, mesh_voxel=0.02, mesh_gt=None, mesh_samples=200_000,
-             mesh_depth_l1=False):
+             mesh_depth_l1=False, tracker="adam"):
     """Tracks and maps a sequence in one process; returns tracking / mapping rates, iterations and the trajectory error (``_report``).
     Every argument is described where it acts: ``_setup``, ``_track_frame``, ``_select_keyframe``, ``_map_keyframe``, ``_map_window``,
     ``_finish`` (what follows the last frame).  ``log``: a callable that gets a line per frame.  ``sensor="monocular"`` adds the result
@@ -432,7 +439,8 @@ def run_slam(n_frames=12, intrinsics="fr3_office", tracking_itr_num=100, mapping
     ``learn_objects=N`` (with ``nr_objects``): learn the object rows, N trainer iterations over the window after each mapping call; only
     then does the result hold an ``objects`` entry (iterations, first and last label loss, label accuracy and mIoU).
     ``mesh_path``: write the final map's triangle mesh there (``_finish``); only then does the result hold a ``mesh`` entry;
-    with ``mesh_gt`` that entry gains ``reconstruction`` and, with ``mesh_depth_l1``, ``depth_l1`` (``_finish``)."""
+    with ``mesh_gt`` that entry gains ``reconstruction`` and, with ``mesh_depth_l1``, ``depth_l1`` (``_finish``).
+    ``tracker="gauss_newton"``: the second-order tracker of ``gn_tracking`` instead of Adam; only then does the result hold a ``tracker`` entry."""
     s = _setup(SimpleNamespace(**locals()))              # (every argument, by name: must stay the first statement)
     for i, vp in enumerate(s.frames):
         if i == 0:
@@ -442,7 +450,7 @@ def run_slam(n_frames=12, intrinsics="fr3_office", tracking_itr_num=100, mapping
             if viewer_dir is not None and viewer_every > 0 and s.stats["keyframes"] % viewer_every == 0:
                 _viewer_frames(s, vp, f"kf{s.stats['keyframes']:04d}")
             continue
-        n_it = _track_frame(s, vp, s.frames[i - 1], tracking_itr_num, graph_tracking, exclusive_device, track_lookahead)
+        n_it = _track_frame(s, vp, s.frames[i - 1], tracking_itr_num, graph_tracking, exclusive_device, track_lookahead, tracker)
         s.stats["renders"] += n_it
         s.per_frame.append((i, n_it))
         pkg, t0 = _select_keyframe(s, i, vp)

@@ -17,6 +17,8 @@ stand-in; the TUM / Replica sequences are not available offline).  Prints one JS
       # ... and scored against the ground-truth mesh: accuracy, completion, completion ratio, Chamfer-L1, F-score (monogs_amd.mesh_eval)
   python tools/slam_bench.py --config tum --room --graph --mesh room.ply --mesh-gt room --mesh-depth-l1
       # ... and Depth L1 between the two meshes rendered from the keyframes (monogs_amd.mesh_render)
+  python tools/slam_bench.py --config tum --room --graph --tracker gauss_newton
+      # the Gauss-Newton tracker (monogs_amd.gn_tracking) instead of Adam: fewer, heavier tracking iterations per frame
 """
 import argparse
 import json
@@ -91,6 +93,9 @@ if __name__ == "__main__":
     ap.add_argument("--mesh-depth-l1", action="store_true",
                     help="with --mesh-gt: `mesh` gains `depth_l1`, the two meshes rendered from the keyframes and compared "
                          "(monogs_amd.mesh_render.eval_depth_l1)")
+    ap.add_argument("--tracker", default="adam", choices=["adam", "gauss_newton"],
+                    help="gauss_newton: track with second-order steps on the pose-tangent planes (monogs_amd.gn_tracking) instead of "
+                         "Adam; the result gains `tracker`, compare `track_iters_per_frame` and `tracking_fps`")
     a = ap.parse_args()
     if a.mesh_gt and not a.mesh:
         ap.error("--mesh-gt evaluates the mesh --mesh writes")
@@ -131,7 +136,8 @@ if __name__ == "__main__":
                    viewer_modes=tuple(a.viewer_modes), viewer_every=a.viewer_every, log=lambda s: print("[slam]", s, file=sys.stderr, flush=True), **objects, **cfg,
                    **(dict(mesh_path=a.mesh, mesh_voxel=a.mesh_voxel) if a.mesh else {}),
                    **(dict(mesh_gt=a.mesh_gt, mesh_samples=a.mesh_samples) if a.mesh_gt else {}),
-                   **(dict(mesh_depth_l1=True) if a.mesh_depth_l1 else {}))
+                   **(dict(mesh_depth_l1=True) if a.mesh_depth_l1 else {}),
+                   **(dict(tracker=a.tracker) if a.tracker != "adam" else {}))
     what = f"{a.dataset}, every {a.stride}. frame" if a.dataset else f"synthetic {a.config}-like sequence"
     out["workload"] = f"{what}, {a.frames} frames" + (" (fork's hard-coded run configuration)" if a.fork else "")
     if sensor == "monocular":
