@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define MGS_ABI_VERSION 29
+#define MGS_ABI_VERSION 30
 #define MGS_TILE 16 /* tile edge in pixels; ranges are per 16x16 tile */
 
 /* GaussianRasterizationSettings, minus `prefiltered` / `debug` which are call flags
@@ -303,6 +303,36 @@ int mgs_debug_last_backward_split(void);
  * 1 = default, 0 = the plain emission and two passes everywhere; the same tables either way.  Set it between whole forwards,
  * like "pre_scan". */
 int mgs_debug_last_tile_sort_bands(void);
+
+/* TEST USE ONLY, a read-only window (pure apart from the options it follows, like mgs_binning_path; no launch, no device): the
+ * route a forward of P Gaussians at W x H with cam.flags = `flags` takes, and -- for R instances, or with capacity_mode != 0 a
+ * capacity of R -- the route of its render call, as MGS_PLAN_WORDS words in out[] [host].  One word per field of the forward
+ * plan ("The forward plan"; csrc/forward_plan.h), flags as 0 / 1: */
+enum {
+    MGS_PLAN_P = 0, MGS_PLAN_W, MGS_PLAN_H, MGS_PLAN_FLAGS, MGS_PLAN_CAPACITY_MODE,           /* the inputs */
+    MGS_PLAN_TILES_X, MGS_PLAN_TILES_Y, MGS_PLAN_NTILES, MGS_PLAN_TILE_BITS,
+    MGS_PLAN_SMALL_GRID,       /* ntiles <= 65536 */
+    MGS_PLAN_PER_TILE,         /* = mgs_binning_path(P, W, H) */
+    MGS_PLAN_SCAN_ITEMS,       /* Gaussians per scan block: 256 = the per-Gaussian forward kernel scans ("pre_scan"), else 2048 */
+    MGS_PLAN_SCAN_SHIFT, MGS_PLAN_SCAN_BLOCKS,
+    MGS_PLAN_SCAN_SMALL,       /* the single-launch scan ("scan_small"; 2048-item granularity and at most 64 blocks only) */
+    MGS_PLAN_BANDS_COUNTED,    /* bands of 256 tiles the preprocess half counts and scans ("tile_sort_banded"); 0 = none */
+    MGS_PLAN_RECT_PACKED,      /* the depth sort carries packed rectangles (else its last pass gathers them) */
+    MGS_PLAN_EXCLUSIVE,        /* MGS_FLAG_EXCLUSIVE_DEVICE */
+    MGS_PLAN_R,                /* the render half from here: R, 0 when P == 0 */
+    MGS_PLAN_R_CAP,            /* the emission's bound: the capacity; exact path 0xFFFFFFFF, or 0 when R == 0 */
+    MGS_PLAN_SLOT_MAJOR,       /* emission balanced by output slots ("dup_slot_major") */
+    MGS_PLAN_BANDS,            /* what mgs_debug_last_tile_sort_bands() reports after that render call */
+    MGS_PLAN_COUNT_DIGITS,     /* the emission counts the tile sort's digits: no histogram launch */
+    MGS_PLAN_KEY_SHIFT, MGS_PLAN_DEPTH_LO_BITS,       /* per-tile path: 32 - tile bits, depth bits kept in the value; else 0, 0 */
+    MGS_PLAN_SORT_TILES,       /* per-tile path with R > 0: each tile's list is sorted by depth ... */
+    MGS_PLAN_TILE_SORT_FUSED,  /* ... inside the blend forward ("tile_sort_fused"), else by a launch of its own */
+    MGS_PLAN_DUP_THREADS,      /* threads of the plain emission's launch */
+    MGS_PLAN_BANDED_BYTES,     /* scratch of the banded tile sort's one pass for R pairs (0 without counted bands) ... */
+    MGS_PLAN_TWO_PASS_BYTES,   /* ... which must fit this, = mgs_debug_sort_temp_bytes(R, tile bits), for MGS_PLAN_BANDS != 0 */
+    MGS_PLAN_WORDS
+};
+int mgs_debug_forward_plan(int32_t P, int32_t W, int32_t H, int32_t flags, uint64_t R, int32_t capacity_mode, uint64_t* out);
 
 /* Diagnostic (not on the hot path): counts what the blend backward of the matching forward does, into
  * stats_dev[MGS_BLEND_STATS_WORDS] (device uint64): [0] 64-instance steps walked, [1] instances that pass the per-quadrant

@@ -11,7 +11,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MGS_LIB_PATH") or os.path.join(_HERE, "lib", "libmonogs_raster.so")   # (override: kernel experiments)
-ABI_VERSION = 29
+ABI_VERSION = 30
 FLAG_EXCLUSIVE_DEVICE = 1          # MGS_FLAG_* bits of mgs_camera.flags (include/monogs_raster.h)
 FLAG_INTRINSICS_GRAD = 2
 
@@ -127,6 +127,7 @@ SIGNATURES = {
     "mgs_debug_set_blend_events": (C.c_int, [C.c_void_p] * 4),
     "mgs_debug_last_backward_split": (C.c_int, []),
     "mgs_debug_last_tile_sort_bands": (C.c_int, []),
+    "mgs_debug_forward_plan": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.POINTER(C.c_uint64)]),
     "mgs_mark_visible": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mgs_loss_scratch_bytes": (C.c_size_t, []),
     "mgs_loss_forward": (C.c_int, [C.c_int32] * 4 + [C.c_float] + [C.c_void_p] * 9 + [C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -178,7 +178,7 @@ using namespace mgs;
 extern "C" {
 
 int mgs_abi_version(void) { return MGS_ABI_VERSION; }
-int mgs_binning_path(int32_t P, int32_t W, int32_t H) { return binning_path(P, W, H); }
+int mgs_binning_path(int32_t P, int32_t W, int32_t H) { return forward_plan(P, W, H, 0).per_tile ? 1 : 0; }
 const char* mgs_last_error(void) { return g_err; }
 
 size_t mgs_geometry_bytes(int32_t P) { return GeometryState::bytes(P < 0 ? 0 : P); }
@@ -239,27 +239,22 @@ int mgs_forward_preprocess(const mgs_camera* cam, int32_t P, const float* means3
     }
     hipStream_t s = (hipStream_t)stream;
     GeometryState g = GeometryState::carve(geometry, P);
+    const ForwardPlan plan = forward_plan(P, cam->image_width, cam->image_height, cam->flags);
     StageTimer tm(s, timing != nullptr);
     tm.mark();
-    if (int rc = launch_preprocess_forward(*cam, P, means3D, shs, colors_precomp, opacities, scales, rotations,
+    if (int rc = launch_preprocess_forward(plan, *cam, means3D, shs, colors_precomp, opacities, scales, rotations,
                                            cov3D_precomp, g, radii,
                                            prepare_backward ? BackwardState::carve(prepare_backward, P).grad_acc : nullptr, s)) return rc;
     tm.mark();
-    const bool exclusive = (cam->flags & MGS_FLAG_EXCLUSIVE_DEVICE) != 0;
-    const bool per_tile = binning_path(P, cam->image_width, cam->image_height) != 0;
-    const int items = scan_items(P, cam->image_width, cam->image_height);      // (the decision launch_preprocess_forward took)
-    if (per_tile) {                         // no global depth sort: the scan runs in index order (binning.hip)
-        tm.mark();
-        if (int rc = launch_scan(g, P, s, exclusive, g.rect, items, tile_sort_bands(P, cam->image_width, cam->image_height))) return rc;
-    } else {
-        if (int rc = launch_depth_sort(g, P, depth_sort_payload(P, cam->image_width, cam->image_height), s, exclusive)) return rc;
-        tm.mark();
-        if (int rc = launch_scan(g, P, s, exclusive, g.rect_sorted, items)) return rc;
-    }
+    // (per-tile path: no global depth sort, the scan runs in index order -- binning.hip)
+    if (!plan.per_tile)
+        if (int rc = launch_depth_sort(plan, g, s)) return rc;
+    tm.mark();
+    if (int rc = launch_scan(plan, g, s)) return rc;
     tm.mark();
     if (num_rendered) {
         uint32_t total = 0, sort_errors[RADIX_ERROR_WORDS] = {0, 0, 0, 0};
-        MGS_HIP(hipMemcpyAsync(&total, g.scan_blocks + scan_nblocks(P, items), sizeof(uint32_t), hipMemcpyDeviceToHost, s));   // grand total
+        MGS_HIP(hipMemcpyAsync(&total, g.scan_blocks + plan.scan_blocks, sizeof(uint32_t), hipMemcpyDeviceToHost, s));   // grand total
         MGS_HIP(hipMemcpyAsync(sort_errors, radix_depth_error_flag(g.sort_temp, (uint64_t)P), sizeof(sort_errors),
                                hipMemcpyDeviceToHost, s));
         // the status word of an EARLIER forward on this stream rides along: its kernels are done by the time this copy runs,
@@ -273,13 +268,11 @@ int mgs_forward_preprocess(const mgs_camera* cam, int32_t P, const float* means3
     if (timing) {
         if (!num_rendered) MGS_HIP(hipStreamSynchronize(s));
         timing->preprocess_ms = tm.ms(0);
-        timing->depth_sort_ms = per_tile ? 0.f : tm.ms(1);
+        timing->depth_sort_ms = plan.per_tile ? 0.f : tm.ms(1);
         timing->scan_ms = tm.ms(2);
     }
     return 0;
 }
-
-static int g_opt_tile_sort_fused = 1;        // mgs_debug_set_option("tile_sort_fused", 0): the per-tile depth sort as a launch of its own
 
 static int forward_render_impl(const mgs_camera* cam, int32_t P, uint64_t R, bool capacity, void* geometry,
                                void* binning, void* image, float* out_color, float* out_depth, float* out_opacity,
@@ -291,38 +284,28 @@ static int forward_render_impl(const mgs_camera* cam, int32_t P, uint64_t R, boo
     if (P > 0 && (!geometry || !n_touched)) { set_error("geometry and n_touched must be non-NULL"); return 1; }
     if (R > 0 && !binning) { set_error("binning scratch is NULL"); return 1; }
     if (R >= (1ull << 32)) { set_error("num_rendered exceeds 2^32-1"); return 1; }
-    // No Gaussians: nothing was preprocessed (geometry may be NULL, its digit table was never cleared), so nothing may be
-    // sorted whatever capacity the caller passed -- the kernels below then only clear the ranges and render the background.
-    if (P == 0) R = 0;
     hipStream_t s = (hipStream_t)stream;
     const int W = cam->image_width, H = cam->image_height;
+    // (P == 0: the plan's R is 0 whatever the caller passed; geometry may be NULL)
+    const ForwardPlan plan = forward_plan(P, W, H, cam->flags).render(R, capacity);
+    R = plan.R;
     auto [g, img, b] = carve_forward(geometry, binning, image, P, R, W, H);
-    const uint32_t* n_dev = nullptr;
     StageTimer tm(s, timing != nullptr);
-    const bool cap = capacity && binning;
-    if (cap) n_dev = b.count;
-    const bool per_tile = binning_path(P, W, H) != 0;       // (the same decision mgs_forward_preprocess took)
+    uint32_t* const count = (capacity && binning) ? b.count : nullptr;      // capacity mode: the live count stays on the device
     tm.mark();
-    // (also zeroes n_touched, the tile ranges and the scratch of the tile sort; in capacity mode it publishes the
-    //  clamped live count and the overflow flag; with R == 0 it emits nothing)
-    if (int rc = launch_duplicate(*cam, P, g, b, capacity ? R : (R > 0 ? 0xFFFFFFFFull : 0ull), n_touched, img, R,
-                                  tile_bits(W, H), cap ? b.count : nullptr, overflow, s, per_tile)) return rc;
+    if (int rc = launch_duplicate(plan, g, b, img, n_touched, count, overflow, s)) return rc;
     tm.mark();
-    // (the sort's final pass writes the per-tile ranges: no ranges launch since round 4)
-    if (int rc = launch_sort(g, b, R, tile_bits(W, H), s, n_dev, (cam->flags & MGS_FLAG_EXCLUSIVE_DEVICE) != 0, img.ranges,
-                             per_tile, per_tile ? tile_sort_bands_render(P, W, H, R) : 0)) return rc;
-    const uint32_t* sort_err = R > 0 ? radix_error_flag(b.sort_temp, R, tile_bits(W, H)) : nullptr;
+    if (int rc = launch_sort(plan, g, b, img, count, s)) return rc;
+    const uint32_t* sort_err = R > 0 ? radix_error_flag(b.sort_temp, R, plan.tile_bits) : nullptr;
     // per-tile depth order: each tile's list, in index order now, sorted by depth in LDS -- by the blend forward's workgroup
     // of the tile (timed with the blend forward), or by a launch of its own (timed with the sort)
-    const bool sort_tiles = per_tile && R > 0;
-    const TileSortArgs ts = sort_tiles ? tile_sort_args(*cam, g, b, R, n_dev) : TileSortArgs{};
-    const bool fused = sort_tiles && g_opt_tile_sort_fused != 0;
-    if (sort_tiles && !fused)
-        if (int rc = launch_tile_depth_sort(*cam, ts, img, sort_err, s)) return rc;
+    const TileSortArgs ts = plan.sort_tiles ? tile_sort_args(plan, g, b, count) : TileSortArgs{};
+    if (plan.sort_tiles && !plan.tile_sort_fused)
+        if (int rc = launch_tile_depth_sort(plan, ts, img, sort_err, s)) return rc;
     tm.mark();
     if (g_dbg_fwd_events[0]) MGS_HIP(hipEventRecord(g_dbg_fwd_events[0], s));
-    if (int rc = launch_blend_forward(*cam, g, b, img, out_color, out_depth, out_opacity, n_touched, sort_err, overflow,
-                                      fused ? &ts : nullptr, P, s)) return rc;
+    if (int rc = launch_blend_forward(plan, *cam, g, b, img, out_color, out_depth, out_opacity, n_touched, sort_err, overflow,
+                                      ts, s)) return rc;
     if (g_dbg_fwd_events[1]) MGS_HIP(hipEventRecord(g_dbg_fwd_events[1], s));
     tm.mark();
     if (timing) {
@@ -528,6 +511,22 @@ int mgs_debug_valu_ceiling(float* out, int32_t iters, void* stream) {
 int mgs_debug_last_backward_split(void) { return g_dbg_last_bwd_split; }
 int mgs_debug_last_tile_sort_bands(void) { return g_dbg_last_tile_sort_bands; }
 
+int mgs_debug_forward_plan(int32_t P, int32_t W, int32_t H, int32_t flags, uint64_t R, int32_t capacity_mode, uint64_t* out) {
+    if (!out || P < 0 || W <= 0 || H <= 0 || R >= (1ull << 32)) { set_error("mgs_debug_forward_plan: out non-NULL, P >= 0, W, H > 0, R < 2^32"); return 1; }
+    const ForwardPlan p = forward_plan(P, W, H, flags).render(R, capacity_mode != 0);
+    auto u = [](int v) { return (uint64_t)(uint32_t)v; };
+    const uint64_t words[MGS_PLAN_WORDS] = {
+        u(p.P), u(p.W), u(p.H), u(p.flags), p.capacity_mode, u(p.tiles_x), u(p.tiles_y), u(p.ntiles), u(p.tile_bits), p.small_grid,
+        p.per_tile, u(p.scan_items), u(p.scan_shift), u(p.scan_blocks), p.scan_small, u(p.bands_counted), p.rect_packed, p.exclusive,
+        p.R, p.r_cap, p.slot_major, u(p.bands), p.count_digits, u(p.key_shift), u(p.depth_lo_bits), p.sort_tiles, p.tile_sort_fused,
+        u(p.dup_threads),
+        // the two scratch sizes the banded decision compares (no banded pass without counted bands)
+        p.bands_counted ? radix_banded_temp_bytes(p.R, p.bands_counted) : 0, radix_temp_bytes(p.R, p.tile_bits)};
+    static_assert(MGS_PLAN_TWO_PASS_BYTES == MGS_PLAN_WORDS - 1 && MGS_PLAN_PER_TILE == 10 && MGS_PLAN_R == 18, "the order of MGS_PLAN_*");
+    memcpy(out, words, sizeof(words));
+    return 0;
+}
+
 int mgs_debug_set_radix_spin_limit(uint32_t limit) { return set_radix_spin_limit(limit); }
 
 int mgs_debug_set_blend_events(void* fwd_start, void* fwd_end, void* bwd_start, void* bwd_end) {
@@ -551,9 +550,9 @@ int mgs_debug_sort_pairs(uint32_t* keys, uint32_t* vals, uint32_t* keys_alt, uin
     }
     if (n == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    if (int rc = radix_sort_pairs(keys, vals, keys_alt, vals_alt, n, bits, temp, s, nullptr, false, nullptr, nullptr, nullptr, false,
-                                  g_opt_debug_sort_exclusive != 0))
-        return rc;
+    RadixSortOptions o;
+    o.exclusive = g_opt_debug_sort_exclusive != 0;
+    if (int rc = radix_sort_pairs(keys, vals, keys_alt, vals_alt, n, bits, temp, s, o)) return rc;
     if (radix_result_in_b(bits)) {
         MGS_HIP(hipMemcpyAsync(keys, keys_alt, n * 4, hipMemcpyDeviceToDevice, s));
         MGS_HIP(hipMemcpyAsync(vals, vals_alt, n * 4, hipMemcpyDeviceToDevice, s));

@@ -13,9 +13,9 @@
 // the hand-written LSD radix sort of radix_sort.hip.  The last pass of the depth sort also lays the tile
 // rectangles out in depth order, so the scan and duplicate below read everything coalesced.
 //
-// Large maps (binning_path() == 1) skip (1): the instances are emitted in index order with their depth in the pair and each
+// Large maps (ForwardPlan::per_tile) skip (1): the instances are emitted in index order with their depth in the pair and each
 // tile's list is sorted by depth on its own (tile_sort.h).  There the tile sort only has to group by tile, stably -- and the
-// band of 256 tiles an instance falls into is known where the instance is made: tile_sort_bands() != 0 emits the instances
+// band of 256 tiles an instance falls into is known where the instance is made: ForwardPlan::bands != 0 emits the instances
 // grouped by band from exact counts (preprocess counts them per scan block, scan_blocks_kernel scans them, emit_banded_kernel
 // places them) and (3) is ONE segmented 8-bit pass, radix_sort_banded, instead of two passes over everything.
 #include "common.h"
@@ -26,7 +26,7 @@ namespace mgs {
 
 // ------------------------------------------------------------------------------------------------
 // inclusive scan of uint32 in two steps: per-block local scan + block sums, exclusive scan of the block sums
-// (+ the grand total).  Global offset of element i = local[i] + block_sums[i / items], items = scan_items() of the forward:
+// (+ the grand total).  Global offset of element i = local[i] + block_sums[i / items], items = ForwardPlan::scan_items:
 //   SCAN_ITEMS (2048; 256 threads x 8 items): scan_local_kernel, a launch of its own over the rectangles -- the global path,
 //     where the scan runs in depth order, after the depth sort;
 //   SCAN_ITEMS_PRE (256): the per-tile path, where the scan runs in index order: preprocess_forward_kernel has the
@@ -188,42 +188,75 @@ __global__ void __launch_bounds__(SCAN_THREADS) scan_small_kernel(const uint2* _
     }
     if (threadIdx.x == 0 && bid == nb - 1) block_sums[nb] = s_prefix + total;
 }
+
+// ---- The forward plan (forward_plan.h; DESIGN.md, "The forward plan"): every route decision of one forward, each rule written
+// once, here.  Every launcher reads the plan; nothing outside this builder reads the five options below.
 int g_opt_scan_small = -1;          // mgs_debug_set_option("scan_small", -1 | 0 | 1): 0 = always the two-launch scan
 int g_opt_pre_scan = -1;            // mgs_debug_set_option("pre_scan", -1 | 0 | 1): 0 = per-tile path scans with launches of its own
-// The ONE host-side place that decides the scan's granularity: preprocess (does it scan?), launch_scan (what is left to
-// launch), launch_duplicate (how the offsets are put together) and the exact path's read-back all ask here.
-int scan_items(int P, int W, int H) {
-    return (g_opt_pre_scan != 0 && binning_path(P, W, H) != 0) ? SCAN_ITEMS_PRE : SCAN_ITEMS;
-}
 int g_opt_tile_sort_banded = 1;     // mgs_debug_set_option("tile_sort_banded", 0): today's two tile-sort passes everywhere
-int g_dbg_last_tile_sort_bands = 0; // mgs_debug_last_tile_sort_bands(): bands of the last forward's tile sort (0: two passes)
-// The ONE host-side place that decides the banded tile sort (common.h): preprocess (does it count bands?), launch_scan (the
-// column scan), launch_duplicate (which emission kernel) and launch_sort (one segmented pass) all ask here.
-int tile_sort_bands(int P, int W, int H) {
-    if (g_opt_tile_sort_banded == 0 || scan_items(P, W, H) != SCAN_ITEMS_PRE) return 0;      // (per-tile path, preprocess scans)
-    const int tb = tile_bits(W, H), ntiles = tiles_x(W) * tiles_y(H);
-    const int bands = (ntiles + (1 << TILE_BAND_BITS) - 1) >> TILE_BAND_BITS;
-    return (tb > TILE_BAND_BITS && bands <= TILE_SORT_MAX_BANDS) ? bands : 0;
-}
-constexpr uint64_t DUP_SLOT_MAJOR_MIN = 768ull * 1024;      // instances (capacity in capacity mode)
 int g_opt_dup_slot_major = -1;      // mgs_debug_set_option("dup_slot_major", -1 | 0 | 1): -1 = by size
-// duplicate_kernel's emission balanced by output slots (see the kernel and launch_duplicate): forced, or many instances AND
-// many per Gaussian
-static bool dup_slot_major(int P, uint64_t sort_n) {
-    return P > 0 && g_opt_dup_slot_major != 0 &&
-           (g_opt_dup_slot_major > 0 || (sort_n >= DUP_SLOT_MAJOR_MIN && sort_n >= 6ull * (uint64_t)P));
+int g_opt_tile_sort_fused = 1;      // mgs_debug_set_option("tile_sort_fused", 0): the per-tile depth sort as a launch of its own
+int g_dbg_last_tile_sort_bands = 0; // mgs_debug_last_tile_sort_bands(): bands of the last emission launched (0: two passes)
+constexpr uint64_t DUP_SLOT_MAJOR_MIN = 768ull * 1024;      // instances (capacity in capacity mode)
+static_assert(SCAN_ITEMS == 1 << 11 && SCAN_ITEMS_PRE == 1 << 8, "scan_shift");
+
+ForwardPlan forward_plan(int P, int W, int H, int flags) {
+    ForwardPlan p{};
+    p.P = P; p.W = W; p.H = H; p.flags = flags;
+    p.tiles_x = tiles_x(W); p.tiles_y = tiles_y(H); p.ntiles = p.tiles_x * p.tiles_y;
+    p.tile_bits = tile_bits(W, H); p.small_grid = p.ntiles <= 65536;
+    // Depth order per tile (tile_depth_sort) wherever the map's depth sort would take the counted-tiles path -- or at any size
+    // when the radix_scanned knob is 1 -- and the tile sort's keys have room for the high depth bits beside a tile id of
+    // <= 16 bits, the values for the low ones beside the index: P <= 2^(37 - tile bits).  Else the global depth sort (one
+    // sweep, or counted tiles with the knob at 0).
+    const RadixSizeClass map_class = P > 0 ? radix_size_class((uint64_t)P) : RADIX_ONE_SWEEP;
+    p.per_tile = map_class != RADIX_ONE_SWEEP && p.tile_bits <= 16 &&
+                 (uint64_t)P <= (1ull << (32 - tile_depth_lo_bits(p.tile_bits)));
+    // the scan's granularity: preprocess scans its own 256 Gaussians on the per-tile path (option "pre_scan" not 0)
+    p.scan_items = (g_opt_pre_scan != 0 && p.per_tile) ? SCAN_ITEMS_PRE : SCAN_ITEMS;
+    p.scan_shift = p.scan_items == SCAN_ITEMS_PRE ? 8 : 11; p.scan_blocks = scan_nblocks(P, p.scan_items);
+    // (SCAN_ITEMS granularity only: the single-launch scan writes GLOBAL sums)
+    p.scan_small = P > 0 && p.scan_items == SCAN_ITEMS && g_opt_scan_small != 0 && p.scan_blocks <= SCAN_SMALL_MAX_BLOCKS;
+    // banded tile sort: the per-tile path where preprocess scans, a tile id wider than one digit, at most 32 bands of 256 tiles
+    const int bands = (p.ntiles + (1 << TILE_BAND_BITS) - 1) >> TILE_BAND_BITS;
+    p.bands_counted = (g_opt_tile_sort_banded != 0 && p.scan_items == SCAN_ITEMS_PRE && p.tile_bits > TILE_BAND_BITS &&
+                       bands <= TILE_SORT_MAX_BANDS) ? bands : 0;
+    // the depth sort carries the rectangles itself on its counted-tiles path; the packed form needs both grid dimensions in a byte
+    p.rect_packed = !p.per_tile && map_class == RADIX_COUNTED && p.tiles_x <= 255 && p.tiles_y <= 255;
+    p.exclusive = (flags & MGS_FLAG_EXCLUSIVE_DEVICE) != 0;
+    return p;
 }
-// Scenes of big splats keep the slot-balanced duplicate_kernel and the two passes: emit_banded_kernel is one workgroup per 256
-// Gaussians, the Gaussian-major balance that kernel was built to escape (a forced "dup_slot_major" = 1 is honoured the same way).
-int tile_sort_bands_render(int P, int W, int H, uint64_t R) {
-    const int bands = tile_sort_bands(P, W, H);
-    if (!bands || R == 0 || dup_slot_major(P, R)) return 0;
-    return radix_banded_temp_bytes(R, bands) <= radix_temp_bytes(R, tile_bits(W, H)) ? bands : 0;
+
+ForwardPlan ForwardPlan::render(uint64_t R_in, bool capacity) const {
+    ForwardPlan p = *this;
+    p.capacity_mode = capacity;
+    // No Gaussians: nothing was preprocessed, so nothing may be sorted whatever capacity the caller passed (background only)
+    p.R = P == 0 ? 0 : R_in;
+    p.r_cap = capacity ? (uint32_t)(p.R > 0xFFFFFFFFull ? 0xFFFFFFFFull : p.R) : (p.R > 0 ? 0xFFFFFFFFu : 0u);
+    // Many instances AND many instances per Gaussian (big splats: the near ones cover hundreds of tiles), or forced: emission
+    // balanced by output slots (see duplicate_kernel), with enough waves for ~512 slots each.  Otherwise the Gaussian-major
+    // walk: no search, fewer loads per slot (C5, 2.6 instances per Gaussian: 22 us against 31 us slot-major; 102 k Gaussians at
+    // 1200x680, 13 per Gaussian: 81 us against 8.6 us; 39 k at VGA, 415 k instances: 7.5 against 8.8 us).
+    p.slot_major = P > 0 && g_opt_dup_slot_major != 0 &&
+                   (g_opt_dup_slot_major > 0 || (p.R >= DUP_SLOT_MAJOR_MIN && p.R >= 6ull * (uint64_t)P));
+    int n = P > ntiles ? P : ntiles;
+    if (p.slot_major && p.R / 8 > (uint64_t)n) n = (int)(p.R / 8 > 0x3FFFFFFFull ? 0x3FFFFFFFull : p.R / 8);
+    p.dup_threads = (n + 255) / 256 * 256;
+    // The banded emission, once R is known.  Scenes of big splats keep the slot-balanced duplicate_kernel and the two passes:
+    // emit_banded_kernel is one workgroup per 256 Gaussians, the Gaussian-major balance that kernel was built to escape (a
+    // forced "dup_slot_major" = 1 is honoured the same way).  And the scratch of the one segmented pass must fit what
+    // mgs_binning_bytes() reserves for the two passes (for a few thousand instances it does not: a partial tile per band
+    // outweighs them).  0: the plain emission and the two passes, whatever preprocess counted.
+    p.bands = (bands_counted && p.R > 0 && !p.slot_major &&
+               radix_banded_temp_bytes(p.R, bands_counted) <= radix_temp_bytes(p.R, tile_bits)) ? bands_counted : 0;
+    // duplicate_kernel counts the digits of the keys it emits where the tile sort reads a global histogram (one sweep)
+    p.count_digits = !p.bands && P > 0 && tile_bits <= 16 && p.R > 0 && radix_size_class(p.R) != RADIX_COUNTED;
+    p.key_shift = per_tile ? 32 - tile_bits : 0; p.depth_lo_bits = per_tile ? tile_depth_lo_bits(tile_bits) : 0;
+    p.sort_tiles = per_tile && p.R > 0;
+    p.tile_sort_fused = p.sort_tiles && g_opt_tile_sort_fused != 0;
+    return p;
 }
-// (SCAN_ITEMS granularity only: the single-launch scan writes GLOBAL sums)
-static bool scan_is_small(int P, int items) {
-    return items == SCAN_ITEMS && g_opt_scan_small != 0 && scan_nblocks(P, SCAN_ITEMS) <= SCAN_SMALL_MAX_BLOCKS;
-}
+
 
 // (There is no third "add the block offset" pass: the only consumer of the offsets, duplicate_kernel, adds
 //  block_sums[i / items] itself -- one launch and a 16-byte-per-Gaussian read-modify-write less.)
@@ -231,22 +264,24 @@ static bool scan_is_small(int P, int items) {
 // (Measured and rejected: a single-workgroup scan for small P -- 1024 threads x a serial run of dependent
 //  gathers each -- took ~300 us at P = 38 k against ~15 us for the three launches below: latency, not launches.)
 //
-// What is launched:  items == SCAN_ITEMS_PRE (per-tile path): preprocess_forward_kernel already wrote the block-local sums
-// of its 256-Gaussian workgroups and their totals -- scan_blocks_kernel alone (the "scan_small" option has no effect).
-// items == SCAN_ITEMS: scan_small_kernel (one launch, P <= 131 072) or scan_local_kernel + scan_blocks_kernel.
-int launch_scan(const GeometryState& g, int P, hipStream_t s, bool exclusive, const uint2* rects, int items, int bands) {
+// What is launched:  scan_items == SCAN_ITEMS_PRE (per-tile path): preprocess_forward_kernel already wrote the block-local sums
+// of its 256-Gaussian workgroups and their totals -- scan_blocks_kernel alone, with a workgroup per counted band.
+// scan_items == SCAN_ITEMS: scan_small_kernel (one launch, P <= 131 072) or scan_local_kernel + scan_blocks_kernel.
+int launch_scan(const ForwardPlan& plan, const GeometryState& g, hipStream_t s) {
+    const int P = plan.P, nb = plan.scan_blocks;
     if (P == 0) return 0;
-    const int nb = scan_nblocks(P, items);
-    if (items == SCAN_ITEMS_PRE) {
-        hipLaunchKernelGGL(scan_blocks_kernel, dim3(1 + bands), dim3(SCANB_THREADS), 0, s, g.scan_blocks, nb, g.band_counts,
-                           g.band_totals);
+    if (plan.scan_items == SCAN_ITEMS_PRE) {
+        hipLaunchKernelGGL(scan_blocks_kernel, dim3(1 + plan.bands_counted), dim3(SCANB_THREADS), 0, s, g.scan_blocks, nb,
+                           g.band_counts, g.band_totals);
         MGS_HIP(hipGetLastError());
         return 0;
     }
-    if (scan_is_small(P, items)) {
+    // the rectangles in the order the scan runs in: depth order behind the depth sort, by index on the per-tile path
+    const uint2* rects = plan.per_tile ? g.rect : g.rect_sorted;
+    if (plan.scan_small) {
         hipLaunchKernelGGL(scan_small_kernel, dim3(nb), dim3(SCAN_THREADS), 0, s, rects, g.point_offsets, g.scan_blocks,
                            g.scan_status, P, nb, const_cast<uint32_t*>(radix_depth_error_flag(g.sort_temp, (uint64_t)P)),
-                           exclusive ? 0 : 1);
+                           plan.exclusive ? 0 : 1);
         MGS_HIP(hipGetLastError());
         return 0;
     }
@@ -539,7 +574,7 @@ __global__ void __launch_bounds__(256) duplicate_kernel(int P, const uint2* __re
 }
 
 // ------------------------------------------------------------------------------------------------
-// Banded emission (tile_sort_bands() != 0): duplicate_kernel's pairs, written grouped by band of 256 tiles.  One workgroup per
+// Banded emission (ForwardPlan::bands != 0): duplicate_kernel's pairs, written grouped by band of 256 tiles.  One workgroup per
 // scan block of 256 Gaussians.  The block's instances are its local slots [0, n) in Gaussian-major order (point_offsets[] are
 // the block-local inclusive sums); a chunk of EB_CHUNK slots is decoded (owner of a slot: binary search of the 256 sums in
 // LDS, then duplicate_kernel's slot decode), ranked stably by band with returning LDS atomics (the radix sort's ranking:
@@ -731,19 +766,19 @@ __global__ void __launch_bounds__(EB_THREADS) emit_banded_kernel(EmitBandedArgs 
     }
 }
 
-int launch_emit_banded(const mgs_camera& cam, int P, const GeometryState& g, uint32_t* keys, uint32_t* vals, uint64_t r_cap,
-                       int32_t* n_touched, const ImageState& img, uint32_t* zero_ptr, size_t zero_words, uint32_t* count,
-                       uint32_t* overflow, int bands, hipStream_t s) {
+static int launch_emit_banded(const ForwardPlan& plan, const GeometryState& g, const BinningState& b, const ImageState& img,
+                              int32_t* n_touched, uint32_t* zero_ptr, size_t zero_words, uint32_t* count, uint32_t* overflow,
+                              hipStream_t s) {
     EmitBandedArgs a;
-    const int tb = tile_bits(cam.image_width, cam.image_height);
-    a.P = P; a.rects = g.rect; a.depth_key = g.depth_key; a.tshift = 32 - tb; a.lo = tile_depth_lo_bits(tb);
+    a.P = plan.P; a.rects = g.rect; a.depth_key = g.depth_key; a.tshift = plan.key_shift; a.lo = plan.depth_lo_bits;
     a.offsets = g.point_offsets; a.block_sums = g.scan_blocks; a.band_counts = g.band_counts; a.band_totals = g.band_totals;
-    a.band_live = g.band_live; a.nbands = bands; a.nblk = scan_nblocks(P, SCAN_ITEMS_PRE);
-    a.keys = keys; a.vals = vals; a.gx = tiles_x(cam.image_width);
-    a.r_cap = (uint32_t)(r_cap > 0xFFFFFFFFull ? 0xFFFFFFFFull : r_cap);
-    a.n_touched = n_touched; a.ranges = img.ranges; a.ntiles = tiles_x(cam.image_width) * tiles_y(cam.image_height);
+    a.band_live = g.band_live; a.nbands = plan.bands; a.nblk = plan.scan_blocks;
+    // the pairs go to the ping-pong side: the ONE pass that follows ends where two passes end
+    a.keys = b.keys_b; a.vals = b.vals_b; a.gx = plan.tiles_x;
+    a.r_cap = plan.r_cap < plan.R ? plan.r_cap : (uint32_t)plan.R;     // (never past the buffers, whatever the counts say)
+    a.n_touched = n_touched; a.ranges = img.ranges; a.ntiles = plan.ntiles;
     a.zero_ptr = zero_ptr; a.zero_words = zero_words; a.count = count; a.overflow = overflow;
-    a.depth_err = radix_depth_error_flag(g.sort_temp, (uint64_t)P);
+    a.depth_err = radix_depth_error_flag(g.sort_temp, (uint64_t)plan.P);
     const int tile_blocks = (a.ntiles + EB_THREADS - 1) / EB_THREADS;
     const int blocks = a.nblk > tile_blocks ? a.nblk : tile_blocks;
     a.n_threads = blocks * EB_THREADS;
@@ -753,48 +788,29 @@ int launch_emit_banded(const mgs_camera& cam, int P, const GeometryState& g, uin
     return 0;
 }
 
-
-int launch_duplicate(const mgs_camera& cam, int P, const GeometryState& g, const BinningState& b, uint64_t r_cap,
-                     int32_t* n_touched, const ImageState& img, uint64_t sort_n, int sort_bits, uint32_t* count,
-                     uint32_t* overflow, hipStream_t s, bool per_tile) {
+// (also zeroes n_touched, the tile ranges and the scratch of the tile sort; in capacity mode it publishes the clamped live
+//  count and the overflow flag; with R == 0 it emits nothing)
+int launch_duplicate(const ForwardPlan& plan, const GeometryState& g, const BinningState& b, const ImageState& img,
+                     int32_t* n_touched, uint32_t* count, uint32_t* overflow, hipStream_t s) {
+    const int P = plan.P;
     const uint32_t* depth_err = P > 0 ? radix_depth_error_flag(g.sort_temp, (uint64_t)P) : nullptr;
-    const int ntiles = tiles_x(cam.image_width) * tiles_y(cam.image_height);
-    int n = P > ntiles ? P : ntiles;
-    if (n == 0) return 0;
-    // Many instances AND many instances per Gaussian (big splats: the near ones cover hundreds of tiles): emission balanced by
-    // output slots (see the kernel), with enough waves for ~512 slots each.  Otherwise the Gaussian-major walk: no search, fewer
-    // loads per slot (C5, 2.6 instances per Gaussian: 22 us against 31 us slot-major; 102 k Gaussians at 1200x680, 13 per
-    // Gaussian: 81 us against 8.6 us; 39 k at VGA, 415 k instances: 7.5 against 8.8 us).
-    const bool slot_major = dup_slot_major(P, sort_n);
-    if (slot_major) {
-        const uint64_t want = sort_n / 8;
-        if (want > (uint64_t)n) n = (int)(want > 0x3FFFFFFFull ? 0x3FFFFFFFull : want);
-    }
-    const int n_threads = (n + 255) / 256 * 256;
+    if (plan.dup_threads == 0) return 0;
     uint32_t* zero_ptr = nullptr;
     size_t zero_words = 0;
-    const int bands = per_tile ? tile_sort_bands_render(P, cam.image_width, cam.image_height, sort_n) : 0;
-    g_dbg_last_tile_sort_bands = bands;
-    if (sort_n > 0) {
-        if (bands) radix_banded_zero_region(b.sort_temp, sort_n, bands, &zero_ptr, &zero_words);
-        else radix_zero_region(b.sort_temp, sort_n, sort_bits, &zero_ptr, &zero_words);
+    g_dbg_last_tile_sort_bands = plan.bands;
+    if (plan.R > 0) {
+        if (plan.bands) radix_banded_zero_region(b.sort_temp, plan.R, plan.bands, &zero_ptr, &zero_words);
+        else radix_zero_region(b.sort_temp, plan.R, plan.tile_bits, &zero_ptr, &zero_words);
     }
-    if (bands)          // the pairs go to the ping-pong side: the ONE pass that follows ends where two passes end.  (r_cap: never
-                        // past the buffers, whatever the counts say)
-        return launch_emit_banded(cam, P, g, b.keys_b, b.vals_b, r_cap < sort_n ? r_cap : sort_n, n_touched, img, zero_ptr,
-                                  zero_words, count, overflow, bands, s);
-    const bool count_digits = P > 0 && sort_bits <= 16 && radix_wants_hist(sort_n);
-    const int tb = tile_bits(cam.image_width, cam.image_height);
-    const int items = scan_items(P, cam.image_width, cam.image_height);
-    hipLaunchKernelGGL(duplicate_kernel, dim3(n_threads / 256), dim3(256), 0, s, P, per_tile ? g.rect : g.rect_sorted,
-                       per_tile ? nullptr : g.perm, per_tile ? g.depth_key : nullptr, per_tile ? 32 - tb : 0,
-                       per_tile ? tile_depth_lo_bits(tb) : 0, g.point_offsets,
-                       g.scan_blocks, b.keys_a, b.vals_a, tiles_x(cam.image_width), tiles_y(cam.image_height),
-                       (uint32_t)(r_cap > 0xFFFFFFFFull ? 0xFFFFFFFFull : r_cap), n_touched, img.ranges, ntiles, zero_ptr,
-                       zero_words, count, overflow, depth_err,
-                       (P > 0 && scan_is_small(P, items)) ? 1 : 0, scan_shift(items), ntiles <= 65536 ? 1 : 0,
-                       count_digits ? g.tile_hist : nullptr, (sort_bits + 7) / 8, n_threads, slot_major ? 1 : 0,
-                       P > 0 ? g.prepare : nullptr);
+    if (plan.bands) return launch_emit_banded(plan, g, b, img, n_touched, zero_ptr, zero_words, count, overflow, s);
+    // per-tile path: emission in Gaussian-index order with the depth bits packed into the pairs
+    const bool per_tile = plan.per_tile;
+    hipLaunchKernelGGL(duplicate_kernel, dim3(plan.dup_threads / 256), dim3(256), 0, s, P, per_tile ? g.rect : g.rect_sorted,
+                       per_tile ? nullptr : g.perm, per_tile ? g.depth_key : nullptr, plan.key_shift, plan.depth_lo_bits,
+                       g.point_offsets, g.scan_blocks, b.keys_a, b.vals_a, plan.tiles_x, plan.tiles_y, plan.r_cap, n_touched,
+                       img.ranges, plan.ntiles, zero_ptr, zero_words, count, overflow, depth_err, plan.scan_small ? 1 : 0,
+                       plan.scan_shift, plan.small_grid ? 1 : 0, plan.count_digits ? g.tile_hist : nullptr,
+                       (plan.tile_bits + 7) / 8, plan.dup_threads, plan.slot_major ? 1 : 0, P > 0 ? g.prepare : nullptr);
     MGS_HIP(hipGetLastError());
     return 0;
 }
@@ -804,43 +820,41 @@ int launch_duplicate(const mgs_camera& cam, int P, const GeometryState& g, const
 // ------------------------------------------------------------------------------------------------
 size_t sort_temp_bytes(uint64_t n, int bits) { return radix_temp_bytes(n, bits); }
 
-int launch_depth_sort(const GeometryState& g, int P, bool payload, hipStream_t s, bool exclusive) {
+int launch_depth_sort(const ForwardPlan& plan, const GeometryState& g, hipStream_t s) {
     // the scratch was cleared by preprocess_forward_kernel; the final pass also lays the tile rectangles out in depth
-    // order for the scan and duplicate (`payload`: they travelled with the pairs, else it gathers them)
-    return radix_sort_depth(g.depth_key, g.depth_alt, g.iota, g.iota_alt, g.rect, payload, g.perm, g.rect_sorted, (uint64_t)P,
-                            g.sort_temp, s, true, exclusive);
+    // order for the scan and duplicate (rect_packed: they travelled with the pairs, else it gathers them)
+    return radix_sort_depth(g.depth_key, g.depth_alt, g.iota, g.iota_alt, g.rect, plan.rect_packed, g.perm, g.rect_sorted,
+                            (uint64_t)plan.P, g.sort_temp, s, true, plan.exclusive);
 }
 
-int launch_sort(const GeometryState& g, const BinningState& b, uint64_t R, int bits, hipStream_t s, const uint32_t* n_dev,
-                bool exclusive, uint2* ranges, bool per_tile, int bands) {
-    if (R == 0) return 0;
+int launch_sort(const ForwardPlan& plan, const GeometryState& g, const BinningState& b, const ImageState& img,
+                const uint32_t* n_dev, hipStream_t s) {
+    if (plan.R == 0) return 0;
     // banded: emit_banded_kernel left the pairs grouped by band on the ping-pong side; one segmented pass on the low 8 tile bits
-    if (bands)
-        return radix_sort_banded(b.keys_b, b.vals_b, b.keys_a, b.vals_a, R, 32 - bits, b.sort_temp, s, n_dev, g.band_live, bands, ranges);
-    // the scratch was cleared by duplicate_kernel, which also counted the digits of the keys it emitted (small sorts; the
-    // same predicate as launch_duplicate's `count_digits` -- R > 0 implies P > 0, forward_render_impl)
-    const bool counted = bits <= 16 && radix_wants_hist(R) && g.tile_hist != nullptr;
-    // per-tile depth order: the tile id is the top `bits` of the key (shift 32 - bits), the depth bits below it ride along
-    return radix_sort_pairs(b.keys_a, b.vals_a, b.keys_b, b.vals_b, R, bits, b.sort_temp, s, n_dev, true, nullptr, nullptr,
-                            counted ? g.tile_hist : nullptr, false, exclusive, ranges, per_tile ? 32 - bits : 0);
+    if (plan.bands)
+        return radix_sort_banded(b.keys_b, b.vals_b, b.keys_a, b.vals_a, plan.R, plan.key_shift, b.sort_temp, s, n_dev, g.band_live,
+                                 plan.bands, img.ranges);
+    // the scratch was cleared by duplicate_kernel, which also counted the digits of the keys it emitted (plan.count_digits;
+    // never a NULL histogram).  Per-tile depth order: the tile id is the top tile_bits of the key, the depth bits ride along.
+    RadixSortOptions o;
+    o.n_dev = n_dev; o.temp_zeroed = true; o.exclusive = plan.exclusive;
+    o.ext_hist = (plan.count_digits && g.tile_hist != nullptr) ? g.tile_hist : nullptr;
+    o.ranges = img.ranges; o.key_shift = plan.key_shift;      // (the final pass writes the per-tile ranges)
+    return radix_sort_pairs(b.keys_a, b.vals_a, b.keys_b, b.vals_b, plan.R, plan.tile_bits, b.sort_temp, s, o);
 }
 
 // ------------------------------------------------------------------------------------------------
-// Per-tile depth order (binning_path() == 1: large maps): tile_sort.h.  By default blend_forward_kernel<true> sorts its
+// Per-tile depth order (ForwardPlan::sort_tiles: large maps): tile_sort.h.  By default blend_forward_kernel<true> sorts its
 // own tile's list before it walks it (option "tile_sort_fused"); this kernel is the same sort as a launch of its own,
 // one 256-thread workgroup per tile.
 // ------------------------------------------------------------------------------------------------
-TileSortArgs tile_sort_args(const mgs_camera& cam, const GeometryState& g, const BinningState& b, uint64_t R,
-                            const uint32_t* n_dev) {
+TileSortArgs tile_sort_args(const ForwardPlan& plan, const GeometryState& g, const BinningState& b, const uint32_t* n_dev) {
     TileSortArgs ts;
-    ts.keys = b.keys_sorted;
-    ts.vals = b.vals_sorted;
+    ts.keys = b.keys_sorted; ts.vals = b.vals_sorted;
     ts.keys_alt = b.keys_sorted == b.keys_a ? b.keys_b : b.keys_a;
     ts.vals_alt = b.vals_sorted == b.vals_a ? b.vals_b : b.vals_a;
-    ts.depth_key = g.depth_key;
-    ts.n_dev = n_dev;
-    ts.n_cap = (uint32_t)R;
-    ts.tb = tile_bits(cam.image_width, cam.image_height);
+    ts.depth_key = g.depth_key; ts.n_dev = n_dev;
+    ts.n_cap = (uint32_t)plan.R; ts.tb = plan.tile_bits;
     return ts;
 }
 
@@ -855,10 +869,9 @@ __global__ void __launch_bounds__(TDS_THREADS) tile_depth_sort_kernel(TileSortAr
     tile_depth_sort(ts, ranges[tile], sort_err && radix_failed(sort_err) != 0u, TdsLds{s_k, s_v, s_cnt, s_wsum, s_red});
 }
 
-int launch_tile_depth_sort(const mgs_camera& cam, const TileSortArgs& ts, const ImageState& img, const uint32_t* sort_err,
+int launch_tile_depth_sort(const ForwardPlan& plan, const TileSortArgs& ts, const ImageState& img, const uint32_t* sort_err,
                            hipStream_t s) {
-    const int ntiles = tiles_x(cam.image_width) * tiles_y(cam.image_height);
-    hipLaunchKernelGGL(tile_depth_sort_kernel, dim3(ntiles), dim3(TDS_THREADS), 0, s, ts, img.ranges, ntiles, sort_err);
+    hipLaunchKernelGGL(tile_depth_sort_kernel, dim3(plan.ntiles), dim3(TDS_THREADS), 0, s, ts, img.ranges, plan.ntiles, sort_err);
     MGS_HIP(hipGetLastError());
     return 0;
 }

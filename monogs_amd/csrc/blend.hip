@@ -117,7 +117,7 @@ __device__ __forceinline__ void blend_one(unsigned long long& live, unsigned lon
     }
 }
 
-// SORT (per-tile depth order, binning_path() == 1): the workgroup first sorts its tile's list by depth (tile_sort.h) and
+// SORT (per-tile depth order, ForwardPlan::per_tile): the workgroup first sorts its tile's list by depth (tile_sort.h) and
 // writes it to point_list for the backward; a list of <= TDS_CAP pairs is then walked from the LDS copy of the sorted
 // indices.  The sort's keys and digit counters live in the record queue's LDS (first written after the sort's last
 // barrier), so the workgroup's LDS grows by the 4 KB index list only.  SORT = false: point_list is already in depth order.
@@ -309,29 +309,27 @@ __global__ void __launch_bounds__(256) blend_forward_kernel(BlendArgs a, float* 
     }
 }
 
-int launch_blend_forward(const mgs_camera& cam, const GeometryState& g, const BinningState& b,
+int launch_blend_forward(const ForwardPlan& plan, const mgs_camera& cam, const GeometryState& g, const BinningState& b,
                          const ImageState& img, float* out_color, float* out_depth, float* out_opacity,
-                         int32_t* n_touched, const uint32_t* sort_err, uint32_t* status, const TileSortArgs* tile_sort,
-                         int P, hipStream_t s) {
+                         int32_t* n_touched, const uint32_t* sort_err, uint32_t* status, const TileSortArgs& ts, hipStream_t s) {
     BlendArgs a = make_args(cam, g, b, img);
 #ifdef BS_TRACE
     a.trace = g_trace_fwd;
 #endif
-    const int ntiles = a.gx * tiles_y(a.H);
+    const int P = plan.P, ntiles = plan.ntiles;
     if (ntiles == 0) return 0;
     const dim3 grid(ntiles), block(256);
-    const TileSortArgs ts = tile_sort ? *tile_sort : TileSortArgs{};
     // (P == 0: nothing was preprocessed and the geometry scratch may be NULL)
     const unsigned long long* const prepare = P > 0 ? g.prepare : nullptr;
     const int lines_per_tile = (P + ntiles - 1) / ntiles;
-    if (tile_sort)
+    if (plan.tile_sort_fused)
         hipLaunchKernelGGL(blend_forward_kernel<true>, grid, block, 0, s, a, out_color, out_depth,
                            out_opacity, img.final_T, img.n_contrib, n_touched, img.ranges, sort_err, status, ts, prepare, P,
                            lines_per_tile);
     else
         hipLaunchKernelGGL(blend_forward_kernel<false>, grid, block, 0, s, a, out_color, out_depth,
-                           out_opacity, img.final_T, img.n_contrib, n_touched, img.ranges, sort_err, status, ts, prepare, P,
-                           lines_per_tile);
+                           out_opacity, img.final_T, img.n_contrib, n_touched, img.ranges, sort_err, status, TileSortArgs{}, prepare,
+                           P, lines_per_tile);
     MGS_HIP(hipGetLastError());
     return 0;
 }

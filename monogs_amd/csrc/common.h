@@ -7,6 +7,7 @@
 
 #include "../../include/monogs_raster.h"
 #include "wave_ops.h"          // wave reductions and scans, the reproducible workgroup sums
+#include "forward_plan.h"      // ForwardPlan: the forward's route decisions, read by every stage launcher
 
 namespace mgs {
 
@@ -166,7 +167,7 @@ struct GeometryState {
     size_t band_room;         // bytes from band_totals to the end of perm
     uint8_t* clamped;         // [P][4] SH colour clamp flags
     uint2* rect;              // [P] tile rectangle {x0 | y0 << 16, w | h << 16} (w = h = 0: culled), by Gaussian index; or
-                              //     (depth_sort_payload()) uint32[2 P]: the first half x0 | y0 << 8 | w << 16 | h << 24,
+                              //     (ForwardPlan::rect_packed) uint32[2 P]: the first half x0 | y0 << 8 | w << 16 | h << 24,
                               //     which the depth sort carries along as a payload, the second half its ping-pong partner
     uint2* rect_sorted;       // [P] the same in depth order: written by the last pass of the depth sort, so that the
                               //     scan and duplicate read it coalesced instead of gathering through perm[]
@@ -216,26 +217,16 @@ struct BinningState {
 
 // Items per scan block.  The scan kernels of binning.hip take SCAN_ITEMS Gaussians per workgroup; on the per-tile path
 // preprocess_forward_kernel scans its own 256 Gaussians (SCAN_ITEMS_PRE) and no scan_local launch follows.  Which one a
-// forward uses is decided in ONE place, scan_items(), and travels to the kernels as a shift.
+// forward uses: ForwardPlan::scan_items; it travels to the kernels as a shift.
 constexpr int SCAN_ITEMS = 2048;
 constexpr int SCAN_ITEMS_PRE = 256;      // = the workgroup of preprocess_forward_kernel
 inline int scan_nblocks(int P, int items) { return (P + items - 1) / items; }
-// items per scan block of a forward of P Gaussians at W x H (preprocess, launch_scan, launch_duplicate and the exact path's
-// read-back of the grand total all ask here): SCAN_ITEMS_PRE when preprocess scans (per-tile path, option "pre_scan" not 0)
-int scan_items(int P, int W, int H);
-inline int scan_shift(int items) { return items == SCAN_ITEMS_PRE ? 8 : 11; }
-static_assert(SCAN_ITEMS == 1 << 11 && SCAN_ITEMS_PRE == 1 << 8, "scan_shift");
 
 // Banded tile sort (binning.hip): on the per-tile path, when the tile id is wider than one 8-bit digit and the image has at
 // most TILE_SORT_MAX_BANDS bands of 256 tiles, the instances are emitted already grouped by band (exact counts from
-// preprocess) and ONE segmented 8-bit pass orders each band.  tile_sort_bands() = the number of bands, 0: the plain emission and two passes.
+// preprocess) and ONE segmented 8-bit pass orders each band (ForwardPlan::bands_counted, ForwardPlan::bands).
 constexpr int TILE_BAND_BITS = 8;
 constexpr int TILE_SORT_MAX_BANDS = 32;
-int tile_sort_bands(int P, int W, int H);
-// ... and the render call's half of the decision, once the instance count (or the capacity) R is known: the scratch of the
-// one segmented pass must fit what mgs_binning_bytes() reserves for the two passes (for a few thousand instances it does
-// not: a partial tile per band outweighs them).  0: the plain emission and the two passes, whatever preprocess counted.
-int tile_sort_bands_render(int P, int W, int H, uint64_t R);
 inline size_t band_table_bytes(int P, int bands) { return (64 + (size_t)bands * ((P + 255) / 256)) * sizeof(uint32_t); }
 
 inline int tiles_x(int W) { return (W + TILE - 1) / TILE; }
@@ -255,8 +246,6 @@ constexpr uint32_t DEPTH_KEY_NARROW = (1u << 27) - 1u;
 // (depth27 & (2^lo - 1)) << (32 - lo) | index, with depth27 = min(key - DEPTH_KEY_SUB, DEPTH_KEY_NARROW) and lo = the
 // depth bits that do not fit beside a tile id of tb bits
 __host__ __device__ inline int tile_depth_lo_bits(int tb) { return tb > 5 ? tb - 5 : 0; }
-// 1: the forward orders the Gaussians by depth per tile (no global depth sort); 0: the global depth sort (radix_sort.hip)
-int binning_path(int P, int W, int H);
 
 // ---- error plumbing --------------------------------------------------------------------------
 void set_error(const char* fmt, ...);
@@ -272,7 +261,7 @@ void set_error(const char* fmt, ...);
 // ---- stage launchers (one per translation unit) ------------------------------------------
 struct StageTimer;  // api.hip
 
-int launch_preprocess_forward(const mgs_camera& cam, int P, const float* means3D, const float* shs,
+int launch_preprocess_forward(const ForwardPlan& plan, const mgs_camera& cam, const float* means3D, const float* shs,
                               const float* colors_precomp, const float* opacities, const float* scales,
                               const float* rotations, const float* cov3D_precomp,
                               const GeometryState& g, int32_t* radii, float* prepare_grad_acc, hipStream_t s);
@@ -289,15 +278,11 @@ struct BackwardState {
 };
 // `prepare_grad_acc` (or NULL): the pose part behind the accumulator is cleared by the kernel itself; the accumulator's address is
 // left in g.prepare[0] for the render call that follows, whose blend forward clears the P gradient lines (blend.hip)
-// `rects`: the rectangles in the order the scan runs in (rect_sorted after a depth sort, rect by index on the per-tile path)
-// `items`: scan_items() of this forward; SCAN_ITEMS_PRE: preprocess wrote the block-local sums, only the block sums are scanned
-// `bands`: tile_sort_bands() of this forward (SCAN_ITEMS_PRE only): the launch also scans the band counts along each band
-int launch_scan(const GeometryState& g, int P, hipStream_t s, bool exclusive, const uint2* rects, int items, int bands = 0);
-// `r_cap`: capacity of the binning buffers; `count` (device): [0] live instance count min(R, r_cap), [1] overflow flag
-// `per_tile`: emit in Gaussian-index order with the depth bits packed into the pairs (binning_path() == 1)
-int launch_duplicate(const mgs_camera& cam, int P, const GeometryState& g, const BinningState& b, uint64_t r_cap,
-                     int32_t* n_touched, const ImageState& img, uint64_t sort_n, int sort_bits, uint32_t* count,
-                     uint32_t* overflow, hipStream_t s, bool per_tile);
+// (the scan runs over rect_sorted after a depth sort, over rect by index on the per-tile path)
+int launch_scan(const ForwardPlan& plan, const GeometryState& g, hipStream_t s);
+// `count` (device, capacity mode): [0] live instance count min(R, r_cap), [1] overflow flag
+int launch_duplicate(const ForwardPlan& plan, const GeometryState& g, const BinningState& b, const ImageState& img,
+                     int32_t* n_touched, uint32_t* count, uint32_t* overflow, hipStream_t s);
 size_t sort_temp_bytes(uint64_t n, int bits);
 size_t radix_temp_bytes(uint64_t n, int bits);
 size_t radix_depth_temp_bytes(uint64_t n);
@@ -308,19 +293,25 @@ const uint32_t* radix_depth_error_flag(void* temp, uint64_t n);
 __device__ __forceinline__ uint32_t radix_failed(const uint32_t* __restrict__ e) { return (e[0] | e[1]) | (e[2] | e[3]); }
 void radix_zero_region(void* temp, uint64_t n, int bits, uint32_t** ptr, size_t* words);   // what must be 0 before a sort
 void radix_depth_zero_region(void* temp, uint64_t n, uint32_t** ptr, size_t* words, bool header_only = false);
-// `ext_hist` ([4][256], one-sweep path only): digit counts of the keys already counted by the kernel that produced them
-// -- the sort then launches no histogram kernel.  radix_wants_hist(n) tells the producer whether they will be used.
+struct RadixSortOptions {
+    const uint32_t* n_dev = nullptr;         // the live pair count is read on the device (min(n, *n_dev)); n is the capacity
+    bool temp_zeroed = false;                // the caller cleared radix_zero_region()
+    const uint2* aux_in = nullptr; uint2* aux_out = nullptr;     // last pass also writes aux_out[i] = aux_in[value i]
+    bool aux_empty_for_ones = false;         // a key of all ones gets aux (0, 0) without the fetch
+    const uint32_t* ext_hist = nullptr;      // [4][256], one-sweep path only (radix_size_class(n) != RADIX_COUNTED): digit counts of the keys,
+                                             // counted by the kernel that produced them -- the sort launches no histogram kernel
+    bool exclusive = false;                  // MGS_FLAG_EXCLUSIVE_DEVICE: small sorts may use block ids as tile ids
+    uint2* ranges = nullptr;                 // keys are small integers: ranges[key] = {first, last + 1} sorted position
+                                             // (the final pass: atomicMin / atomicMax on words preset to {~0, 0})
+    int key_shift = 0;                       // the bits sorted are [key_shift, key_shift + bits); ranges are indexed
+                                             // by key >> key_shift, and the final pass keeps the keys
+};
 int radix_sort_pairs(uint32_t* ka, uint32_t* va, uint32_t* kb, uint32_t* vb, uint64_t n, int bits, void* temp,
-                     hipStream_t s, const uint32_t* n_dev = nullptr, bool temp_zeroed = false,
-                     const uint2* aux_in = nullptr, uint2* aux_out = nullptr,   // last pass also writes aux_out[i] = aux_in[value i]
-                     const uint32_t* ext_hist = nullptr,
-                     bool aux_empty_for_ones = false,        // a key of all ones gets aux (0, 0) without the fetch
-                     bool exclusive = false,                 // MGS_FLAG_EXCLUSIVE_DEVICE: small sorts may use block ids as tile ids
-                     uint2* ranges = nullptr,                // keys are small integers: ranges[key] = {first, last + 1} sorted position
-                                                             // (the final pass: atomicMin / atomicMax on words preset to {~0, 0})
-                     int key_shift = 0);                     // the bits sorted are [key_shift, key_shift + bits); ranges are indexed
-                                                             // by key >> key_shift, and the final pass keeps the keys
-bool radix_wants_hist(uint64_t n);
+                     hipStream_t s, const RadixSortOptions& o);
+// The size class of a sort of n pairs, for the forward plan.  RADIX_COUNTED: the counted-tiles path (a payload can travel, no global digit histogram
+// is read).  RADIX_COUNTED_WANTED: the "radix_scanned" knob asks for it, n is too small to be forced onto it: one sweep, but a map that size counts as large.
+enum RadixSizeClass { RADIX_ONE_SWEEP = 0, RADIX_COUNTED_WANTED = 1, RADIX_COUNTED = 2 };
+RadixSizeClass radix_size_class(uint64_t n);
 // Banded tile sort (radix_sort.hip): (ka, va) hold <= 32 independent runs end to end, run b of band_totals[b] pairs (device);
 // ONE counted-tiles pass on key bits [key_shift, key_shift + 8) orders each run into the same positions of (kb, vb) and
 // writes `ranges` (indexed by key >> key_shift).  Scratch: radix_banded_temp_bytes(n, bands), its zero region as for the other sorts.
@@ -329,19 +320,16 @@ void radix_banded_zero_region(void* temp, uint64_t n, int bands, uint32_t** ptr,
 int radix_sort_banded(const uint32_t* ka, const uint32_t* va, uint32_t* kb, uint32_t* vb, uint64_t n, int key_shift, void* temp,
                       hipStream_t s, const uint32_t* n_dev, const uint32_t* band_totals, int bands, uint2* ranges);
 // The forward's first sort (radix_sort.hip): depth keys -> perm + rect_sorted; three 9-bit passes (+ a fourth that only
-// runs for depths beyond 13 107 units).  radix_depth_payload(n): the sort carries the packed rectangles itself.
-bool radix_depth_payload(uint64_t n);
+// runs for depths beyond 13 107 units).  `payload` (ForwardPlan::rect_packed): the sort carries the packed rectangles itself.
 int radix_sort_depth(uint32_t* keys, uint32_t* key_b, uint32_t* val_a, uint32_t* val_b, void* rect, bool payload,
                      uint32_t* perm, uint2* rect_sorted, uint64_t n, void* temp, hipStream_t s, bool temp_zeroed,
                      bool exclusive = false);
-// the packed form needs both tile-grid dimensions to fit a byte
-inline bool depth_sort_payload(int P, int W, int H) { return radix_depth_payload((uint64_t)P) && tiles_x(W) <= 255 && tiles_y(H) <= 255; }
-int launch_depth_sort(const GeometryState& g, int P, bool payload, hipStream_t s, bool exclusive = false);
-int launch_sort(const GeometryState& g, const BinningState& b, uint64_t R, int bits, hipStream_t s,
-                const uint32_t* n_dev = nullptr, bool exclusive = false, uint2* ranges = nullptr, bool per_tile = false,
-                int bands = 0 /* tile_sort_bands() of this forward: one segmented pass behind the banded emission */);
+int launch_depth_sort(const ForwardPlan& plan, const GeometryState& g, hipStream_t s);
+// `n_dev`: capacity mode's live pair count (NULL: plan.R); the final pass writes img.ranges
+int launch_sort(const ForwardPlan& plan, const GeometryState& g, const BinningState& b, const ImageState& img,
+                const uint32_t* n_dev, hipStream_t s);
 // per-tile depth order: each tile's list, grouped by the tile sort in index order, sorted by (depth, index) in place
-// (tile_sort.h) -- by blend_forward_kernel (launch_blend_forward's `tile_sort`) or by a launch of its own
+// (tile_sort.h) -- by blend_forward_kernel (ForwardPlan::tile_sort_fused) or by a launch of its own
 struct TileSortArgs {
     uint32_t* keys;                            // the tile sort's output pairs: read, and the long-list path's ping-pong
     uint32_t* vals;                            // = point_list: the sorted indices are written here in place
@@ -352,21 +340,19 @@ struct TileSortArgs {
     uint32_t n_cap;
     int tb;                                    // tile bits
 };
-TileSortArgs tile_sort_args(const mgs_camera& cam, const GeometryState& g, const BinningState& b, uint64_t R,
-                            const uint32_t* n_dev);
-int launch_tile_depth_sort(const mgs_camera& cam, const TileSortArgs& ts, const ImageState& img, const uint32_t* sort_err,
+TileSortArgs tile_sort_args(const ForwardPlan& plan, const GeometryState& g, const BinningState& b, const uint32_t* n_dev);
+int launch_tile_depth_sort(const ForwardPlan& plan, const TileSortArgs& ts, const ImageState& img, const uint32_t* sort_err,
                            hipStream_t s);
 int set_radix_spin_limit(uint32_t limit);
 extern bool g_opt_blend_bwd_transposed_set;
 extern int g_dbg_last_bwd_split, g_dbg_last_tile_sort_bands;
-extern int g_opt_radix_ballot_rank, g_opt_radix_scanned, g_opt_radix_xcd_band, g_opt_knn_grid_min, g_opt_scan_small, g_opt_pre_scan, g_opt_tile_sort_banded, g_opt_dup_slot_major, g_opt_blend_bwd_transposed, g_opt_blend_bwd_split, g_opt_blend_bwd_split_min, g_opt_blend_bwd_split_frac;      // test knobs (mgs_debug_set_option)
+extern int g_opt_radix_ballot_rank, g_opt_radix_scanned, g_opt_radix_xcd_band, g_opt_knn_grid_min, g_opt_scan_small, g_opt_pre_scan, g_opt_tile_sort_banded, g_opt_tile_sort_fused, g_opt_dup_slot_major, g_opt_blend_bwd_transposed, g_opt_blend_bwd_split, g_opt_blend_bwd_split_min, g_opt_blend_bwd_split_frac;      // test knobs (mgs_debug_set_option)
 // `sort_err`: the tile sort's error words (NULL: nothing was sorted); a raised word empties every tile and sets
-// MGS_STATUS_TILE_SORT_TIMEOUT in *status (what ranges_kernel did until round 4).  `tile_sort` (per-tile depth order, or
-// NULL): every workgroup first sorts its tile's list (tile_sort.h)
-int launch_blend_forward(const mgs_camera& cam, const GeometryState& g, const BinningState& b,
+// MGS_STATUS_TILE_SORT_TIMEOUT in *status (what ranges_kernel did until round 4).  `ts`: read with plan.tile_sort_fused, when
+// every workgroup first sorts its tile's list (tile_sort.h)
+int launch_blend_forward(const ForwardPlan& plan, const mgs_camera& cam, const GeometryState& g, const BinningState& b,
                          const ImageState& img, float* out_color, float* out_depth, float* out_opacity,
-                         int32_t* n_touched, const uint32_t* sort_err, uint32_t* status, const TileSortArgs* tile_sort,
-                         int P, hipStream_t s);
+                         int32_t* n_touched, const uint32_t* sort_err, uint32_t* status, const TileSortArgs& ts, hipStream_t s);
 int launch_blend_backward(const mgs_camera& cam, const GeometryState& g, const BinningState& b,
                           const ImageState& img, const float* dL_dcolor, const float* dL_ddepth, const float* out_color,
                           const float* out_depth, float* grad_acc, bool pose_only, uint64_t num_rendered, hipStream_t s);

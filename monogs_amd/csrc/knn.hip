@@ -231,7 +231,7 @@ void morton_bbox_extend(int P, const float* points, int32_t* bbox, hipStream_t s
 int morton_build(int P, const float* points, const int32_t* bbox, const MortonIndex& k, hipStream_t s, const uint32_t** codes_sorted) {
     const int blocks = (P + KNN_THREADS - 1) / KNN_THREADS;
     hipLaunchKernelGGL(knn_morton_kernel, dim3(blocks), dim3(KNN_THREADS), 0, s, P, points, bbox, k.code_a, k.idx_a);
-    if (int rc = radix_sort_pairs(k.code_a, k.idx_a, k.code_b, k.idx_b, (uint64_t)P, 32, k.sort_temp, s, nullptr)) return rc;
+    if (int rc = radix_sort_pairs(k.code_a, k.idx_a, k.code_b, k.idx_b, (uint64_t)P, 32, k.sort_temp, s, RadixSortOptions{})) return rc;
     const uint32_t* idx_sorted = radix_result_in_b(32) ? k.idx_b : k.idx_a;
     if (codes_sorted) *codes_sorted = radix_result_in_b(32) ? k.code_b : k.code_a;
     hipLaunchKernelGGL(knn_gather_kernel, dim3(blocks), dim3(KNN_THREADS), 0, s, P, points, idx_sorted, k.sorted, k.box_lo, k.box_hi);

@@ -358,7 +358,7 @@ __device__ __forceinline__ uint32_t preprocess_gaussian(const PreArgs& a, const 
     return vis ? (o.rect.y & 0xFFFFu) * (o.rect.y >> 16) : 0u;
 }
 
-// SCAN (per-tile path, scan_items() == SCAN_ITEMS_PRE): the workgroup also writes the block-local inclusive scan of the tiles
+// SCAN (per-tile path, ForwardPlan::scan_items == SCAN_ITEMS_PRE): the workgroup also writes the block-local inclusive scan of the tiles
 // its 256 Gaussians touch to point_offsets[] and its total to scan_blocks[blockIdx.x] -- what scan_local_kernel
 // (binning.hip) computes from the rectangles this kernel has just had in registers, in the same (index) order; one
 // scan_blocks_kernel launch then finishes the scan.
@@ -417,10 +417,11 @@ __global__ void __launch_bounds__(256) preprocess_forward_kernel(PreArgs a) {
     }
 }
 
-int launch_preprocess_forward(const mgs_camera& cam, int P, const float* means3D, const float* shs,
+int launch_preprocess_forward(const ForwardPlan& plan, const mgs_camera& cam, const float* means3D, const float* shs,
                               const float* colors_precomp, const float* opacities, const float* scales,
                               const float* rotations, const float* cov3D_precomp, const GeometryState& g,
                               int32_t* radii, float* prepare_grad_acc, hipStream_t s) {
+    const int P = plan.P;
     PreArgs a;
     a.means3D = means3D; a.shs = shs; a.colors = colors_precomp; a.opacities = opacities;
     a.scales = scales; a.rotations = rotations; a.cov3D = cov3D_precomp;
@@ -440,18 +441,15 @@ int launch_preprocess_forward(const mgs_camera& cam, int P, const float* means3D
     if (P == 0) return 0;
     // per-tile depth order: no depth sort follows -- the scan and duplicate read the rectangles {x0 | y0 << 16, w | h << 16}
     // by index, and of the depth sort's scratch only the header (its error words, which the consumers check) is cleared
-    const bool per_tile = binning_path(P, cam.image_width, cam.image_height) != 0;
-    a.rect_packed = (!per_tile && depth_sort_payload(P, cam.image_width, cam.image_height)) ? 1 : 0;
-    radix_depth_zero_region(g.sort_temp, (uint64_t)P, &a.zero_ptr, &a.zero_words, per_tile);
+    a.rect_packed = plan.rect_packed ? 1 : 0;
+    radix_depth_zero_region(g.sort_temp, (uint64_t)P, &a.zero_ptr, &a.zero_words, plan.per_tile);
     // + the two small tables carved right in front of it (scan status words, tile-sort digit counts)
     a.zero_words += (size_t)((char*)a.zero_ptr - (char*)g.scan_status) / 4;
     a.zero_ptr = (uint32_t*)g.scan_status;
     const dim3 grid((P + 255) / 256), block(256);
-    // the scan folded in (see the kernel): the same host-side decision launch_scan and launch_duplicate take
-    const bool scan = scan_items(P, cam.image_width, cam.image_height) == SCAN_ITEMS_PRE;
+    const bool scan = plan.scan_items == SCAN_ITEMS_PRE;      // the scan folded in (see the kernel)
     a.point_offsets = g.point_offsets; a.scan_blocks = g.scan_blocks;
-    // banded tile sort: the same host-side decision launch_scan, launch_duplicate and launch_sort take
-    a.nbands = tile_sort_bands(P, cam.image_width, cam.image_height);
+    a.nbands = plan.bands_counted;                            // banded tile sort: the kernel counts them
     a.band_counts = a.nbands ? g.band_counts : nullptr;
     // (the tables lie over the global depth sort's four idle u32[P] buffers: P / 2 + 256 bytes against >= 16 P)
     if (a.nbands && band_table_bytes(P, a.nbands) > g.band_room) { set_error("band tables do not fit the geometry scratch"); return 1; }

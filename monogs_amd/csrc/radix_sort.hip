@@ -118,16 +118,12 @@ static inline bool rs_scanned(uint64_t n) {
     return n > RS_ONE_SWEEP_MAX;
 }
 
-// Which depth order the forward builds (binning.hip): 1 = per tile (tile_depth_sort_kernel) wherever the map's depth sort
-// would take the counted-tiles path -- or at any size when the radix_scanned knob is 1 -- and the tile sort's keys have
-// room for the high depth bits beside a tile id of <= 16 bits, the values for the low ones beside the index:
-// P <= 2^(37 - tile bits).  0 = the global depth sort (one sweep, or counted tiles with the knob at 0).
-int binning_path(int P, int W, int H) {
-    if (P <= 0) return 0;
-    const bool large = g_opt_radix_scanned >= 0 ? g_opt_radix_scanned == 1 : (uint64_t)P > RS_ONE_SWEEP_MAX;
-    const int tb = tile_bits(W, H);
-    if (!large || tb > 16) return 0;
-    return (uint64_t)P <= (1ull << (32 - tile_depth_lo_bits(tb))) ? 1 : 0;
+// What the forward plan asks (common.h).  "Large" -- where the forward orders by depth per tile -- is wherever the sort would
+// take the counted-tiles path, or at ANY size when the radix_scanned knob is 1: rs_scanned additionally needs n > RS_SCANNED_MIN.
+RadixSizeClass radix_size_class(uint64_t n) {
+    if (rs_scanned(n)) return RADIX_COUNTED;
+    const bool large = g_opt_radix_scanned >= 0 ? g_opt_radix_scanned == 1 : n > RS_ONE_SWEEP_MAX;
+    return large ? RADIX_COUNTED_WANTED : RADIX_ONE_SWEEP;
 }
 // Pairs per thread.  On the counted-tiles path a tile lives ~10-20 us and the kernel ends when the last one does: if the
 // tiles do not all fit on the chip at once, the stragglers start when the first ones retire and the pass takes two tile
@@ -1028,11 +1024,6 @@ void radix_depth_zero_region(void* temp, uint64_t n, uint32_t** ptr, size_t* wor
     *words = header_only ? (size_t)((char*)t.status - (char*)t.hist) / 4 : t.zero_bytes / 4;
 }
 
-// does a sort of n pairs read a global digit histogram (one-sweep path) -- i.e. is it worth counting one while the keys are produced?
-bool radix_wants_hist(uint64_t n) { return n > 0 && !rs_scanned(n); }
-// does the depth sort of n Gaussians carry the rectangle as a payload (else it gathers it in its final pass)?
-bool radix_depth_payload(uint64_t n) { return n > 0 && rs_scanned(n); }
-
 template <int ITEMS, int DB, bool SCANNED, bool PAYLOAD>
 static void rs_launch_pass(const RsPassArgs& a, uint32_t tiles, bool ballot, hipStream_t s) {
     if (ballot && DB == 8 && !PAYLOAD && a.vin != nullptr)
@@ -1156,19 +1147,18 @@ static int rs_run(const RsPlan& pl, const RsBuffers& b, uint64_t n, void* temp, 
 }
 
 int radix_sort_pairs(uint32_t* ka, uint32_t* va, uint32_t* kb, uint32_t* vb, uint64_t n, int bits, void* temp,
-                     hipStream_t s, const uint32_t* n_dev, bool temp_zeroed, const uint2* aux_in, uint2* aux_out,
-                     const uint32_t* ext_hist, bool aux_empty_for_ones, bool exclusive, uint2* ranges, int key_shift) {
+                     hipStream_t s, const RadixSortOptions& o) {
     RsPlan pl = rs_plan_plain(bits);
-    for (int p = 0; p < RS_MAX_PASSES; ++p) pl.shift[p] += key_shift;      // (same passes, same scratch, same result side)
+    for (int p = 0; p < RS_MAX_PASSES; ++p) pl.shift[p] += o.key_shift;    // (same passes, same scratch, same result side)
     if (pl.npasses > RS_MAX_PASSES) { set_error("radix sort: more than 32 key bits"); return 1; }
     RsBuffers b;
-    b.ranges = ranges;
+    b.ranges = o.ranges;
     b.ka = ka; b.va = va; b.va_is_index = false; b.pa = nullptr; b.kb = kb; b.vb = vb; b.pb = nullptr; b.kfinal = nullptr; b.vfinal = nullptr;
-    b.aux_in = aux_in; b.aux_out = aux_out; b.aux_skip_ones = aux_empty_for_ones;
-    return rs_run(pl, b, n, temp, s, n_dev, temp_zeroed, ext_hist, exclusive, key_shift);
+    b.aux_in = o.aux_in; b.aux_out = o.aux_out; b.aux_skip_ones = o.aux_empty_for_ones;
+    return rs_run(pl, b, n, temp, s, o.n_dev, o.temp_zeroed, o.ext_hist, o.exclusive, o.key_shift);
 }
 
-// ---- banded tile sort (binning.hip, tile_sort_bands()): the pairs arrive grouped by band of 256 tiles -- band b's
+// ---- banded tile sort (binning.hip, ForwardPlan::bands): the pairs arrive grouped by band of 256 tiles -- band b's
 // band_totals[b] pairs (a device table: the host never learns the sizes) behind those of the bands before it -- so the 8 key
 // bits from key_shift up order each band completely: ONE counted-tiles pass, run as <= 32 independent sorts in one
 // rs_tile_hist + one rs_pass launch.  Band b has ceil(n_b / tile) sort tiles of its own, only the last one partial; the grids

@@ -1,4 +1,4 @@
-// Per-tile depth sort (binning_path() == 1: large maps), shared by binning.hip (tile_depth_sort_kernel) and blend.hip
+// Per-tile depth sort (ForwardPlan::per_tile: large maps), shared by binning.hip (tile_depth_sort_kernel) and blend.hip
 // (blend_forward_kernel<true>, which sorts its own tile before walking it).
 //
 // Instead of a global depth sort of all P Gaussians (three or four counted-tiles passes: ~105 us at C5, 2 M Gaussians),

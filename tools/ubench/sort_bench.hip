@@ -75,7 +75,7 @@ int main(int argc, char** argv) {
     uint32_t *ka, *va, *kb, *vb, *perm;
     uint2 *aux_in, *aux_out;
     void* temp;
-    const bool payload = depth && mgs::radix_depth_payload(n);
+    const bool payload = depth && mgs::radix_size_class(n) == mgs::RADIX_COUNTED;
     const size_t tb = depth ? mgs::radix_depth_temp_bytes(n) : mgs::radix_temp_bytes(n, bits);
     CK(hipMalloc(&perm, n * 4));
     CK(hipMalloc(&ka, n * 4)); CK(hipMalloc(&va, n * 4)); CK(hipMalloc(&kb, n * 4)); CK(hipMalloc(&vb, n * 4));
@@ -96,7 +96,7 @@ int main(int argc, char** argv) {
     };
     auto sort = [&]() {
         if (depth) return mgs::radix_sort_depth(ka, kb, va, vb, aux_in, payload, perm, aux_out, n, temp, s, false);
-        return mgs::radix_sort_pairs(ka, va, kb, vb, n, bits, temp, s, nullptr, false, nullptr, nullptr, nullptr, false);
+        return mgs::radix_sort_pairs(ka, va, kb, vb, n, bits, temp, s, mgs::RadixSortOptions{});
     };
     // ---- correctness against std::stable_sort
     upload();
@@ -150,7 +150,7 @@ int main(int argc, char** argv) {
         CK(hipMemsetAsync(htrace, 0, (size_t)tiles * 32, s));
         if (which == 1 && depth) break;     // (the depth plan has no one-pass form)
         int rc = which == 0 ? sort()
-                            : mgs::radix_sort_pairs(ka, va, kb, vb, n, 8, temp, s, nullptr, false, nullptr, nullptr, nullptr, false);
+                            : mgs::radix_sort_pairs(ka, va, kb, vb, n, 8, temp, s, mgs::RadixSortOptions{});
         if (rc) return 1;
         CK(hipStreamSynchronize(s));
         std::vector<uint64_t> tr((size_t)tiles * 8);
