@@ -17,7 +17,7 @@ import torch
 from . import _lib, fused_losses
 from .map_step import render_map
 from .pose_optim import PoseAdam
-from .rasterizer import _device_guard, _stream
+from ._launch import _device_guard, _stream
 
 NAMES = ("fx", "fy", "cx", "cy")
 # Default learning rates, in pixels per step per pixel of image width (Adam's step is about one learning rate while the gradient

@@ -43,7 +43,7 @@ def fused_camera_matrices(R: torch.Tensor, t: torch.Tensor, projmatrix_raw: torc
     ``out``: three existing tensors to write into (a loop whose pose step keeps them current -- ``PoseAdam.step_and_retract(camera=...)`` --
     computes them once per frame, not once per render)."""
     from . import _lib
-    from .rasterizer import _stream, _device_guard
+    from ._launch import _stream, _device_guard
     lib = _lib.load()
     f = lambda x: x.detach().to(torch.float32).contiguous()  # noqa: E731
     R, t, Pm = f(R), f(t), f(projmatrix_raw)

@@ -10,7 +10,8 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .rasterizer import _camera, _f32, _ptr, _stream, _device_guard
+from ._launch import _f32, _ptr, _stream, _device_guard
+from .rasterizer import _camera
 
 _FLOAT_TABLES = ("geometry.rec", "image.final_T", "backward.grad_acc", "backward.tau_part", "backward.tau")
 

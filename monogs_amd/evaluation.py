@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .rasterizer import _f32, _stream, _device_guard
+from ._launch import _f32, _stream, _device_guard
 from .ssim import C1 as SSIM_C1, C2 as SSIM_C2
 
 

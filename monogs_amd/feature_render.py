@@ -20,10 +20,10 @@ from typing import Optional
 import torch
 
 from . import _lib
-from .rasterizer import (ForwardScratch, GaussianRasterizationSettings, GaussianRasterizer, _device_guard, _ptr, _stream,
-                         forward_scratch)
+from ._launch import _device_guard, _ptr, _stream
+from .rasterizer import ForwardScratch, GaussianRasterizationSettings, GaussianRasterizer, forward_scratch
 
-MAX_FEATURE_CHANNELS = 256          # MGS_MAX_FEATURE_CHANNELS
+MAX_FEATURE_CHANNELS = _lib.H.MGS_MAX_FEATURE_CHANNELS
 
 
 def _check(t: ForwardScratch, features, bg) -> int:

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .rasterizer import _device_guard, _stream
+from ._launch import _device_guard, _stream
 
 EDGE_THRESHOLD = 1.1      # camera_utils.py:185
 GRAD_EPS = 0.01           # slam_utils.py:26

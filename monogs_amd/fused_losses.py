@@ -16,12 +16,11 @@ from __future__ import annotations
 import torch
 
 from . import _lib
-from .rasterizer import _f32, _stream, _device_guard
+from ._launch import _f32, _stream, _device_guard
 
 
-_TRACKING, _INVERT, _RGB_ONLY = 1, 2, 4     # MGS_LOSS_TRACKING, MGS_LOSS_INVERT_DEPTH, MGS_LOSS_RGB_ONLY (include/monogs_raster.h)
-_DAB = 10     # MGS_LOSS_SCRATCH_DAB
-_LOSS = 12    # MGS_LOSS_SCRATCH_LOSS
+_TRACKING, _INVERT, _RGB_ONLY = _lib.H.MGS_LOSS_TRACKING, _lib.H.MGS_LOSS_INVERT_DEPTH, _lib.H.MGS_LOSS_RGB_ONLY
+_DAB, _LOSS = _lib.H.MGS_LOSS_SCRATCH_DAB, _lib.H.MGS_LOSS_SCRATCH_LOSS        # float indices into the loss scratch
 
 
 def _u8(t):
@@ -181,7 +180,7 @@ def loss_grads(render_image, render_depth, render_opacity, viewpoint, tracking: 
 
 
 # ---- colour refinement: (1 - lambda) L1 + lambda (1 - SSIM) ------------------------------------------------------------------
-_R_LOSS, _R_L1, _R_SSIM = 0, 1, 2     # MGS_SSIM_SCRATCH_LOSS / _L1 / _SSIM (include/monogs_raster.h)
+_R_LOSS, _R_L1, _R_SSIM = _lib.H.MGS_SSIM_SCRATCH_LOSS, _lib.H.MGS_SSIM_SCRATCH_L1, _lib.H.MGS_SSIM_SCRATCH_SSIM
 
 
 def _refine_inputs(image, gt_image):

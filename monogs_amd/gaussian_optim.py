@@ -13,7 +13,7 @@ from typing import Sequence
 import torch
 
 from . import _lib
-from .rasterizer import _stream, _device_guard, _ptr
+from ._launch import _stream, _device_guard, _ptr
 
 
 class GaussianAdam:

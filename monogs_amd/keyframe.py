@@ -30,7 +30,7 @@ import torch
 
 from . import _lib
 from .knn import distCUDA2
-from .rasterizer import _stream, _device_guard
+from ._launch import _stream, _device_guard
 
 
 def densification_mask(gt_depth: torch.Tensor, render_depth: Optional[torch.Tensor], render_opacity: Optional[torch.Tensor],

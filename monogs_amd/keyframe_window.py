@@ -25,7 +25,7 @@ import torch
 
 from . import _lib
 from . import window as W
-from .rasterizer import _device_guard, _stream
+from ._launch import _device_guard, _stream
 
 MAX_KEYFRAMES = 32
 

@@ -8,7 +8,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib
-from .rasterizer import _stream, _device_guard
+from ._launch import _stream, _device_guard
 
 
 def distCUDA2(points: torch.Tensor) -> torch.Tensor:

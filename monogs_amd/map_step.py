@@ -13,7 +13,8 @@ import torch
 from . import _lib
 from .gaussian_map import GaussianMap
 from .gaussian_optim import activate, activate_backward_into, activate_into
-from .rasterizer import GaussianRasterizer, _device_guard, _stream
+from ._launch import _device_guard, _stream
+from .rasterizer import GaussianRasterizer
 from .renderer import raster_settings, render
 
 

@@ -47,7 +47,7 @@ from .gaussian_optim import fan_out, window_stats
 from .map_step import MapStep, rasterize, render_map      # noqa: F401  (render_map: re-exported, tests and tools import it from here)
 from .monocular import window_is_monocular
 from .pose_optim import PoseAdam
-from .rasterizer import _device_guard, _stream
+from ._launch import _device_guard, _stream
 
 BUCKET_COLS = 16          # floats per Gaussian in the exchange bucket (see the module docstring)
 _GRAD_COLS = 14

@@ -24,7 +24,7 @@ import torch
 
 from . import _lib
 from .frames import Viewpoint
-from .rasterizer import _device_guard, _stream
+from ._launch import _device_guard, _stream
 
 PSEUDO_DEPTH_DEFAULTS = dict(init_mean=2.0, init_sigma=0.3, opacity_min=0.95, sigma_in=0.2, sigma_out=0.5)
 

@@ -20,10 +20,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from .rasterizer import _device_guard, _f32, _ptr, _stream
+from ._launch import _device_guard, _f32, _ptr, _stream
 
-MAX_OBJECTS = 256           # MGS_MAX_FEATURE_CHANNELS: ids are 8-bit
-_LOSS = 0                   # MGS_LABEL_SCRATCH_LOSS (a float index)
+MAX_OBJECTS = _lib.H.MGS_MAX_FEATURE_CHANNELS           # ids are 8-bit
+_LOSS = _lib.H.MGS_LABEL_SCRATCH_LOSS                   # a float index
 
 
 def _no_cpu(t, what):

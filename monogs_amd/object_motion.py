@@ -23,10 +23,11 @@ from . import _lib
 from . import camera as cam
 from . import fused_losses
 from .gaussian_map import object_labels
-from .rasterizer import GaussianRasterizer, _device_guard, _f32, _ptr, _stream
+from ._launch import _device_guard, _f32, _ptr, _stream
+from .rasterizer import GaussianRasterizer
 from .renderer import raster_settings
 
-MAX_MOVING_OBJECTS = 16       # MGS_MAX_MOVING_OBJECTS
+MAX_MOVING_OBJECTS = _lib.H.MGS_MAX_MOVING_OBJECTS
 
 
 def _check_ids(ids) -> List[int]:

@@ -19,9 +19,10 @@ import torch
 
 from . import _lib
 from .fused_losses import _RGB_ONLY, _TRACKING, _u8
-from .rasterizer import _device_guard, _f32, _stream, forward_scratch
+from ._launch import _device_guard, _f32, _stream
+from .rasterizer import forward_scratch
 
-SYSTEM_DOUBLES = 75          # MGS_GN_SYSTEM_DOUBLES: H[8][8], g[8], E, N_rgb, N_d
+SYSTEM_DOUBLES = _lib.H.MGS_GN_SYSTEM_DOUBLES          # H[8][8], g[8], E, N_rgb, N_d
 
 
 @torch.no_grad()

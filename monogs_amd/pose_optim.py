@@ -10,7 +10,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib
-from .rasterizer import _stream, _device_guard
+from ._launch import _stream, _device_guard
 
 
 class PoseAdam:
@@ -117,7 +117,7 @@ class PoseGaussNewton:
     function ``PoseAdam``'s step uses and adds ``x[6:8]`` to the exposure -- one single-wave launch, no host synchronisation
     unless ``sync``.  ``fix_exposure``: the 6 x 6 pose block only.  ``sticky``: once converged, further steps are no-ops.
     The reference has no counterpart (its tracker is Adam, /root/reference/utils/slam_tracker.py:113-176)."""
-    STICKY, FIX_EXPOSURE = 1, 2        # MGS_POSE_STICKY, MGS_GN_FIX_EXPOSURE
+    STICKY, FIX_EXPOSURE = _lib.H.MGS_POSE_STICKY, _lib.H.MGS_GN_FIX_EXPOSURE
 
     def __init__(self, viewpoint, lam=1e-3, lam_abs=0.0, max_rot=0.05, max_trans=0.05, fix_exposure=False, sticky=False):
         self.vp = viewpoint

@@ -23,8 +23,11 @@ from typing import List, Optional, Tuple
 
 import torch
 
+from ._lib import H
+
 HINTS_MAX, PENDING_MAX = 64, 1024
-STATUS_CAPACITY_OVERFLOW, STATUS_DEPTH_SORT_TIMEOUT, STATUS_TILE_SORT_TIMEOUT = 1, 2, 4     # MGS_STATUS_* (monogs_raster.h)
+STATUS_CAPACITY_OVERFLOW, STATUS_DEPTH_SORT_TIMEOUT = H.MGS_STATUS_CAPACITY_OVERFLOW, H.MGS_STATUS_DEPTH_SORT_TIMEOUT
+STATUS_TILE_SORT_TIMEOUT = H.MGS_STATUS_TILE_SORT_TIMEOUT
 _TIMEOUTS = STATUS_DEPTH_SORT_TIMEOUT | STATUS_TILE_SORT_TIMEOUT
 
 

@@ -18,6 +18,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._launch import _device_guard, _f32, _ptr, _raw_stream, _stream  # noqa: F401  (re-exported: tests and tools import them here)
 from .raster_status import (GraphFlags, StatusLedger, STATUS_CAPACITY_OVERFLOW,  # noqa: F401  (re-exported)
                             STATUS_DEPTH_SORT_TIMEOUT, STATUS_TILE_SORT_TIMEOUT)
 
@@ -148,27 +149,14 @@ def collect_timing():
         _timing_sink = prev
 
 
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else t.data_ptr()
-
-
 def _al(n: int) -> int:
     return (int(n) + 255) // 256 * 256
-
-
-def _f32(t: torch.Tensor, name: str) -> torch.Tensor:
-    if not t.is_cuda:
-        raise RuntimeError(f"{name} must be a CUDA/HIP tensor (got device {t.device}); "
-                           "the rasteriser has no CPU path")
-    if t.dtype != torch.float32:
-        raise RuntimeError(f"{name} must be float32 (got {t.dtype})")
-    return t.contiguous()
 
 
 def _camera(rs: GaussianRasterizationSettings, sh_coeffs: int, keep: list, scale_dim: int = 3) -> _lib.MgsCamera:
     cam = _lib.MgsCamera()
     cam.scale_dim = int(scale_dim)
-    cam.flags = 1 if _call_flags["exclusive"] else 0            # MGS_FLAG_EXCLUSIVE_DEVICE
+    cam.flags = _lib.FLAG_EXCLUSIVE_DEVICE if _call_flags["exclusive"] else 0
     cam.image_height, cam.image_width = int(rs.image_height), int(rs.image_width)
     cam.tanfovx, cam.tanfovy = float(rs.tanfovx), float(rs.tanfovy)
     cam.scale_modifier = float(rs.scale_modifier)
@@ -178,41 +166,6 @@ def _camera(rs: GaussianRasterizationSettings, sh_coeffs: int, keep: list, scale
         keep.append(t)
         setattr(cam, field, t.data_ptr())
     return cam
-
-
-_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-
-
-class _device_guard:
-    """``with _device_guard(dev)`` for the common case.  The stock context manager spends ~45 us per use in this
-    torch build (``_get_device_index`` consults the environment on entry and exit); five uses per render + loss +
-    backward were ~0.2 ms of host time per iteration (tools/host_overhead.py).  Here nothing happens unless ``dev``
-    is not the current device."""
-    __slots__ = ("idx", "prev")
-
-    def __init__(self, dev):
-        idx = getattr(dev, "index", dev)
-        self.idx = torch._C._cuda_getDevice() if idx is None else int(idx)
-
-    def __enter__(self):
-        self.prev = torch._C._cuda_getDevice()
-        if self.prev != self.idx:
-            torch._C._cuda_setDevice(self.idx)
-        return self
-
-    def __exit__(self, *exc):
-        if self.prev != self.idx:
-            torch._C._cuda_setDevice(self.prev)
-        return False
-
-
-def _stream():
-    """Raw handle of the caller's current stream.  torch.cuda.current_stream() costs ~40 us per call in this torch
-    build (environment lookups inside _get_device_index) -- four calls per render + backward; the C-level accessor
-    is ~100x cheaper (tools/host_overhead.py)."""
-    if _raw_stream is not None:
-        return _raw_stream(torch._C._cuda_getDevice())
-    return torch.cuda.current_stream().cuda_stream
 
 
 class _RasterizeGaussians(torch.autograd.Function):
@@ -466,7 +419,7 @@ def _blend_counters(color, symbol: str, words: int) -> list:
 def debug_blend_stats(color: torch.Tensor) -> dict:
     """Diagnostic: what the blend backward of the forward that produced ``color`` walks, fetches and reduces
     (``mgs_debug_blend_stats``; call before ``backward()`` frees the saved scratch).  Synchronises."""
-    v = _blend_counters(color, "mgs_debug_blend_stats", 24)                  # MGS_BLEND_STATS_WORDS
+    v = _blend_counters(color, "mgs_debug_blend_stats", _lib.H.MGS_BLEND_STATS_WORDS)
     groups = {}
     for d, name in enumerate(("halves_8x4", "halves_4x8", "blocks_4x4", "strips_8x2", "blocks_4x2")):
         groups[name] = dict(trips_paired_per_step=v[8 + 3 * d], rows=v[9 + 3 * d], trips_own_lists=v[10 + 3 * d])
@@ -478,7 +431,7 @@ def debug_blend_mask_stats(color: torch.Tensor) -> dict:
     """Diagnostic: the survivor masks the blend forward that produced ``color`` left for its backward, against the cull the
     backward would run for itself (``mgs_debug_blend_mask_stats``; call before ``backward()`` frees the saved scratch).
     Synchronises."""
-    v = _blend_counters(color, "mgs_debug_blend_mask_stats", 4)              # MGS_BLEND_MASK_STATS_WORDS
+    v = _blend_counters(color, "mgs_debug_blend_mask_stats", _lib.H.MGS_BLEND_MASK_STATS_WORDS)
     return dict(steps=v[0], own_cull=v[1], forward_masks=v[2], missing=v[3])
 
 

@@ -31,7 +31,7 @@ import torch
 from . import _lib, camera as cam, fused_losses, rasterizer as _rast
 from .gaussian_map import GaussianMap
 from .map_step import MapStep, rasterize
-from .rasterizer import _device_guard, _stream
+from ._launch import _device_guard, _stream
 
 
 class _Buffers:

@@ -12,9 +12,9 @@ from __future__ import annotations
 import torch
 
 from . import _lib
-from .rasterizer import _f32, _stream, _device_guard
+from ._launch import _f32, _stream, _device_guard
 
-C1, C2 = 0.01 ** 2, 0.03 ** 2          # MGS_SSIM_C1, MGS_SSIM_C2 (include/monogs_raster.h)
+C1, C2 = _lib.H.MGS_SSIM_C1, _lib.H.MGS_SSIM_C2          # 0.01 ** 2 and 0.03 ** 2: the same float32 bits
 WINDOW = 11
 
 

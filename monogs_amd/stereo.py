@@ -26,7 +26,7 @@ import torch
 from . import _lib
 from .dataset import load_config, quaternion_pose
 from .frame_ingest import _host_array, grad_mask, grad_mask_scratch
-from .rasterizer import _device_guard, _stream
+from ._launch import _device_guard, _stream
 
 EUROC_BF = 47.90639384423901      # baseline x fx of the rectified EuRoC pair (dataset.py:610, "following ORB-SLAM2")
 MATCHER_KEYS = ("num_disparities", "block_size", "uniqueness_ratio", "p1", "p2", "disp12_max_diff", "pre_filter_cap", "bf")

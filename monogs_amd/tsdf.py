@@ -14,7 +14,7 @@ import torch
 
 from . import _lib
 from .camera import cached_camera_tensors, fused_camera_matrices
-from .rasterizer import _device_guard, _f32, _stream
+from ._launch import _device_guard, _f32, _stream
 
 
 class TriangleMesh(NamedTuple):

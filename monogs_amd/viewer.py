@@ -28,11 +28,13 @@ import torch
 from . import _lib
 from .camera import fused_camera_matrices
 from .gaussian_map import object_labels
-from .rasterizer import GaussianRasterizer, _device_guard, _ptr, _stream, forward_scratch
+from ._launch import _device_guard, _ptr, _stream
+from .rasterizer import GaussianRasterizer, forward_scratch
 from .renderer import raster_settings
 
 MODES = ("rgb", "segmentation", "depth", "time", "elipsoids")
-_COMPOSE_MODE = dict(rgb=0, segmentation=0, depth=1, time=2, elipsoids=3)          # MGS_VIEWER_*
+_COMPOSE_MODE = dict(rgb=_lib.H.MGS_VIEWER_RGB, segmentation=_lib.H.MGS_VIEWER_RGB, depth=_lib.H.MGS_VIEWER_DEPTH, time=_lib.H.MGS_VIEWER_TIME,
+                     elipsoids=_lib.H.MGS_VIEWER_ELLIPSOIDS)
 ELLIPSOID_THRESHOLD = 0.4            # gau_frag.glsl:30-33
 NEAR = 0.2                           # the rasteriser's near plane: segments are clipped against z >= NEAR
 GUARD = 1024.0                       # segments are clipped to the image grown by this many pixels before quantisation

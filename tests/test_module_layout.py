@@ -82,3 +82,35 @@ def test_the_dataset_readers_do_not_load_the_harness():
             "sys.exit(1 if 'monogs_amd.slam_harness' in sys.modules else 0)")
     r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
+
+
+def test_the_call_helpers_live_in_launch():
+    """``_stream``, ``_device_guard``, ``_ptr`` and ``_f32`` have nothing to do with rasterisation: every module takes them from
+    ``_launch``; only ``rasterizer`` itself names them (it re-exports them for tests and tools)."""
+    helpers = {"_stream", "_device_guard", "_ptr", "_f32"}
+    for path in sorted(glob.glob(os.path.join(PKG, "*.py"))):
+        if os.path.basename(path) == "rasterizer.py":
+            continue
+        with open(path) as f:
+            tree = ast.parse(f.read())
+        for node in ast.walk(tree):
+            if isinstance(node, ast.ImportFrom) and (node.module or "").split(".")[-1] == "rasterizer":
+                assert not helpers & {a.name for a in node.names}, (path, node.lineno)
+    import monogs_amd._launch
+    import monogs_amd.rasterizer
+    for name in sorted(helpers | {"_raw_stream"}):
+        assert getattr(monogs_amd.rasterizer, name) is getattr(monogs_amd._launch, name), name
+    assert monogs_amd.rasterizer._camera.__module__ == "monogs_amd.rasterizer"
+
+
+def test_the_binding_does_not_import_torch():
+    for name in ("_lib.py", "_header.py"):
+        with open(os.path.join(PKG, name)) as f:
+            names = list(_imported_names(ast.parse(f.read())))
+        assert not [n for n in names if n.split(".")[0] == "torch"], name
+
+
+def test_knn_does_not_load_the_rasteriser():
+    code = "import sys; import monogs_amd.knn; sys.exit(1 if 'monogs_amd.rasterizer' in sys.modules else 0)"
+    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
