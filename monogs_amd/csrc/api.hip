@@ -117,9 +117,7 @@ size_t ImageState::bytes(int W, int H) { Carver<ImageState> c(nullptr); image_la
 size_t BinningState::bytes(uint64_t R, int W, int H) { Carver<BinningState> c(nullptr); binning_layout(R, W, H, c); return c.bytes(); }
 size_t BackwardState::bytes(int P) { Carver<BackwardState> c(nullptr); backward_layout(P, c); return c.bytes(); }
 
-// the three scratches of a finished (or running) forward, carved together
-struct ForwardStates { GeometryState g; ImageState img; BinningState b; };
-static ForwardStates carve_forward(const void* geometry, const void* binning, const void* image, int P, uint64_t R, int W, int H) {
+ForwardStates carve_forward(const void* geometry, const void* binning, const void* image, int P, uint64_t R, int W, int H) {
     return {GeometryState::carve(const_cast<void*>(geometry), P), ImageState::carve(const_cast<void*>(image), W, H),
             BinningState::carve(const_cast<void*>(binning), R, W, H)};
 }
@@ -149,23 +147,29 @@ struct StageTimer {
     }
 };
 
-static int check_cam(const mgs_camera* cam) {
-    if (!cam) { set_error("camera is NULL"); return 1; }
-    if (cam->image_width <= 0 || cam->image_height <= 0) { set_error("image size must be positive"); return 1; }
+// the checks every entry point that takes a camera and a map makes first (common.h); `who`: the text's prefix, or NULL
+static void entry_error(const char* who, const char* text) {
+    if (who) set_error("%s: %s", who, text);
+    else set_error("%s", text);
+}
+
+int check_cam(const mgs_camera* cam, const char* who) {
+    if (!cam) { entry_error(who, "camera is NULL"); return 1; }
+    if (cam->image_width <= 0 || cam->image_height <= 0) { entry_error(who, "image size must be positive"); return 1; }
     if (!cam->bg || !cam->viewmatrix || !cam->projmatrix || !cam->projmatrix_raw || !cam->campos) {
-        set_error("camera tensors (bg, viewmatrix, projmatrix, projmatrix_raw, campos) must be non-NULL");
+        entry_error(who, "camera tensors (bg, viewmatrix, projmatrix, projmatrix_raw, campos) must be non-NULL");
         return 1;
     }
     return 0;
 }
 
-// the blend backward forms `index * 64 + slot` in 32 bits (blend.hip, bt_flush): refuse maps it cannot address
 // mgs_debug_set_blend_events: recorded around the blend forward / backward launch of every call while set
 static hipEvent_t g_dbg_fwd_events[2] = {nullptr, nullptr}, g_dbg_bwd_events[2] = {nullptr, nullptr};
 
-static int check_map_size(int32_t P) {
+// the blend backward forms `index * 64 + slot` in 32 bits (blend.hip, bt_flush): refuse maps it cannot address
+int check_map_size(int32_t P, const char* who) {
     if (P > MGS_MAX_GAUSSIANS) {
-        set_error("P exceeds MGS_MAX_GAUSSIANS (2^26 - 1): the gradient-line offset of the blend backward is 32-bit");
+        entry_error(who, "P exceeds MGS_MAX_GAUSSIANS (2^26 - 1): the gradient-line offset of the blend backward is 32-bit");
         return 1;
     }
     return 0;

@@ -247,6 +247,10 @@ constexpr uint32_t DEPTH_KEY_NARROW = (1u << 27) - 1u;
 // depth bits that do not fit beside a tile id of tb bits
 __host__ __device__ inline int tile_depth_lo_bits(int tb) { return tb > 5 ? tb - 5 : 0; }
 
+// the three scratches of a finished (or running) forward, carved together (api.hip)
+struct ForwardStates { GeometryState g; ImageState img; BinningState b; };
+ForwardStates carve_forward(const void* geometry, const void* binning, const void* image, int P, uint64_t R, int W, int H);
+
 // ---- error plumbing --------------------------------------------------------------------------
 void set_error(const char* fmt, ...);
 #define MGS_HIP(expr)                                                                     \
@@ -257,6 +261,12 @@ void set_error(const char* fmt, ...);
             return 2;                                                                     \
         }                                                                                 \
     } while (0)
+
+// The first checks of an entry point that takes a camera and a map (api.hip); 1 with the error set.  `who`: the entry point's
+// name, put in front of the text ("who: text"), or NULL for the bare text.  check_map_size: the blend backward forms
+// `index * 64 + slot` in 32 bits (blend.hip, bt_flush), so a larger map is refused everywhere.
+int check_cam(const mgs_camera* cam, const char* who = nullptr);
+int check_map_size(int32_t P, const char* who = nullptr);
 
 // ---- stage launchers (one per translation unit) ------------------------------------------
 struct StageTimer;  // api.hip

@@ -1,5 +1,5 @@
-// Gauss-Newton tracking: the normal equations of the tracking loss's rows from the pose-tangent planes (pose_tangent.h), and the
-// damped step with the SE(3) retraction and camera refresh of mgs_pose_step.  Included by pose.hip (MGS_SE3_RETRACT, camera_entry).
+// Gauss-Newton tracking: the normal equations of the tracking loss's rows from the pose-tangent planes (pose_tangent.hip), and the
+// damped step with the SE(3) retraction and camera refresh of mgs_pose_step (se3.h: MGS_SE3_RETRACT, camera_entry).
 //
 // Boundary replaced: the reference's tracker takes up to 100 Adam steps per frame on the summed gradient
 // (/root/reference/utils/slam_tracker.py:142-176, get_loss_tracking at utils/slam_utils.py:58-98); second-order steps need the
@@ -11,9 +11,8 @@
 // with the Huber weight omega = 1 if |r| <= delta else delta / |r|, formed in float32; everything else in double from the
 // per-pixel product on.  Launch 1: per-workgroup partial sums (block_sum: fixed order), launch 2: one workgroup per output
 // adds the partials in a fixed order, applies 1 / N_d and writes the system.  No atomics: bitwise reproducible.
-#pragma once
-
 #include "common.h"
+#include "se3.h"
 
 namespace mgs {
 

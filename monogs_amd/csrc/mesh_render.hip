@@ -1,6 +1,6 @@
 // Triangle-mesh rendering ("Mesh rendering"; tests/mesh_render_mirror.py restates it in float64): depth, triangle id,
-// vertex colour and face label of an indexed mesh seen by a pinhole camera.  Kernels, launcher and entry points; included by
-// exactly one unit, metrics.hip, after common.h (the manner of tile_sort.h).  No counterpart in the reference, which has no mesh.
+// vertex colour and face label of an indexed mesh seen by a pinhole camera.  Kernels, launcher and entry points; what the Depth L1
+// of metrics.hip compares.  No counterpart in the reference, which has no mesh.
 //
 //   clear    the key image to all ones
 //   setup    one lane per triangle: index check, transform, the three canonical edge vectors and the z's as ONE 64-byte record,
@@ -19,7 +19,7 @@
 // way; w_i is one fixed fma chain, whose result negates exactly with its inputs.  Two triangles that share an edge by index see the
 // same magnitude, so a ray cannot pass between them.  The image is the minimum of the keys over all hits: independent of the order
 // of execution and of the triangles, bitwise reproducible.  No host synchronisation, no read-back, kernel nodes only.
-#pragma once
+#include "common.h"
 
 namespace mgs {
 

@@ -18,7 +18,6 @@
 // one rounding of 2^-24 = 6e-8.  The psnr is formed from the double mse, then rounded once.  The count is an exact integer
 // (uint32; stored as float in the row: exact up to 2^24 elements, 5.5 megapixels).
 #include "common.h"
-#include "mesh_render.h"     // mesh rendering: what the Depth L1 below compares (kernels, launcher, entry points)
 
 namespace mgs {
 

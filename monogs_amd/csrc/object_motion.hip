@@ -1,7 +1,7 @@
 // Rigid object motion ("Object motion"; tests/object_motion_mirror.py restates it in float64): the Gaussians of up to
 // MGS_MAX_MOVING_OBJECTS objects moved by one world-frame SE(3) pose each, and the gradient of that reduced to one se(3) tangent per
-// object.  Kernels and entry points; included by exactly one unit, pose.hip, after common.h (the manner of mesh_render.h in
-// metrics.hip).  The reference moves nothing: its configs only name the dynamic ids.
+// object.  Kernels and entry points; the poses are the ones mgs_pose_step_batch (pose.hip) steps.  The reference moves nothing: its
+// configs only name the dynamic ids.
 //
 //   forward   one workgroup of 256 threads per 1024 Gaussians, four per thread 256 apart (coalesced): label -> slot through the
 //             256-entry table staged in LDS beside the poses; a moved Gaussian gets x' = R x + t as three fma per component and
@@ -17,7 +17,7 @@
 // No float atomics anywhere: the [M,6] result is a function of the inputs alone, bit for bit.  quat(R) is computed per workgroup by
 // M lanes in float64 (Shepperd's branches) and rounded once: 16 square roots against 1024 Gaussians' traffic.
 // Streaming kernels: 29 + 28 bytes per Gaussian forward (label, mean and quaternion in and out), 1 + 4 x 28 backward.
-#pragma once
+#include "common.h"
 
 namespace mgs {
 

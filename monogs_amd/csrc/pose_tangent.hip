@@ -1,7 +1,7 @@
 // Pose-tangent rendering: the per-pixel Jacobian of (R, G, B, depth, opacity) with respect to the six pose tangents
 // tau = (rho, theta) of T_cw(tau) = exp(tau^) T_cw at tau = 0 -- a FORWARD-mode pass through the rasteriser, walked through the
-// lists and survivor masks of a finished forward ("Pose tangents").  Included by features.hip: the tangent
-// blend is a feat_walk with 30 accumulators per lane and forms alpha with tile_walk.h's falloff under that unit's flags.
+// lists and survivor masks of a finished forward ("Pose tangents").  The tangent blend is a feat_walk
+// (feat_walk.h) with 30 accumulators per lane; it forms alpha with tile_walk.h's falloff and is compiled with features.hip's flags.
 //
 // Boundary replaced: the reference tracks with first-order Adam steps on the summed gradient (utils/slam_tracker.py:142-176
 // there); it has no per-pixel Jacobian.  The conventions are the backward's: decisions, radii and rectangles are constants, a
@@ -13,9 +13,8 @@
 //                                 record's log2-scaled conic (common.h), so the walk forms d power in the units of `power`.
 //   pose_tangent_blend_kernel     one 256-thread workgroup per tile, four independent waves, one pixel per lane; blend and tangent
 //                                 record of a survivor through the scalar cache; no LDS, no barriers, no atomics.
-#pragma once
-
 #include "common.h"
+#include "feat_walk.h"
 #include "tile_walk.h"
 
 namespace mgs {
@@ -261,14 +260,9 @@ extern "C" int mgs_pose_jacobian(const mgs_camera* cam, int32_t P, uint64_t num_
                                  const void* geometry, const void* binning, const void* image, void* tangent_scratch, float* J,
                                  void* stream) {
     using namespace mgs;
-    if (!cam) { set_error("mgs_pose_jacobian: camera is NULL"); return 1; }
-    if (cam->image_width <= 0 || cam->image_height <= 0) { set_error("mgs_pose_jacobian: image size must be positive"); return 1; }
-    if (!cam->bg || !cam->viewmatrix || !cam->projmatrix || !cam->projmatrix_raw || !cam->campos) {
-        set_error("mgs_pose_jacobian: camera tensors (bg, viewmatrix, projmatrix, projmatrix_raw, campos) must be non-NULL");
-        return 1;
-    }
+    if (check_cam(cam, "mgs_pose_jacobian")) return 1;
     if (P < 0) { set_error("mgs_pose_jacobian: P must be >= 0"); return 1; }
-    if (P > MGS_MAX_GAUSSIANS) { set_error("mgs_pose_jacobian: P exceeds MGS_MAX_GAUSSIANS (2^26 - 1)"); return 1; }
+    if (check_map_size(P, "mgs_pose_jacobian")) return 1;
     if (cam->sh_coeffs > 0) {
         set_error("mgs_pose_jacobian: the forward used SH colours, which depend on the camera position; only colors_precomp is supported");
         return 1;
@@ -289,9 +283,7 @@ extern "C" int mgs_pose_jacobian(const mgs_camera* cam, int32_t P, uint64_t num_
         return 1;
     }
     if (num_rendered > 0 && !binning) { set_error("mgs_pose_jacobian: binning scratch is NULL"); return 1; }
-    const GeometryState g = GeometryState::carve(const_cast<void*>(geometry), P);
-    const ImageState img = ImageState::carve(const_cast<void*>(image), W, H);
-    const BinningState b = BinningState::carve(const_cast<void*>(binning), num_rendered, W, H);
+    const auto [g, img, b] = carve_forward(geometry, binning, image, P, num_rendered, W, H);
     ScratchCursor cur(tangent_scratch);
     float* tan = cur.take<float>((size_t)P * TAN_FLOATS * sizeof(float));
 

@@ -1,5 +1,5 @@
 """A triangle mesh seen from a camera: depth, triangle id, vertex colour and face label images of an indexed mesh
-(``csrc/mesh_render.h``; the specification is DESIGN.md, "Mesh rendering"), and Depth L1, the 2-D figure of the Replica
+(``csrc/mesh_render.hip``; the specification is DESIGN.md, "Mesh rendering"), and Depth L1, the 2-D figure of the Replica
 reconstruction tables, between two meshes rendered from the same views.  No counterpart in the reference, which has no mesh.
 
 ``MeshRenderer.render`` is six launches with no host synchronisation and no read-back (capturable in a hipGraph); the image is

@@ -1,5 +1,5 @@
 """Rigid object motion: one world-frame SE(3) pose per dynamic object of the map's object layer ("Object motion";
-csrc/object_motion.h).
+csrc/object_motion.hip).
 
 The reference's configs split a scene's segment ids into ``static``, ``dynamic`` and ``masked`` objects and its map carries a row of
 object probabilities per Gaussian, but nothing in it moves a Gaussian.  Here the Gaussians whose label (``labels_of``) is one of

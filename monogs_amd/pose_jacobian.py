@@ -1,5 +1,5 @@
 """Pose-tangent rendering and the normal equations of the tracking loss (``mgs_pose_jacobian`` / ``mgs_gn_normal_equations``,
-csrc/pose_tangent.h and csrc/gauss_newton.h).
+csrc/pose_tangent.hip and csrc/gauss_newton.hip).
 
 The reference's tracker (/root/reference/utils/slam_tracker.py:142-176) only ever sees the summed gradient of its loss; a
 Gauss-Newton step needs the per-pixel Jacobian of the render with respect to the six pose tangents, a forward-mode pass:

@@ -1,5 +1,6 @@
 """What the HIP units share is stated once: the wave primitives in ``csrc/wave_ops.h`` (reached through ``common.h``), the
-order-preserving float/int map and the scratch cursor in ``common.h``.  Reads the sources only; no GPU, no library."""
+order-preserving float/int map and the scratch cursor in ``common.h``.  And what a unit is: a file with kernels or entry points
+is a ``.hip`` named in the Makefile's ``SRCS``, a header is what units include.  Reads the sources only; no GPU, no library."""
 import glob
 import os
 import re
@@ -14,6 +15,34 @@ def _sources(pattern):
         with open(path) as f:
             out[os.path.basename(path)] = f.read()
     return out
+
+
+def _makefile_srcs():
+    with open(os.path.join(CSRC, "Makefile")) as f:
+        (srcs,) = re.findall(r"^SRCS\s*=\s*(.+)$", f.read(), re.M)
+    return srcs.split()
+
+
+def _the_units():
+    """The ``*.hip`` files, which are exactly the Makefile's ``SRCS``."""
+    units, srcs = _sources("*.hip"), _makefile_srcs()
+    assert len(srcs) == len(set(srcs)), srcs
+    assert set(units) == set(srcs), set(units) ^ set(srcs)
+    assert len(units) >= 25
+    return units
+
+
+def test_the_units_are_the_makefiles_srcs():
+    _the_units()
+
+
+def test_kernels_and_entry_points_live_in_units():
+    headers = _sources("*.h")
+    assert not [name for name, text in headers.items() if 'extern "C"' in text]
+    assert {name for name, text in headers.items() if "__global__" in text} == {"common.h"}      # its two static fill kernels
+    assert len(re.findall(r"__global__", headers["common.h"])) == 2
+    for name, text in {**_sources("*.hip"), **headers}.items():
+        assert not [inc for inc in re.findall(r'^\s*#\s*include\s+["<]([^">]+)[">]', text, re.M) if inc.endswith(".hip")], name
 
 
 def test_the_xor_butterfly_is_written_in_wave_ops_only():
@@ -32,8 +61,7 @@ def test_ord2f_is_defined_once():
 def test_no_unit_pastes_the_bump_allocator():
     """``align_up(`` with a ``take`` lambda behind it is how the five copies of the allocator looked."""
     lam = re.compile(r"align_up\(.{0,400}?auto\s+take\s*=\s*\[|auto\s+take\s*=\s*\[[^\n]*align_up\(", re.S)
-    units = _sources("*.hip")
-    assert len(units) == 21
+    units = _the_units()
     assert not [name for name, text in units.items() if lam.search(text)]
 
 

@@ -12,7 +12,9 @@ COMMON = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fno-gpu-rdc",
 BLEND = ["-fno-slp-vectorize", "-Wno-inline-asm"]         # scalar blend loops; the forward clobbers M0 on purpose
 EXTRA = {
     "tsdf": [], "stereo": [], "labels": [], "ingest": [], "ssim": [], "metrics": [], "kfwindow": [],
+    "pose": [], "gauss_newton": [], "object_motion": [], "mesh_render": [],
     "features": ["-fno-slp-vectorize"], "viewer": ["-fno-slp-vectorize"],      # alpha as the blend forms it: the same code generation
+    "pose_tangent": ["-fno-slp-vectorize"],                                    # the tangent blend: alpha as features.hip forms it
     "preprocess": ["-ffp-contract=off"],                                       # the geometry that decides integers
     "blend": BLEND, "blend_stats": BLEND,
 }

@@ -1,4 +1,4 @@
-"""Mesh rendering and Depth L1 on the device (csrc/mesh_render.h, csrc/metrics.hip, monogs_amd/mesh_render.py) against the float64
+"""Mesh rendering and Depth L1 on the device (csrc/mesh_render.hip, csrc/metrics.hip, monogs_amd/mesh_render.py) against the float64
 mirror of the specification (tests/mesh_render_mirror.py) and, for the room, against the closed form of ``raycast_room``.
 
 Tolerances (tests/mesh_render_cases.py; measured by tests/test_mesh_render_host.py), at the pixels the mirror does not call ambiguous:

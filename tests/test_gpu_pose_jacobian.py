@@ -1,5 +1,5 @@
-"""Pose-tangent rendering (csrc/pose_tangent.h, ``pose_jacobian``), the normal equations and the Gauss-Newton step
-(csrc/gauss_newton.h, ``normal_equations``, ``PoseGaussNewton``) on the GPU.
+"""Pose-tangent rendering (csrc/pose_tangent.hip, ``pose_jacobian``), the normal equations and the Gauss-Newton step
+(csrc/gauss_newton.hip, ``normal_equations``, ``PoseGaussNewton``) on the GPU.
 
 Reference of the Jacobian: the float64 oracle by the double-backward construction (tests/pose_jacobian_mirror.py, checked without a
 GPU in tests/test_pose_jacobian_host.py).  Per plane, on the pixels the oracle does not flag ambiguous in float64 or in float32,

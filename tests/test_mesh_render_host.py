@@ -141,9 +141,12 @@ def test_abi_version_and_symbols(native_lib):
     assert re.search(r"#define MGS_MESH_ONE_SIDED 1\b", text) and re.search(r"#define MGS_MESH_RENDER_MAX_IMAGE 16384\b", text)
     # the struct of the binding is the header's: 2 ints, 5 pointers, 2 ints, 6 floats, an int, 3 floats, 5 pointers
     assert C.sizeof(_lib.MgsMeshRender) == 8 + 5 * 8 + 8 + 6 * 4 + 4 + 3 * 4 + 5 * 8
-    units = [f for f in os.listdir(os.path.join(ROOT, "monogs_amd", "csrc")) if f.endswith((".hip", ".h"))]
-    users = [f for f in units if '#include "mesh_render.h"' in open(os.path.join(ROOT, "monogs_amd", "csrc", f)).read()]
-    assert users == ["metrics.hip"]
+    # a unit of its own: in the Makefile's SRCS, and included by nothing
+    csrc = os.path.join(ROOT, "monogs_amd", "csrc")
+    assert os.path.isfile(os.path.join(csrc, "mesh_render.hip"))
+    assert re.search(r"^SRCS\s*=.*\bmesh_render\.hip\b", open(os.path.join(csrc, "Makefile")).read(), flags=re.M)
+    units = [f for f in os.listdir(csrc) if f.endswith((".hip", ".h"))]
+    assert not [f for f in units if re.search(r'#\s*include\s+"[^"]*mesh_render\.\w+"', open(os.path.join(csrc, f)).read())]
     from monogs_amd import mesh_render
     assert re.search(r"#define MGS_MESH_NO_SMALL 2\b", text)
     assert (mesh_render.MESH_ONE_SIDED, mesh_render.MESH_NO_SMALL) == (1, 2)

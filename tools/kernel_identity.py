@@ -6,8 +6,8 @@
 
 OLD and NEW are source trees or git revisions (a revision is unpacked with `git archive`); NEW defaults to the working
 tree, the units to every .hip of NEW's monogs_amd/csrc that OLD has too or that --from names.  `--from U=V`: unit U of NEW was
-split off unit V of OLD; its functions are looked up, by symbol, in OLD's V, and the functions that V lost must be exactly those
-that U holds.  Each unit is compiled from both trees to gfx950
+split off unit V of OLD; its functions are looked up, by symbol, in OLD's V.  Several units may come from the same V: the functions
+that V lost must be exactly those that the units split off it hold, taken together.  Each unit is compiled from both trees to gfx950
 assembly with the command its Makefile would run for that file (taken from `make -n`, so per-file flags are included),
 `-c` replaced by `--cuda-device-only -S`; no GPU needed.  The listing is cut into functions; comments go, and the
 numbers the compiler gives out in order of appearance -- `.LBB<function>_<block>` and the like -- lose the function
@@ -126,11 +126,13 @@ def main() -> int:
                 for n in sorted(group):
                     size = sum(1 for b in f[n][1] if not b.startswith(".") and not b.endswith(":"))
                     lines.append(f"  {tag:<11} {'kernel' if f[n][0] else 'func  '} {size:6d} instr  {names[n]}")
-        for unit, src in source.items():
-            if unit in found and src in lost:
-                ok = found[unit] - held[src] == lost[src]            # (both may hold common.h's static kernels)
+        for src in sorted(set(source.values()) & set(lost)):
+            split = sorted(u for u in source if source[u] == src and u in found)
+            if split:
+                took = set().union(*(found[u] for u in split)) - held[src]    # (all may hold common.h's static kernels)
+                ok = took == lost[src]
                 bad += not ok
-                lines.append(f"\n{unit}: its identical functions are {'exactly' if ok else 'NOT'} those only OLD's {src} has")
+                lines.append(f"\n{src}: the identical functions of {', '.join(split)} are {'exactly' if ok else 'NOT'} those only OLD's {src} has")
         lines.append(f"\nRESULT: {'every function of NEW is in OLD and identical' if not bad else f'{bad} functions of NEW differ from OLD'}")
     text = "\n".join(lines) + "\n"
     sys.stdout.write(text)

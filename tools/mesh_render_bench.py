@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Device time of mesh rendering (monogs_amd.mesh_render, csrc/mesh_render.h) at 640 x 480 and 1200 x 680, camera inside the room:
+"""Device time of mesh rendering (monogs_amd.mesh_render, csrc/mesh_render.hip) at 640 x 480 and 1200 x 680, camera inside the room:
 
   room_0.1    ``sequences.room_mesh(max_edge=0.1)``: about 70 k triangles of tens of pixels each;
   room_0.02   the same at 0.02: about 1.8 M triangles, scan density, sub-pixel to a few pixels each;
