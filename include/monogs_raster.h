@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define MGS_ABI_VERSION 30
+#define MGS_ABI_VERSION 31
 #define MGS_TILE 16 /* tile edge in pixels; ranges are per 16x16 tile */
 
 /* GaussianRasterizationSettings, minus `prefiltered` / `debug` which are call flags
@@ -414,6 +414,45 @@ size_t mgs_pose_tangent_bytes(int32_t P);
 int mgs_pose_jacobian(const mgs_camera* cam, int32_t P, uint64_t num_rendered, const float* means3D, const float* scales,
                       const float* rotations, const float* cov3D_precomp, const int32_t* radii, const void* geometry,
                       const void* binning, const void* image, void* tangent_scratch, float* J /* [30,H,W] */, void* stream);
+
+/* ---- Surface depth: median depth, depth variance, depth normals (ABI v31) ------------------------------------
+ * mgs_surface_depth: one more walk through the lists and the per-pixel decisions a finished forward left in its scratch
+ * ("Surface depth").  For pixel p and its contributors i = 1 .. n in blend order -- list positions
+ * 1 .. n_contrib[p] with power <= 0 and alpha >= 1/255, as mgs_features_forward -- with T_1 = 1, w_i = alpha_i T_i,
+ * t_i = T_i (1 - alpha_i) = T_(i+1) and z_i the blend record's float32 view-space depth of the Gaussian's centre:
+ *
+ *     median_depth[p] = z_m, median_id[p] = the Gaussian's index, m = the first i with t_i <= 0.5;  0 and -1 if there is none
+ *     depth_var[p]    = max(0, S2 / O - (S1 / O)^2),  O = sum w_i, S1 = sum w_i (z_i - z_1), S2 = sum w_i (z_i - z_1)^2;  0 for n = 0
+ *
+ * (m is the first contributor the forward did not count in n_touched).  Gates, on median_depth / median_id only: they become
+ * 0 / -1 where 1.0f - final_T[p] < min_opacity (the float32 opacity the forward wrote), and where max_std > 0 and
+ * depth_var[p] > max_std * max_std.  min_opacity = 0, max_std = 0 disables both.  `want`: which planes are written, a sum of the
+ * bits below; median_id may be NULL.  max_std > 0 needs MGS_SURFACE_VARIANCE and its plane.  With MGS_SURFACE_MEDIAN alone and
+ * max_std == 0 a wave leaves the walk once every pixel of its quadrant has its median or has passed its last contributor.
+ * LIFETIME: as mgs_features_forward -- `geometry`, `binning`, `image` are the scratch of a finished mgs_forward_render /
+ * _capacity for the same cam, P and num_rendered; they are only READ, on either binning path, before or after mgs_backward.
+ * No atomics, no host synchronisation, no state: capturable, and bit-reproducible.  P == 0: the requested planes are cleared
+ * (0, -1, 0), nothing else is read.  Returns 1 with a message before any launch for: a NULL plane that `want` asks for, want == 0
+ * or unknown bits, a NaN or negative min_opacity / max_std, max_std > 0 without the variance, a NULL scratch pointer with P > 0.
+ *
+ * mgs_depth_normals: the camera-frame normal of a metric depth plane (d <= 0: invalid), central differences of the
+ * back-projected pixel centres P(x, y) = d(x, y) ((x + 0.5 - cx) / fx, (y + 0.5 - cy) / fy, 1) -- the pixel centre of
+ * mgs_backproject:
+ *
+ *     n = normalize((P(x+1, y) - P(x-1, y)) x (P(x, y+1) - P(x, y-1))),  negated if n . P(x, y) > 0 (it faces the camera)
+ *
+ * and (0, 0, 0) on the image border, where any of the five depths is invalid, where max_jump > 0 and a neighbour differs from the
+ * centre depth by more than max_jump, and where the cross product has zero length.  normals is [3, H, W].  Plain IEEE float32
+ * arithmetic in the order written above, no contraction.  W, H <= 0, W x H >= 2^31, a NULL pointer, non-finite or non-positive
+ * fx / fy, a NaN cx / cy, a NaN or negative max_jump return 1 before any launch. */
+#define MGS_SURFACE_MEDIAN   1   /* median_depth (and median_id if non-NULL) */
+#define MGS_SURFACE_VARIANCE 2   /* depth_var */
+int mgs_surface_depth(const mgs_camera* cam, int32_t P, uint64_t num_rendered, const void* geometry, const void* binning,
+                      const void* image, int32_t want, float min_opacity, float max_std,
+                      float* median_depth /* [H,W] */, int32_t* median_id /* [H,W] or NULL */, float* depth_var /* [H,W] */,
+                      void* stream);
+int mgs_depth_normals(int32_t W, int32_t H, const float* depth /* [H,W] */, float fx, float fy, float cx, float cy,
+                      float max_jump, float* normals /* [3,H,W] */, void* stream);
 
 /* ---- Label loss and confusion count of the object layer (ABI v21) ----------------------------------------
  * Softmax cross-entropy of a blended K-channel image against 8-bit ids, value + gradient to the image, for learning the

@@ -33,4 +33,8 @@ def __getattr__(name):
     if name in ("MeshRenderer", "render_mesh", "eval_depth_l1", "depth_l1_row"):
         from . import mesh_render
         return getattr(mesh_render, name)
+    # median depth, depth variance, depth normals and the geometry figures (monogs_amd.surface) likewise
+    if name in ("surface_depth", "depth_normals", "eval_geometry", "SurfaceDepth"):
+        from . import surface
+        return getattr(surface, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -306,7 +306,10 @@ def _finish(s):
     world frame, or ``"room"`` for ``sequences.room_mesh``): ``mesh["reconstruction"]`` = ``mesh_eval.eval_reconstruction`` of the written
     mesh against it, ``mesh_samples`` samples each, both culled by the keyframes (their estimated poses) and their depth images.
     ``mesh_depth_l1`` (with both): ``mesh["depth_l1"]`` = ``mesh_render.eval_depth_l1`` of the two meshes over the keyframes; a monocular
-    run then culls by the rendered ground-truth mesh (``depths="render"``) instead of without an occlusion test."""
+    run then culls by the rendered ground-truth mesh (``depths="render"``) instead of without an occlusion test.
+    ``mesh_depth="median"`` fuses ``surface.surface_depth``'s median depth instead of the blended mean, gated by the spread
+    ``mesh_max_std`` (metres; 0: no gate); the entry then also holds ``depth_mode`` and ``max_std``.  ``eval_geometry`` (with ``mesh_gt``):
+    ``mesh["geometry"]`` = ``surface.eval_geometry`` of the map over the keyframes against the ground-truth mesh."""
     c, frames, gmap, intr, bg, mapper, kf_list = s.c, s.frames, s.gmap, s.intr, s.bg, s.mapper, s.kf_list
     _drop_tracking_graph(s)
     extra = {}
@@ -346,8 +349,11 @@ def _finish(s):
         extra["eager_tracking"] = eager_tracking_probe(frames, intr, gmap, bg, int(c.eager_probe))
     if c.mesh_path is not None:          # (only then: tests/golden/run_slam_contract.json pins the keys of the default flags)
         from .tsdf import mesh_from_map
-        m = mesh_from_map(gmap, [frames[k] for k in kf_list], intr, bg, float(c.mesh_voxel), path=c.mesh_path)
+        m = mesh_from_map(gmap, [frames[k] for k in kf_list], intr, bg, float(c.mesh_voxel), path=c.mesh_path,
+                          depth=c.mesh_depth, max_std=float(c.mesh_max_std))
         mesh = m.pop("mesh")
+        if c.mesh_depth != "mean":       # (the default keeps exactly the keys it always had)
+            m.update(depth_mode=c.mesh_depth, max_std=float(c.mesh_max_std))
         if c.sequence is None and c.scene == "room" and m["vertices"]:
             from .sequences import room_surface_distance
             m["accuracy_mean_m"] = float(room_surface_distance(mesh.vertices).mean())
@@ -367,6 +373,9 @@ def _finish(s):
             if c.mesh_depth_l1:
                 from .mesh_render import eval_depth_l1
                 m["depth_l1"] = eval_depth_l1(mesh, gt, kfs, intr)
+            if c.eval_geometry:
+                from .surface import eval_geometry
+                m["geometry"] = eval_geometry(gmap, kfs, intr, bg, gt_mesh=gt)
         extra["mesh"] = m
     return extra
 
@@ -429,7 +438,7 @@ def run_slam(n_frames=12, intrinsics="fr3_office", tracking_itr_num=100, mapping
              kf_selection="interval", check_viewpoints_overlap=False, kf_trace=None, refine_iters=0, eval_render=False,
              sequence=None, nr_objects=None, sensor="depth", viewer_dir=None, viewer_modes=("rgb",), viewer_every=0,
              learn_objects=0, mesh_path=None, mesh_voxel=0.02, mesh_gt=None, mesh_samples=200_000,
-             mesh_depth_l1=False, tracker="adam"):
+             mesh_depth_l1=False, tracker="adam", mesh_depth="mean", mesh_max_std=0.0, eval_geometry=False):
     """Tracks and maps a sequence in one process; returns tracking / mapping rates, iterations and the trajectory error (``_report``).
     Every argument is described where it acts: ``_setup``, ``_track_frame``, ``_select_keyframe``, ``_map_keyframe``, ``_map_window``,
     ``_finish`` (what follows the last frame).  ``log``: a callable that gets a line per frame.  ``sensor="monocular"`` adds the result
@@ -439,7 +448,8 @@ def run_slam(n_frames=12, intrinsics="fr3_office", tracking_itr_num=100, mapping
     ``learn_objects=N`` (with ``nr_objects``): learn the object rows, N trainer iterations over the window after each mapping call; only
     then does the result hold an ``objects`` entry (iterations, first and last label loss, label accuracy and mIoU).
     ``mesh_path``: write the final map's triangle mesh there (``_finish``); only then does the result hold a ``mesh`` entry;
-    with ``mesh_gt`` that entry gains ``reconstruction`` and, with ``mesh_depth_l1``, ``depth_l1`` (``_finish``).
+    with ``mesh_gt`` that entry gains ``reconstruction`` and, with ``mesh_depth_l1``, ``depth_l1`` (``_finish``); ``mesh_depth``,
+    ``mesh_max_std``, ``eval_geometry``: the depth that is fused and the map's geometry figures (``_finish``).
     ``tracker="gauss_newton"``: the second-order tracker of ``gn_tracking`` instead of Adam; only then does the result hold a ``tracker`` entry."""
     s = _setup(SimpleNamespace(**locals()))              # (every argument, by name: must stay the first statement)
     for i, vp in enumerate(s.frames):

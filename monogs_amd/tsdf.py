@@ -126,12 +126,20 @@ class TSDFVolume:
 
 
 @torch.no_grad()
-def fuse_map(gmap, viewpoints, intr, bg, volume: TSDFVolume, timing: bool = False, **integrate_kw):
+def fuse_map(gmap, viewpoints, intr, bg, volume: TSDFVolume, timing: bool = False, depth: str = "mean", max_std: float = 0.0,
+             **integrate_kw):
     """One no-grad ``render()`` of the map per viewpoint (detached activations, as ``evaluation.eval_rendering``), each integrated into
     ``volume`` with the render's ``depth`` / ``opacity`` / ``render``.  Nothing is read back.  ``{renders, integrations, readbacks}``;
-    ``timing``: also ``integrate_ms``, the device time of the integrations alone (events around each; one synchronisation at the end)."""
+    ``timing``: also ``integrate_ms``, the device time of the integrations alone (events around each; one synchronisation at the end).
+    ``depth="median"``: the render keeps its tables and the frame's depth is ``surface.surface_depth``'s median, gated by
+    ``opacity_min`` (``integrate``'s default where not given) and, with ``max_std > 0``, by the depth's spread along the ray; it is
+    integrated without an opacity plane, the gates having zeroed the pixels ``integrate`` must skip."""
     from .gaussian_optim import activate
     from .renderer import render
+    if depth not in ("mean", "median"):
+        raise ValueError(f"depth must be \"mean\" or \"median\", got {depth!r}")
+    if depth == "mean" and max_std:
+        raise ValueError("max_std gates the median depth: it needs depth=\"median\"")
     stats = dict(renders=0, integrations=0, readbacks=0)
     events = []
     if not len(gmap):
@@ -139,12 +147,21 @@ def fuse_map(gmap, viewpoints, intr, bg, volume: TSDFVolume, timing: bool = Fals
     rot, scales3, opac = activate(gmap._rotation.detach(), gmap._scaling.detach(), gmap._opacity.detach())
     xyz, feat = gmap._xyz.detach(), gmap._rgb.detach()
     for vp in viewpoints:
-        pkg = render(vp, intr, xyz, rot, scales3, opac, feat, bg)
+        if depth == "median":
+            from .surface import render_with_tables, surface_depth
+            pkg = render_with_tables(vp, intr, (xyz, rot, scales3, opac, feat), bg)
+            median = surface_depth(pkg["render"], want=("median", "variance") if max_std > 0 else ("median",),
+                                   min_opacity=integrate_kw.get("opacity_min", 0.9), max_std=max_std).median
+        else:
+            pkg = render(vp, intr, xyz, rot, scales3, opac, feat, bg)
         stats["renders"] += 1
         if timing:
             events.append((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
             events[-1][0].record()
-        volume.integrate(pkg["depth"], vp, None, intr, rgb=pkg["render"], opacity=pkg["opacity"], **integrate_kw)
+        if depth == "median":
+            volume.integrate(median, vp, None, intr, rgb=pkg["render"], opacity=None, **integrate_kw)
+        else:
+            volume.integrate(pkg["depth"], vp, None, intr, rgb=pkg["render"], opacity=pkg["opacity"], **integrate_kw)
         if timing:
             events[-1][1].record()
         stats["integrations"] += 1
@@ -154,10 +171,12 @@ def fuse_map(gmap, viewpoints, intr, bg, volume: TSDFVolume, timing: bool = Fals
     return stats
 
 
-def mesh_from_map(gmap, viewpoints, intr, bg, voxel: float, path: Optional[str] = None, max_voxels: int = 1 << 29) -> dict:
+def mesh_from_map(gmap, viewpoints, intr, bg, voxel: float, path: Optional[str] = None, max_voxels: int = 1 << 29,
+                  depth: str = "mean", max_std: float = 0.0) -> dict:
     """What ``run_slam(mesh_path=...)`` does at the end of a run: a volume over the bounds of the map's centres (padded by the
     truncation distance), ``fuse_map`` over ``viewpoints``, ``extract``, and the PLY at ``path``.  Returns ``{path, vertices, triangles,
-    voxel, integrate_ms, extract_ms, mesh}``.  The bounds are read back (six floats): this runs once, after the run."""
+    voxel, integrate_ms, extract_ms, mesh}``.  The bounds are read back (six floats): this runs once, after the run.  ``depth``,
+    ``max_std``: as ``fuse_map``."""
     import time
     from .ply_io import save_mesh_ply
     if not len(gmap):
@@ -171,7 +190,7 @@ def mesh_from_map(gmap, viewpoints, intr, bg, voxel: float, path: Optional[str] 
     if n > max_voxels:
         raise ValueError(f"a {voxel} m grid over the map's bounds {lo} .. {hi} has {n} voxels (limit {max_voxels}): choose a larger voxel")
     vol = TSDFVolume.for_bounds(lo, hi, float(voxel), xyz.device)
-    stats = fuse_map(gmap, viewpoints, intr, bg, vol, timing=True)
+    stats = fuse_map(gmap, viewpoints, intr, bg, vol, timing=True, depth=depth, max_std=max_std)
     torch.cuda.synchronize(xyz.device)
     t0 = time.perf_counter()
     mesh = vol.extract()

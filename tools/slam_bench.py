@@ -17,6 +17,8 @@ stand-in; the TUM / Replica sequences are not available offline).  Prints one JS
       # ... and scored against the ground-truth mesh: accuracy, completion, completion ratio, Chamfer-L1, F-score (monogs_amd.mesh_eval)
   python tools/slam_bench.py --config tum --room --graph --mesh room.ply --mesh-gt room --mesh-depth-l1
       # ... and Depth L1 between the two meshes rendered from the keyframes (monogs_amd.mesh_render)
+  python tools/slam_bench.py --config tum --room --graph --mesh room.ply --mesh-gt room --mesh-depth median [--mesh-max-std 0.05] --eval-geometry
+      # ... fused from the median depth instead of the blended mean, and the map's depth and normals against the ground truth (monogs_amd.surface)
   python tools/slam_bench.py --config tum --room --graph --tracker gauss_newton
       # the Gauss-Newton tracker (monogs_amd.gn_tracking) instead of Adam: fewer, heavier tracking iterations per frame
 """
@@ -93,6 +95,14 @@ if __name__ == "__main__":
     ap.add_argument("--mesh-depth-l1", action="store_true",
                     help="with --mesh-gt: `mesh` gains `depth_l1`, the two meshes rendered from the keyframes and compared "
                          "(monogs_amd.mesh_render.eval_depth_l1)")
+    ap.add_argument("--mesh-depth", default="mean", choices=["mean", "median"],
+                    help="with --mesh: the depth that is fused -- the alpha-blended mean over the opacity, or the median depth of "
+                         "monogs_amd.surface (the contributor at which the transmittance falls through one half); `mesh` gains `depth_mode`")
+    ap.add_argument("--mesh-max-std", type=float, default=0.0, metavar="S",
+                    help="with --mesh-depth median: skip pixels whose depth along the ray spreads by more than S metres (0: no gate)")
+    ap.add_argument("--eval-geometry", action="store_true",
+                    help="with --mesh-gt: `mesh` gains `geometry`, the L1 of the mean and of the median depth and the angle of their "
+                         "normals against the ground-truth mesh rendered from the keyframes (monogs_amd.surface.eval_geometry)")
     ap.add_argument("--tracker", default="adam", choices=["adam", "gauss_newton"],
                     help="gauss_newton: track with second-order steps on the pose-tangent planes (monogs_amd.gn_tracking) instead of "
                          "Adam; the result gains `tracker`, compare `track_iters_per_frame` and `tracking_fps`")
@@ -101,6 +111,12 @@ if __name__ == "__main__":
         ap.error("--mesh-gt evaluates the mesh --mesh writes")
     if a.mesh_depth_l1 and not a.mesh_gt:
         ap.error("--mesh-depth-l1 compares the mesh with --mesh-gt")
+    if a.mesh_depth != "mean" and not a.mesh:
+        ap.error("--mesh-depth chooses what --mesh fuses")
+    if a.mesh_max_std and a.mesh_depth != "median":
+        ap.error("--mesh-max-std gates the median depth: it needs --mesh-depth median")
+    if a.eval_geometry and not a.mesh_gt:
+        ap.error("--eval-geometry compares the map with --mesh-gt")
     from monogs_amd.slam_harness import run_slam
     cfg = dict(CONFIGS[a.config])
     init_iters = a.init_iters
@@ -137,6 +153,8 @@ if __name__ == "__main__":
                    **(dict(mesh_path=a.mesh, mesh_voxel=a.mesh_voxel) if a.mesh else {}),
                    **(dict(mesh_gt=a.mesh_gt, mesh_samples=a.mesh_samples) if a.mesh_gt else {}),
                    **(dict(mesh_depth_l1=True) if a.mesh_depth_l1 else {}),
+                   **(dict(mesh_depth=a.mesh_depth, mesh_max_std=a.mesh_max_std) if a.mesh_depth != "mean" else {}),
+                   **(dict(eval_geometry=True) if a.eval_geometry else {}),
                    **(dict(tracker=a.tracker) if a.tracker != "adam" else {}))
     what = f"{a.dataset}, every {a.stride}. frame" if a.dataset else f"synthetic {a.config}-like sequence"
     out["workload"] = f"{what}, {a.frames} frames" + (" (fork's hard-coded run configuration)" if a.fork else "")
